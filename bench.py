@@ -3,7 +3,7 @@
 
 Metric (BASELINE.json): restored-audio seconds per wall-second (RTF^-1).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload NAME]
+    python bench.py [--gpus N --steps K --warmup W] [--workload NAME] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks
@@ -85,7 +85,12 @@ def parse():
                          "an identity stub; the line says dry_run_cpu and its value means nothing")
     ap.add_argument("--tuning", type=int, default=0, help="vfx_config.tuning mask (include/vfx.h VFX_TUNE_*); 0 = the shipped kernel selection")
     ap.add_argument("--precision", type=int, default=2, help="0 = exact fp32 MFMA, 1 = split-bf16 (hi+lo, 3 bf16 MFMAs), 2 = ResUNet split-bf16 + vocoder fp16 (1 MFMA per product)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32, at most 64 MB in "
+                         "all: a fixed, seeded sample of the clips when larger), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     d_clips, d_sec, d_cpu = {"gsr16x10": (16, 10.0, 2), "sharded1024": (128, 10.0, 0), "ssr_sr64": (64, 3.0, 1),
                              "stream1s": (1, 1.0, 1)}[args.workload]
     args.clips = args.clips or d_clips
@@ -664,6 +669,14 @@ class Workload:
         self.step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)] if ev else []
         return dt
 
+    def outputs(self):
+        """What a caller of the timed path received from its last step: {name: (B, L) tensor}."""
+        if self.wl == "gsr16x10":
+            return {"wav": self.out}
+        if self.wl == "sharded1024":
+            return {"wav": self.gathered[0]} if self.rank == 0 else {}
+        return {"wav": self.holder[0]}
+
     def flags(self):
         """The handle's sticky flags after the timed region: a 16-bit vocoder whose activations left the fp16 range, or a
         negative mel, makes the measurement INVALID (bench.py times the raw entry point, not the re-running wrapper)."""
@@ -681,6 +694,33 @@ def dtype_string(gsr, precision, tuning=0):
     return {0: "f32", 1: "bf16x3 (split-bf16 operands hi+lo, fp32 accumulate)",
             2: "f16 (vocoder: fp16 operands, 1 MFMA per product, %s; ResUNet: split-bf16 hi+lo; fp32 accumulate)" % trunk
             if gsr else "bf16x3 (split-bf16 operands hi+lo, fp32 accumulate)"}[precision]
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: budget of all files together
+
+
+def dump_outputs(outputs, path, budget=DUMP_BYTES):
+    """--dump-outputs: every output as path/<name>.npy in float32.  An output larger than its share of `budget` is cut to a
+    fixed, seeded sample of its rows (clips), sorted; the result line records which.  Returns the line's `dump_outputs` entry."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(len(outputs), 1) - 4096     # room for the .npy header
+    files = {}
+    for name, t in outputs.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        entry = {"shape": list(a.shape), "dtype": "float32"}
+        if a.nbytes > share:
+            if a.ndim >= 2 and a[0].nbytes <= share:
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // a[0].nbytes, replace=False))
+                a = a[rows]
+                entry["sampled_rows"] = rows.tolist()
+            else:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+                a = a.reshape(-1)[idx]
+                entry["sampled_flat_elements"] = {"count": int(idx.size), "seed": 0}
+            entry["written_shape"] = list(a.shape)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        files[name] = entry
+    return {"dir": os.path.abspath(path), "files": files}
 
 
 def step_stats(step_ms, sclk_mhz):
@@ -833,6 +873,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     flags = w.flags()
+    # the outputs of the last timed step, before anything below reuses the output buffers
+    dumped = dump_outputs(w.outputs(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     res = None
     failed = None
@@ -850,6 +892,8 @@ def main():
             "rccl_ranks": rccl_ranks, "dry_run_cpu": bool(args.dry_run_cpu), "negative_input_flag": int(flags["negative_input"]), "f16_saturated": flags["f16_saturated"],
         }
         res.update(w.extra)
+        if dumped:
+            res["dump_outputs"] = dumped
         res["power"] = sampler.result()
         res.update(step_stats(w.step_ms, (res["power"] or {}).get("avg_sclk_mhz")))
         if flags["f16_saturated"]:

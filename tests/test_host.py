@@ -462,6 +462,42 @@ def test_bench_rank_plumbing_dry_run_two_ranks(workload, launcher):
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`--dump-outputs DIR` writes what the timed path returned in its last step, float32, the same on every run of the same
+    arguments; `--steps` is the number of timed steps.  The --dry-run-cpu stub restores as the identity, so the dump is the
+    seeded input clips themselves."""
+    import json
+    from voicefixer_main_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dry-run-cpu", "--clips", "3", "--seconds", "0.2", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, env=env, timeout=300, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dump_outputs"]["files"]["wav"]["shape"] == [3, 8820]
+        assert sorted(os.listdir(d)) == ["wav.npy"]
+        got.append(np.load(d / "wav.npy"))
+    assert got[0].dtype == np.float32 and np.array_equal(got[0], got[1])
+    assert np.array_equal(got[0], synth.make_clips(3, 0.2, seed=1234)[:, 0])
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path):
+    """An output over the 64 MB budget is cut to a fixed, seeded sample of whole clips, the same every time."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    t = torch.arange(128 * 441000, dtype=torch.float32).reshape(128, 441000)
+    e1 = bench.dump_outputs({"wav": t}, str(tmp_path / "a"))["files"]["wav"]
+    e2 = bench.dump_outputs({"wav": t}, str(tmp_path / "b"))["files"]["wav"]
+    assert e1 == e2 and os.path.getsize(tmp_path / "a" / "wav.npy") <= bench.DUMP_BYTES
+    a = np.load(tmp_path / "a" / "wav.npy")
+    assert a.shape == (len(e1["sampled_rows"]), 441000) and np.array_equal(a, t.numpy()[e1["sampled_rows"]])
+
+
 def test_length_bucketing_in_a_world_of_one():
     """dist.restore_sharded_lengths without a process group = the single-GPU length-bucketing helper: clips of equal length share
     a call (at most max_batch), the results come back in file order."""
