@@ -37,7 +37,9 @@ typedef struct vfx_handle vfx_handle;
 
 /* model ids for weights / plans */
 enum { VFX_MODEL_UNET_MEL = 0, VFX_MODEL_UNET_SPEC = 1, VFX_MODEL_VOCODER = 2,
-       VFX_MODEL_FRONTEND = 3 /* buffers of f_helper / mel: "mel.fb" (1025,128) */ };
+       VFX_MODEL_FRONTEND = 3, /* buffers of f_helper / mel: "mel.fb" (1025,128) */
+       VFX_MODEL_GRU_MEL = 4,  /* the bi_gru analysis module of Generator (gsr_voicefixer.py:59-68) */
+       VFX_MODEL_DNN_MEL = 5   /* the dnn analysis module (gsr_voicefixer.py:69-87) */ };
 
 /* sticky device-side flags returned by vfx_take_flags */
 enum {
@@ -169,6 +171,18 @@ int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int
  * (models/components/unet.py:60-103): linear mel (B, T, 128) >= 0 -> log10 mel (B, T, 128). */
 int vfx_resunet_mel(vfx_handle* h, const float* mel_linear, int B, int T, float* logmel_out,
                     void* stream);
+
+/* Generator.forward of models/gsr_voicefixer.py:86-91 with ANY analysis module (`model` = VFX_MODEL_UNET_MEL, _GRU_MEL or
+ * _DNN_MEL): linear mel (B, T, 128) >= 0 -> log10 mel estimate (B, T, 128).  frames (HOST array of B, or NULL = all T): clip b
+ * has frames[b] <= T live rows, gets what its own call with T = frames[b] computes (the backward GRU starts at ITS last frame)
+ * and zero rows past them.  The ResUNet takes frames = NULL only.  The tensor names of the bi_gru / dnn weights are the reference
+ * keys without the "generator.analysis_module." prefix ("1.weight", "2.gru.weight_hh_l0_reverse", ...). */
+int vfx_analysis_mel(vfx_handle* h, int model, const float* mel_linear, int B, int T, const int* frames, float* logmel_out,
+                     void* stream);
+
+/* The analysis module vfx_restore_gsr and vfx_restore_gsr_varlen run: VFX_MODEL_UNET_MEL (the default), _GRU_MEL or _DNN_MEL;
+ * its weights must be finalized.  A GRU / DNN module runs once over a whole varlen batch with the clips' frame counts. */
+int vfx_select_analysis(vfx_handle* h, int model);
 
 /* UNetResComplex_100Mb.forward of models/components/unet_v2.py:86-148 (ssr_unet / gsr_unet):
  * sp (B, T, 1025), wav (B, L) -> wav_out (B, L). */

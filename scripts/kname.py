@@ -33,6 +33,8 @@ def short(n, width=40):
         return "k_up16<%s> f16" % ", ".join(args)
     if name == "k_block2d32":                            # round 6: the persistent C = 32 ConvBlockRes of ResUNet level 1
         return "k_block2d<32, 4>"
+    if name in ("k_dense", "k_gru_seq"):                # the bi_gru / dnn analysis modules (analysis.hip): one Linear; one GRU layer
+        return name
     if name == "k_resblock" and len(args) >= 2:
         hi = len(args) >= 3 and args[2] == "true"
         return "k_resblock<%s, %s>%s" % (args[0], args[1], " f16" if hi else "")

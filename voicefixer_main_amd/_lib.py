@@ -14,7 +14,7 @@ TEST_LIB_PATH = os.path.join(HERE, "libvfx_test.so")
 CSRC = os.path.join(HERE, "csrc")
 
 VFX_MAX_STAGES = 8
-MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER, MODEL_FRONTEND = 0, 1, 2, 3
+MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER, MODEL_FRONTEND, MODEL_GRU_MEL, MODEL_DNN_MEL = 0, 1, 2, 3, 4, 5
 # vfx_config.tuning bits (include/vfx.h)
 TUNE_NO_FUSED_STACKS, TUNE_NO_FUSED_WIDE, TUNE_NO_FUSED_UNET, TUNE_NO_PERSISTENT_C64, TUNE_NO_PAIRS, TUNE_NO_SPLITK, \
     TUNE_F32_TRUNK, TUNE_SMALL_2D_TILES, TUNE_DEBUG_POISON_ARENA, TUNE_NO_FUSED_UPSAMPLERS, TUNE_OLD_BLOCK2D, \
@@ -55,6 +55,8 @@ SIGNATURES = {
     "vfx_chunk_ola": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_void_p, c_void_p]),
     "vfx_resunet_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "vfx_analysis_mel": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_select_analysis": (c_int, [c_void_p, c_int]),
     "vfx_resunet_spec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_vocoder_out_len": (c_int64, [c_void_p, c_int]),
     "vfx_vocoder": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -889,8 +889,9 @@ int vfx_create(int device, const vfx_config* cfg, vfx_handle** out) {
   }
   h->d_flags = static_cast<int*>(h->blob.alloc(sizeof(int)));
   VFX_HIP(hipMemset(h->d_flags, 0, sizeof(int)));
-  h->d_lens = static_cast<int*>(h->blob.alloc(9 * kMaxVarlenClips * sizeof(int)));  // rows 0-2: the batch; 3-5: the ResUNet group, 6-8: the vocoder run in flight
-  VFX_HIP(hipMemset(h->d_lens, 0, 9 * kMaxVarlenClips * sizeof(int)));
+  // rows 0-2: the batch; 3-5: the ResUNet group, 6-8: the vocoder run in flight; 9: frames of a vfx_analysis_mel call
+  h->d_lens = static_cast<int*>(h->blob.alloc(10 * kMaxVarlenClips * sizeof(int)));
+  VFX_HIP(hipMemset(h->d_lens, 0, 10 * kMaxVarlenClips * sizeof(int)));
   *out = h.release();
   VFX_API_END
 }
@@ -913,7 +914,7 @@ int vfx_destroy(vfx_handle* h) {
 int vfx_load_tensor(vfx_handle* h, int model, const char* name, const float* data, const int64_t* shape, int ndim) {
   VFX_API_BEGIN
   VFX_CHECK(h && name && data, "vfx_load_tensor: NULL argument");
-  VFX_CHECK(model >= 0 && model <= VFX_MODEL_FRONTEND, "vfx_load_tensor: bad model id %d", model);
+  VFX_CHECK(model >= 0 && model <= VFX_MODEL_DNN_MEL, "vfx_load_tensor: bad model id %d", model);
   HostTensor t;
   int64_t n = 1;
   for (int i = 0; i < ndim; ++i) {
@@ -932,6 +933,9 @@ int vfx_finalize_weights(vfx_handle* h, int model) {
     h->unet[model] = build_unet_weights(h, model);
   } else if (model == VFX_MODEL_VOCODER) {
     h->voc = build_vocoder_weights(h);
+  } else if (model == VFX_MODEL_GRU_MEL || model == VFX_MODEL_DNN_MEL) {
+    h->analysis[model - VFX_MODEL_GRU_MEL] = nullptr;
+    h->analysis[model - VFX_MODEL_GRU_MEL] = build_analysis_weights(h, model);
   } else if (model == VFX_MODEL_FRONTEND) {
     auto it = h->staged[model].find("mel.fb");
     if (it != h->staged[model].end()) {
@@ -1148,6 +1152,7 @@ size_t vfx_workspace_bytes(vfx_handle* h, int model, int B, int T) {
     if (model == VFX_MODEL_UNET_MEL) build_unet_mel(pb, B, T, ext(0), ext(1));
     else if (model == VFX_MODEL_UNET_SPEC) build_unet_spec(pb, B, T, ext(0), ext(1), ext(2), ext(3), ext(4));
     else if (model == VFX_MODEL_VOCODER) build_vocoder(pb, B, T, ext(0), ext(1));
+    else if (model == VFX_MODEL_GRU_MEL || model == VFX_MODEL_DNN_MEL) build_analysis_mel(pb, model, B, T, ext(0), ext(1));
     else return 0;
     return pb.arena.high;
   } catch (...) {
@@ -1208,6 +1213,66 @@ static int vfx_resunet_mel_1(vfx_handle* h, const float* mel_linear, int B, int 
   debug_poison(h, *plan, stream);
   RunCtx ctx{static_cast<hipStream_t>(stream), {const_cast<float*>(mel_linear), logmel_out}, h->d_flags, &h->prof};
   plan->run(ctx);
+  VFX_API_END
+}
+
+// Generator.forward with the bi_gru / dnn module (analysis.hip); the ResUNet goes through vfx_resunet_mel.  frames (HOST) are copied
+// into row 9 of the handle's per-clip table (a row of its own), in stream order, for kMaxVarlenClips clips per launch set.
+static int vfx_analysis_mel_1(vfx_handle* h, int model, const float* mel_linear, int B, int T, const int* frames, float* logmel_out,
+                              void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(h && mel_linear && logmel_out && B > 0 && T > 0, "bad argument");
+  VFX_CHECK(h->analysis[model - VFX_MODEL_GRU_MEL], "vfx_analysis_mel: weights of the %s module are not finalized",
+            model == VFX_MODEL_GRU_MEL ? "bi_gru" : "dnn");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_f = h->d_lens + 9 * kMaxVarlenClips;
+  if (frames) {
+    for (int b = 0; b < B; ++b)
+      VFX_CHECK(frames[b] >= 1 && frames[b] <= T, "vfx_analysis_mel: clip %d has %d frames (need 1 <= frames <= T = %d)", b, frames[b], T);
+    launch_set_frames(d_f, frames, B, s);
+  }
+  auto plan = get_plan(h, key_of(model == VFX_MODEL_GRU_MEL ? "gru_mel" : "dnn_mel", B, T, frames ? 1 : 0), [&](PlanBuilder& pb) {
+    if (frames) pb.lens_t = d_f;
+    build_analysis_mel(pb, model, B, T, ext(0), ext(1));
+  }, stream);
+  debug_poison(h, *plan, stream);
+  RunCtx ctx{s, {const_cast<float*>(mel_linear), logmel_out}, h->d_flags, &h->prof};
+  plan->run(ctx);
+  VFX_API_END
+}
+
+int vfx_analysis_mel(vfx_handle* h, int model, const float* mel_linear, int B, int T, const int* frames, float* logmel_out,
+                     void* stream) {
+  if (model == VFX_MODEL_UNET_MEL) {
+    if (frames) {
+      set_error("vfx_analysis_mel: the ResUNet takes no per-clip frame counts (frames must be NULL)");
+      return 1;
+    }
+    return vfx_resunet_mel(h, mel_linear, B, T, logmel_out, stream);
+  }
+  if (model != VFX_MODEL_GRU_MEL && model != VFX_MODEL_DNN_MEL) {
+    set_error("vfx_analysis_mel: model %d is not an analysis module", model);
+    return 1;
+  }
+  if (!h || B <= 0 || T <= 0) return vfx_analysis_mel_1(h, model, mel_linear, B, T, frames, logmel_out, stream);
+  for (int b = 0; b < B; b += kMaxVarlenClips) {
+    const int rc = vfx_analysis_mel_1(h, model, mel_linear + (int64_t)b * T * 128, std::min(kMaxVarlenClips, B - b), T,
+                                      frames ? frames + b : nullptr, logmel_out + (int64_t)b * T * 128, stream);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int vfx_select_analysis(vfx_handle* h, int model) {
+  VFX_API_BEGIN_H(h)
+  if (model == VFX_MODEL_UNET_MEL) {
+    VFX_CHECK(h->unet[VFX_MODEL_UNET_MEL], "vfx_select_analysis: weights of the mel ResUNet are not finalized");
+  } else {
+    VFX_CHECK(model == VFX_MODEL_GRU_MEL || model == VFX_MODEL_DNN_MEL, "vfx_select_analysis: model %d is not an analysis module", model);
+    VFX_CHECK(h->analysis[model - VFX_MODEL_GRU_MEL], "vfx_select_analysis: weights of the %s module are not finalized",
+              model == VFX_MODEL_GRU_MEL ? "bi_gru" : "dnn");
+  }
+  h->analysis_model = model;
   VFX_API_END
 }
 
@@ -1299,14 +1364,16 @@ static int vfx_restore_gsr_1(vfx_handle* h, const float* wav, int B, int L, floa
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(h && wav && wav_out && B > 0, "bad argument");
   VFX_CHECK(L > h->cfg.n_fft / 2, "vfx_restore_gsr: clip too short for reflect padding (L=%d)", L);
-  VFX_CHECK(h->unet[VFX_MODEL_UNET_MEL] && h->voc, "vfx_restore_gsr: weights are not finalized");
+  const int am = h->analysis_model;
+  VFX_CHECK((am == VFX_MODEL_UNET_MEL ? (bool)h->unet[am] : (bool)h->analysis[am - VFX_MODEL_GRU_MEL]) && h->voc,
+            "vfx_restore_gsr: weights are not finalized");
   const int T = frames_of(h, L);
   const int64_t Llong = vocoder_out_len(h->cfg, T);
   const int unify = flags & 1;
   // keyed on L, not on T: the plan's launches hold the sample count (STFT row stride and reflection point, trim_center) -- two
   // clips with the same frame count and different lengths must not share it (rounds 1-4 keyed on T: the second of two such
   // clips on one handle was framed and trimmed with the first one's length; found by the varlen comparison of round 5)
-  auto plan = get_plan(h, key_of("restore_gsr", B, L, unify), [&](PlanBuilder& pb) {
+  auto plan = get_plan(h, key_of("restore_gsr", B, L, unify + 2 * am), [&](PlanBuilder& pb) {
     const int64_t nmel = (int64_t)B * T * 128;
     const size_t o_mel = pb.alloc_f(nmel), o_log = pb.alloc_f(nmel), o_den = pb.alloc_f(nmel);
     const size_t o_long = pb.alloc_f((int64_t)B * Llong), o_ws = pb.alloc_f(2 * B + 64), o_pk = pb.alloc_f(B + 64);
@@ -1317,7 +1384,8 @@ static int vfx_restore_gsr_1(vfx_handle* h, const float* wav, int B, int L, floa
       launch_stft_mel(hh->fe, c.ext[0], B, L, T, reinterpret_cast<float*>(pl->bound_base + o_mel), nullptr, nullptr,
                       nullptr, 0, hh->cfg.hop, 1e-8f, c.stream);
     });
-    build_unet_mel(pb, B, T, arena_buf(o_mel), arena_buf(o_log));
+    if (am == VFX_MODEL_UNET_MEL) build_unet_mel(pb, B, T, arena_buf(o_mel), arena_buf(o_log));
+    else build_analysis_mel(pb, am, B, T, arena_buf(o_mel), arena_buf(o_log));
     pl->ops.push_back([=](const RunCtx& c) {
       float* lg = reinterpret_cast<float*>(pl->bound_base + o_log);
       if (c.ext[2]) VFX_HIP(hipMemcpyAsync(c.ext[2], lg, sizeof(float) * nmel, hipMemcpyDeviceToDevice, c.stream));
@@ -1390,7 +1458,9 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
                                     float* logmel_out, int flags, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(h && wav && wav_out && lengths && B > 0 && B <= kMaxVarlenClips, "bad argument");
-  VFX_CHECK(h->unet[VFX_MODEL_UNET_MEL] && h->voc, "vfx_restore_gsr_varlen: weights are not finalized");
+  const int am = h->analysis_model;
+  VFX_CHECK((am == VFX_MODEL_UNET_MEL ? (bool)h->unet[am] : (bool)h->analysis[am - VFX_MODEL_GRU_MEL]) && h->voc,
+            "vfx_restore_gsr_varlen: weights are not finalized");
   const int hop = h->cfg.hop;
   const int T = frames_of(h, Lmax);
   std::vector<int> host(3 * (size_t)B);
@@ -1443,6 +1513,7 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   int64_t gmax = 0, vmel = 0, vlong = 0;
   int nmax = 0;
   for (auto& kv : groups) {
+    if (am != VFX_MODEL_UNET_MEL) break;   // a GRU / DNN module runs on the batch tensors themselves
     const int step = std::max(1, max_clips_per_launch(h, kv.first, true, false, false) / 4 * 4);
     gmax = std::max<int64_t>(gmax, (int64_t)std::min(padded_group((int)kv.second.size()), step) * kv.first * 128);
   }
@@ -1469,6 +1540,17 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   launch_stft_mel(h->fe, wav, B, Lmax, T, mel, nullptr, nullptr, nullptr, 0, hop, 1e-8f, s, d_l);
   // ---- the mel ResUNet, one launch set per padded frame count (unet.py:75-77 pads every clip to ITS multiple of 64 frames): the
   // group's clips -- wherever they sit in the batch -- are gathered into a compact (Bg, Tpad, 128) tensor, restored, scattered back
+  // ---- a GRU / DNN module: ONE run over the whole padded batch with the clips' own frame counts (row 1 of the table)
+  if (am != VFX_MODEL_UNET_MEL) {
+    auto plan = get_plan(h, key_of(am == VFX_MODEL_GRU_MEL ? "gru_mel_vl" : "dnn_mel_vl", B, T), [&](PlanBuilder& pb) {
+      pb.lens_t = d_t;
+      build_analysis_mel(pb, am, B, T, ext(0), ext(1));
+    }, stream);
+    debug_poison(h, *plan, stream);
+    RunCtx ctx{s, {mel, lg}, h->d_flags, &h->prof};
+    plan->run(ctx);
+    groups.clear();
+  }
   for (auto& kv : groups) {
     const int Tg = kv.first;
     const std::vector<int>& idx = kv.second;

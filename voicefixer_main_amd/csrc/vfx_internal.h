@@ -569,6 +569,20 @@ struct VocConvW {
   int mode = 0;  // pack_conv mode the weights were packed with (follows the form of the source tensor in the plan)
 };
 
+// Linear layers and GRUs of the bi_gru / dnn analysis modules (analysis.hip)
+struct DenseW {
+  int K = 0, N = 0;
+  float* wT = nullptr;    // (K, N): the weight transposed
+  float* bias = nullptr;  // (N)
+};
+struct AnalysisWeights {
+  int model = 0;
+  std::vector<DenseW> dense;  // bi_gru: Linear 1, GRU projections of layers 1 / 2 (N = 1536), Linear 4, 6; dnn: Linear 0, 3, .., 12, 14
+  float bn_scale[4] = {1.f, 1.f, 1.f, 1.f}, bn_shift[4] = {0.f, 0.f, 0.f, 0.f};  // the BatchNorm2d(1) scalars in module order
+  float* whhT[2] = {nullptr, nullptr};  // per GRU layer: (2 directions, 256, 768) W_hh transposed
+  float* bhn[2] = {nullptr, nullptr};   // per GRU layer: (2, 256) b_hn
+};
+
 struct VocoderWeights {
   std::vector<VocConvW> cond;   // k3 convs
   VocConvW pre;                 // k7 reflect
@@ -600,19 +614,22 @@ void launch_or_flags(int* flags, int bits, hipStream_t s);  // small_ops.hip: fl
 struct vfx_handle {
   int device = 0;
   vfx_config cfg{};
-  std::map<std::string, vfx::HostTensor> staged[4];
+  std::map<std::string, vfx::HostTensor> staged[6];
   vfx::FrontEndTables fe;
   vfx::DeviceBlob blob;  // front-end tables + weights
   std::shared_ptr<vfx::UNetWeights> unet[2];
   std::shared_ptr<vfx::VocoderWeights> voc;
+  std::shared_ptr<vfx::AnalysisWeights> analysis[2];  // VFX_MODEL_GRU_MEL, VFX_MODEL_DNN_MEL
+  int analysis_model = VFX_MODEL_UNET_MEL;             // what vfx_restore_gsr(_varlen) runs (vfx_select_analysis)
   std::map<std::string, std::shared_ptr<vfx::Plan>> plans;  // at most kMaxCachedPlans, least recently used evicted
   std::vector<std::shared_ptr<vfx::Plan>> retired;  // evicted plans whose device blocks are freed in batches (get_plan)
   uint64_t plan_tick = 0;
   char* arena = nullptr;
   size_t arena_bytes = 0;
   int* d_flags = nullptr;
-  int* d_lens = nullptr;     // [6][kMaxVarlenClips]: samples / frames / vocoder frames per clip of the varlen call in flight; frames /
-                             // batch index of the clips of its ResUNet group in flight (row 5 unused)
+  int* d_lens = nullptr;     // [10][kMaxVarlenClips]: rows 0-2 samples / frames / vocoder frames per clip of the varlen call in flight;
+                             // rows 3-4 frames / batch index of the clips of its ResUNet group in flight (5 unused); rows 6-8 samples /
+                             // frames / vocoder frames of its vocoder run in flight; row 9 frames per clip of a vfx_analysis_mel call
   char* scratch = nullptr;   // the tensors between the plans of a varlen call (api.cpp: ensure_scratch), grow-only
   size_t scratch_bytes = 0;
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
@@ -626,6 +643,7 @@ void set_mel_filterbank(vfx_handle* h, const float* fb /*1025x128*/);
 void bind_plan(vfx_handle* h, Plan& plan);  // ensures the arena is large enough and rebases the plan on it
 std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model);
 std::shared_ptr<VocoderWeights> build_vocoder_weights(vfx_handle* h);
+std::shared_ptr<AnalysisWeights> build_analysis_weights(vfx_handle* h, int model);
 
 // plan builders: append the ops of one stage to `pb`.  Buffers named *_off are arena byte
 // offsets; ext slots index RunCtx::ext.
@@ -638,5 +656,9 @@ struct BufRef {
 void build_unet_mel(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef logmel_out);
 void build_unet_spec(PlanBuilder& pb, int B, int T, BufRef sp, BufRef cosb, BufRef sinb, BufRef re_out, BufRef im_out);
 void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_out, const BufRef* peak = nullptr);
+// bi_gru / dnn Generator.forward: linear mel (B,T,128) -> log-mel (B,T,128); pb.lens_t (frames per clip) or all T
+void build_analysis_mel(PlanBuilder& pb, int model, int B, int T, BufRef mel_linear, BufRef logmel_out);
+// d[0 .. B) = host[0 .. B) in stream order (kernel arguments: legal inside a stream capture); one row, unlike launch_set_lens
+void launch_set_frames(int* d, const int* host, int B, hipStream_t s);
 int64_t vocoder_out_len(const vfx_config& cfg, int T);
 }  // namespace vfx

@@ -9,7 +9,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MODEL_FRONTEND, MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER
+from ._lib import MODEL_DNN_MEL, MODEL_FRONTEND, MODEL_GRU_MEL, MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER  # noqa: F401
+
+ANALYSIS_MODELS = (MODEL_UNET_MEL, MODEL_GRU_MEL, MODEL_DNN_MEL)
 
 N_BINS = 1025
 N_MELS = 128
@@ -54,6 +56,7 @@ class Engine:
         self.loaded = set()
         self._state = {}        # model id -> (state_dict, prefix) as loaded, for the stricter-arithmetic twin
         self._strict = None
+        self.analysis_model = MODEL_UNET_MEL   # what restore_gsr(_varlen) runs (select_analysis)
 
     def close(self):
         if getattr(self, "_strict", None) is not None:
@@ -119,6 +122,8 @@ class Engine:
             twin = Engine(self.device, config=cfg)
             for model, (sd, prefix) in self._state.items():
                 twin.load_state_dict(model, sd, prefix)
+            if self.analysis_model != MODEL_UNET_MEL:
+                twin.select_analysis(self.analysis_model)
             self._strict = twin
         return self._strict
 
@@ -242,6 +247,30 @@ class Engine:
         out = torch.empty_like(mel)
         _lib.check(self.lib.vfx_resunet_mel(self.h, _ptr(mel), B, T, _ptr(out), self._stream()), "vfx_resunet_mel")
         return out
+
+    def analysis_mel(self, model, mel_linear, frames=None):
+        """Generator.forward with analysis module `model` (MODEL_UNET_MEL, MODEL_GRU_MEL or MODEL_DNN_MEL): linear mel (B,T,128)
+        -> log10 mel estimate (B,T,128).  `frames` (B ints, or None = all T): clip b has frames[b] live rows; its result is that of
+        its own call on them, rows past them are zero (the ResUNet takes None only)."""
+        mel = _dev_f32(mel_linear, self.device)
+        B, T, _ = mel.shape
+        out = torch.empty_like(mel)
+        arr = None
+        if frames is not None:
+            frames = [int(v) for v in frames]
+            if len(frames) != B:
+                raise ValueError("analysis_mel: %d frame counts for %d clips" % (len(frames), B))
+            arr = (ctypes.c_int * B)(*frames)
+        _lib.check(self.lib.vfx_analysis_mel(self.h, int(model), _ptr(mel), B, T, arr, _ptr(out), self._stream()),
+                   "vfx_analysis_mel")
+        return out
+
+    def select_analysis(self, model):
+        """The analysis module restore_gsr / restore_gsr_varlen run (default MODEL_UNET_MEL); its weights must be loaded."""
+        _lib.check(self.lib.vfx_select_analysis(self.h, int(model)), "vfx_select_analysis")
+        self.analysis_model = int(model)
+        if self._strict is not None:
+            self._strict.select_analysis(model)
 
     def resunet_spec(self, sp, wav):
         sp, wav = _dev_f32(sp, self.device), _dev_f32(wav, self.device)

@@ -24,7 +24,7 @@ import pickle
 import numpy as np
 import torch
 
-from .engine import Engine, MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER
+from .engine import Engine, MODEL_DNN_MEL, MODEL_GRU_MEL, MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER
 
 EPS = 1e-8
 
@@ -268,15 +268,20 @@ class _PickleModule:
     __name__ = "pickle"
 
 
-def read_checkpoint(path):
-    """Lightning .ckpt (``{'state_dict': ..., 'hyper_parameters': ...}``, eval_gsr_voicefixer.py:33), a GAN-style container
-    (``{'generator': state_dict, ...}``: the pip vocoder's own file; ``{'model': ...}``) or a bare state_dict file ->
-    state_dict of CPU tensors.  Tries torch's `weights_only` reader first; a file that only fails there because it pickles
-    project classes is re-read with the allow-listing unpickler above (nothing the file names is imported or executed)."""
+def _load_checkpoint_obj(path):
     try:
-        obj = torch.load(path, map_location="cpu", weights_only=True)
+        return torch.load(path, map_location="cpu", weights_only=True)
     except pickle.UnpicklingError:
-        obj = torch.load(path, map_location="cpu", weights_only=False, pickle_module=_PickleModule)
+        return torch.load(path, map_location="cpu", weights_only=False, pickle_module=_PickleModule)
+
+
+def _checkpoint_hp(obj):
+    """The `hyper_parameters["hp"]` a Lightning checkpoint object saved (`save_hyperparameters()`, gsr_voicefixer.py:106), or None."""
+    hyper = obj.get("hyper_parameters") if isinstance(obj, dict) else None
+    return _hp_get(hyper, "hp") if hyper is not None else None
+
+
+def _state_dict_of(obj, path):
     sd = obj
     for key in ("state_dict", "generator", "model"):
         if isinstance(obj, dict) and isinstance(obj.get(key), dict) and obj[key] and \
@@ -286,6 +291,14 @@ def read_checkpoint(path):
     if not isinstance(sd, dict) or not sd or not all(isinstance(v, torch.Tensor) for v in sd.values()):
         raise ValueError("%s holds no state_dict of tensors" % path)
     return sd
+
+
+def read_checkpoint(path):
+    """Lightning .ckpt (``{'state_dict': ..., 'hyper_parameters': ...}``, eval_gsr_voicefixer.py:33), a GAN-style container
+    (``{'generator': state_dict, ...}``: the pip vocoder's own file; ``{'model': ...}``) or a bare state_dict file ->
+    state_dict of CPU tensors.  Tries torch's `weights_only` reader first; a file that only fails there because it pickles
+    project classes is re-read with the allow-listing unpickler above (nothing the file names is imported or executed)."""
+    return _state_dict_of(_load_checkpoint_obj(path), path)
 
 
 class _Base:
@@ -335,19 +348,95 @@ class _Base:
         return self
 
 
-class VoiceFixer(_Base):
-    """models/gsr_voicefixer.py:93-193 (inference surface): mel ResUNet + TFGAN vocoder."""
+ANALYSIS_PREFIX = "generator.analysis_module."
+ANALYSIS_SWITCHES = ("unet", "unet_small", "bi_gru", "dnn")   # the order Generator.__init__ tests them (gsr_voicefixer.py:46-87)
+ANALYSIS_MODEL_IDS = {"unet": MODEL_UNET_MEL, "bi_gru": MODEL_GRU_MEL, "dnn": MODEL_DNN_MEL}
+_MODULE_OF_ID = {v: k for k, v in ANALYSIS_MODEL_IDS.items()}
 
-    unet_prefix = "generator.analysis_module."
+
+def analysis_module_from_keys(keys, prefix=ANALYSIS_PREFIX):
+    """'unet', 'bi_gru' or 'dnn' by the state-dict keys of Generator.analysis_module, or None when there are none."""
+    keys = list(keys)
+    has = lambda sfx: any(k == prefix + sfx or k == sfx for k in keys)
+    if has("2.gru.weight_hh_l0"):
+        return "bi_gru"
+    if has("14.weight"):
+        return "dnn"
+    if any(k.startswith(prefix + "encoder_block1.") or k.startswith("encoder_block1.") for k in keys):
+        return "unet"
+    return None
+
+
+def analysis_module_from_hp(hp):
+    """The module Generator.__init__ builds for `hp` ('unet_small' is the same network as 'unet'), or None when `hp` has no
+    switches or switches none on (Generator.__init__ then builds no module: nothing to cross-check).  Refuses mel_freq_bins != 128."""
+    sw = _hp_get(hp, "task", "gsr", "gsr_model", "voicefixer")
+    if sw is None:
+        return None
+    n_mel = _hp_get(hp, "model", "mel_freq_bins", default=128)
+    if int(n_mel) != 128:
+        raise ValueError("mel_freq_bins = %s: the analysis modules are implemented for 128 mel bins only" % n_mel)
+    for name in ANALYSIS_SWITCHES:
+        if _hp_get(sw, name, default=False):
+            return "unet" if name == "unet_small" else name
+    return None
+
+
+def select_analysis_module(keys, hp=None, ckpt_hp=None, prefix=ANALYSIS_PREFIX):
+    """The analysis module of a VoiceFixer checkpoint: decided by its weights, cross-checked against the model's hp and the hp the
+    checkpoint saved.  A switch that disagrees with the weights raises ValueError naming both."""
+    by_keys = analysis_module_from_keys(keys, prefix)
+    for what, h in (("hp", hp), ("the checkpoint's hyper_parameters['hp']", ckpt_hp)):
+        if h is None:
+            continue
+        by_hp = analysis_module_from_hp(h)
+        if by_hp is not None and by_keys is not None and by_hp != by_keys:
+            raise ValueError("%s selects the '%s' analysis module but the weights are those of '%s'" % (what, by_hp, by_keys))
+    return by_keys
+
+
+class VoiceFixer(_Base):
+    """models/gsr_voicefixer.py:93-193 (inference surface): analysis module (mel ResUNet, bi_gru or dnn) + TFGAN vocoder."""
+
+    unet_prefix = ANALYSIS_PREFIX
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._ckpt_hp = None
+
+    @property
+    def analysis_module(self):
+        """'unet', 'bi_gru' or 'dnn': the module the ENGINE has selected (the one source of truth: a model built on another
+        handle -- the handlers' split-bf16 twin -- runs what that handle selected)."""
+        return _MODULE_OF_ID[self.engine.analysis_model]
+
+    def load_from_checkpoint(self, ckpt):
+        obj = _load_checkpoint_obj(ckpt)        # read once: the state_dict and the hp the checkpoint saved
+        self._ckpt_hp = _checkpoint_hp(obj)
+        try:
+            self.load_state_dict(_state_dict_of(obj, ckpt))
+        finally:
+            self._ckpt_hp = None
+        return self
 
     def load_state_dict(self, sd, strict=True):
         keys = list(sd.keys())
-        if any(k.startswith(self.unet_prefix) for k in keys):
+        module = select_analysis_module(keys, self.hp, self._ckpt_hp, self.unet_prefix)
+        if module in ("bi_gru", "dnn"):
+            mid = ANALYSIS_MODEL_IDS[module]
+            if any(k.startswith(self.unet_prefix) for k in keys):
+                self.engine.load_state_dict(mid, sd, self.unet_prefix)
+            else:
+                self.engine.load_state_dict(mid, {k: v for k, v in sd.items() if k[:1].isdigit()})
+            self.engine.select_analysis(mid)
+        elif any(k.startswith(self.unet_prefix) for k in keys):
             self.engine.load_state_dict(MODEL_UNET_MEL, sd, self.unet_prefix)
         elif any(k.startswith("encoder_block1.") for k in keys):
             self.engine.load_state_dict(MODEL_UNET_MEL, sd)
         elif strict:
             raise KeyError("no ResUNet weights ('%s*') in the state_dict" % self.unet_prefix)
+        if module == "unet" and self.engine.analysis_model != MODEL_UNET_MEL:
+            self.engine.select_analysis(MODEL_UNET_MEL)
         for pfx in ("vocoder.model.", "vocoder."):
             sub = {k[len(pfx):]: v for k, v in sd.items() if k.startswith(pfx)}
             if any(k.startswith("condnet.") for k in sub):
@@ -360,7 +449,11 @@ class VoiceFixer(_Base):
     def forward(self, mel_orig, check=True):
         """mel_orig (B,1,T,128) linear, non-negative -> {'mel': log10 estimate}  (Generator.forward,
         gsr_voicefixer.py:86-91).  `check` reproduces to_log's assert (one device sync)."""
-        out = self.engine.resunet_mel(mel_orig[:, 0])[:, None]
+        mid = self.engine.analysis_model
+        if mid != MODEL_UNET_MEL:
+            out = self.engine.analysis_mel(mid, mel_orig[:, 0])[:, None]
+        else:
+            out = self.engine.resunet_mel(mel_orig[:, 0])[:, None]
         if check:
             # to_log's assert; a saturation bit left by a deferred vocoder check (Vocoder.__call__(check=False), raw engine calls)
             # is NOT consumed here -- it stays raised for that check

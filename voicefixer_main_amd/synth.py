@@ -218,3 +218,57 @@ def make_clips(n_clips, seconds, seed=1234, mode="noise", distinct=8, sr=SAMPLE_
     for i in range(n_clips):
         out[i, 0] = degrade(bases[i % len(bases)], seed + i, mode, sr)
     return out
+
+
+# ----------------------------------------------------------------------------
+# bi_gru / dnn analysis modules of Generator (models/gsr_voicefixer.py:59-87)
+# ----------------------------------------------------------------------------
+def _scalar_bn(out, p, gen, mean, var):
+    """BatchNorm2d(1) with randomized eval statistics (a folding bug of the scalar affine must show)."""
+    u = lambda lo, hi: torch.empty(1).uniform_(lo, hi, generator=gen)
+    out[p + ".weight"] = u(0.6, 1.4)
+    out[p + ".bias"] = u(-0.3, 0.3)
+    out[p + ".running_mean"] = u(*mean)
+    out[p + ".running_var"] = u(*var)
+    out[p + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+
+def _linear(out, p, n_in, n_out, gen):
+    bound = 1.0 / np.sqrt(n_in)
+    out[p + ".weight"] = torch.empty(n_out, n_in).uniform_(-bound, bound, generator=gen)
+    out[p + ".bias"] = torch.empty(n_out).uniform_(-0.2, 0.2, generator=gen)   # non-zero: a misplaced bias must show
+
+
+def make_gru_analysis_state_dict(seed=2):
+    """state_dict of the bi_gru analysis module (nn.Sequential keys, without the 'generator.analysis_module.' prefix): scalar BNs
+    with random statistics, nn.GRU-style uniform(+-1/sqrt(256)) weights and NON-zero biases (b_hn included: it sits inside
+    r * (W_hn h + b_hn) and a kernel that folds it with b_in must fail)."""
+    gen = torch.Generator().manual_seed(seed)
+    out = OrderedDict()
+    _scalar_bn(out, "0", gen, (-4.0, -2.0), (2.0, 6.0))    # on to_log(mel): values around -8 .. 2
+    _linear(out, "1", 128, 256, gen)
+    _scalar_bn(out, "2.bn", gen, (-0.3, 0.3), (0.3, 1.5))
+    k = 1.0 / np.sqrt(256)
+    for layer, n_in in ((0, 256), (1, 512)):
+        for sfx in ("", "_reverse"):
+            s = "_l%d%s" % (layer, sfx)
+            out["2.gru.weight_ih" + s] = torch.empty(768, n_in).uniform_(-k, k, generator=gen)
+            out["2.gru.weight_hh" + s] = torch.empty(768, 256).uniform_(-k, k, generator=gen)
+            out["2.gru.bias_ih" + s] = torch.empty(768).uniform_(-k, k, generator=gen)
+            out["2.gru.bias_hh" + s] = torch.empty(768).uniform_(-k, k, generator=gen)
+    _linear(out, "4", 512, 256, gen)
+    _linear(out, "6", 256, 128, gen)
+    return out
+
+
+def make_dnn_analysis_state_dict(seed=3):
+    """state_dict of the dnn analysis module (keys as make_gru_analysis_state_dict)."""
+    gen = torch.Generator().manual_seed(seed)
+    out = OrderedDict()
+    widths = (128, 256, 512, 1024, 512, 256, 128)
+    for i in range(6):
+        p = 3 * i if i < 5 else 14
+        _linear(out, str(p), widths[i], widths[i + 1], gen)
+        if i < 4:
+            _scalar_bn(out, str(p + 2), gen, (0.2, 0.6), (0.1, 0.5))   # after a ReLU: non-negative inputs
+    return out
