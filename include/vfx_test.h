@@ -72,6 +72,37 @@ int vfx_op_block2d(vfx_handle* h, const float* x, int B, int H, int W, int C, co
                    const float* sc1, const float* sh1, const float* w2, const float* sc2,
                    const float* sh2, float slope, float* y, void* stream);
 
+/* The vocoder's launches exactly as its plan builds them (vocoder.cpp: the same builder functions), for tests/test_gpu_vocoder_launches.py.
+ * Activations are channels-last fp32 tensors on the device; weights and biases in PyTorch layout on the HOST; lens: NULL or a HOST
+ * array [B] of per-clip lengths in the launch's input positions (a clip's sequence ends there, as in a varlen batch).
+ *
+ * vfx_op_voc_upsample: ConvTranspose1d(k = 2 stride, stride, padding stride / 2 + stride % 2, output_padding stride % 2) of
+ *   x (B, T, Cin) -> (B, T * stride, Cin / 2), weight (Cin, Cin / 2, 2 stride), bias (Cin / 2), as ONE phased launch -- on k_up16 where
+ *   the plan picks it (*used_up16 = 1), else on the phased k_conv.  src_act = 0: the launch reads x through its LeakyReLU(up_slope)
+ *   prologue; 1: it reads the ACTIVATED form of LeakyReLU(x, up_slope), built here in the handle's operand form (16-bit mode: fp16).
+ *   want_raw: the raw fp32 output into y; want_act: the activated output LeakyReLU(., act_slope) (act_slope = 1: the fp16 trunk of the
+ *   16-bit mode) into ya, widened to fp32 from the stored form.  ya starts as NaN patterns; y is the caller's (fill it first). */
+int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, int Cin, const float* weight, const float* bias, int stride,
+                        float up_slope, int src_act, int want_raw, int want_act, float act_slope, const int* lens, float* y, float* ya,
+                        int* used_up16, void* stream);
+/* vfx_op_voc_conv1d: Conv1d (K = 3 or 7, dilation dil, zero 'same' padding or -- reflect -- ReflectionPad1d(K / 2)) of
+ *   x (B, T, Cin) -> (B, T, Cout), weight (Cout, Cin, K), bias (Cout).  Prologue act (0 none, 1 LeakyReLU(slope), 2 ELU) applied by the
+ *   launch (src_act = 0) or already in the activated source built here (src_act = 1).  residual (B, T, Cout) on the device or NULL;
+ *   residual_act: the launch reads it as the activated fp16 trunk fp16(LeakyReLU(residual, voc_res_slope)) of the 16-bit mode and
+ *   inverts it.  Outputs: raw fp32 into y (want_raw) and / or activated next_act(., next_slope) into ya (as for vfx_op_voc_upsample). */
+int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, int Cin, const float* weight, const float* bias, int Cout, int K, int dil,
+                      int reflect, int src_act, int act, float slope, const float* residual, int residual_act, int want_raw, int next_act,
+                      float next_slope, const int* lens, float* y, float* ya, void* stream);
+/* vfx_op_voc_final: the vocoder tail tanh(conv1d(ReflectionPad1d(3)(LeakyReLU(x, slope)), weight (1, C, 7)) + bias) of x (B, T, C)
+ *   -> wav (B, T); x_f16: the tail reads x as an fp16 trunk (converted here).  With lens, clip b reflects at its own end and its samples
+ *   from lens[b] on are not written. */
+int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const float* weight, float bias, float slope, int x_f16,
+                     const int* lens, float* wav, void* stream);
+/* Host-only: the kernel the vocoder plan runs a Cin -> Cout = Cin / 2 upsampler of stride s over T input positions on (a stage behind the
+ * first and not the last, in precision mode `precision` with vfx_config.tuning = `tuning`): 1 = k_up16, 0 = the phased k_conv,
+ * -1 = bad arguments. */
+int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, int precision, int tuning);
+
 #ifdef __cplusplus
 }
 #endif

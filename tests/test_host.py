@@ -528,13 +528,18 @@ def test_store_hazard_checker_sees_the_pattern(tmp_path):
         "imm": ("buffer_store_dwordx4 v[0:3], v9, s[16:19], 0 offen\n v_pk_add_f32 v[0:1], v[4:5], v[60:61]\n", 0),
         "other_regs": ("buffer_store_dwordx4 v[0:3], v9, s[16:19], s79 offen\n v_pk_add_f32 v[4:5], v[4:5], v[60:61]\n", 0),
         "x2": ("buffer_store_dwordx2 v[0:1], v9, s[16:19], s79 offen\n v_mov_b32_e32 v0, v1\n", 0),
+        # a wave that ends early: the kernel goes on past its first s_endpgm, and so must the scan
+        "after_early_endpgm": ("s_cbranch_scc1 .LBB0_2\n s_endpgm\n.LBB0_2:\n buffer_store_dwordx4 v[0:3], v9, s[16:19], s79 offen\n"
+                               " v_pk_add_f32 v[0:1], v[4:5], v[60:61]\n", 1),
     }
     for name, (body, hits) in cases.items():
         f = tmp_path / (name + ".s")
-        f.write_text(head + body + " s_endpgm\n")
+        f.write_text(head + body + " s_endpgm\n.Lfunc_end0:\n .size _ZN3vfx6k_testEv, .Lfunc_end0-_ZN3vfx6k_testEv\n")
         r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "asm_store_hazard_check.py"), str(f)], capture_output=True, text=True)
         assert r.returncode == (1 if hits else 0), (name, r.stdout)
         assert ("%d unfenced" % hits) in r.stdout, (name, r.stdout)
+        n_store = 0 if name == "x2" else 1
+        assert "_ZN3vfx6k_testEv: %d x3/x4 store(s) scanned, %d with a register soffset" % (n_store, 0 if name == "imm" else n_store) in r.stdout, (name, r.stdout)
 
 
 def test_no_compiler_touch_of_inflight_weight_registers(tmp_path):
@@ -583,12 +588,34 @@ def test_no_compiler_touch_of_inflight_weight_registers(tmp_path):
         # that hazard for immediate soffsets only, gfx950 has it for both (profiles/r06_store_data_hazard.md)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "asm_store_hazard_check.py"), out], capture_output=True, text=True)
         assert r.returncode == 0, (name, r.stdout[-2000:])
+        if name in ("resblock_w64.hip", "upsample16.hip", "block2d32.hip"):
+            # the kernels with 16-byte buffer stores: the scan reached them (k_resblock_w64 ends a wave early, ~70 lines into a 7000-line
+            # function, and a scan that stopped at the first s_endpgm saw none of its 80 stores)
+            counts = re.findall(r"\n(_ZN3vfx\w+): (\d+) x3/x4 store\(s\) scanned", "\n" + r.stdout)
+            assert counts and all(int(c) > 0 for _, c in counts), (name, r.stdout[-2000:])
         if name == "block2d32.hip":
             # the interior tile loop of k_block2d32 is spill-free: no scratch access between the first and the last MFMA of the loop body
             body = asm[asm.index("v_mfma_f32_32x32x16_bf16"):asm.rindex("v_mfma_f32_32x32x16_bf16")]
             blocks = re.split(r"\n\.LBB\d+_\d+:", body)
             mfma_blocks = [b for b in blocks if b.count("v_mfma") >= 100]
             assert mfma_blocks and all("scratch_" not in b for b in mfma_blocks), "k_block2d32: the convolution blocks spill"
+
+
+def test_vocoder_upsampler_kernel_selection():
+    """The kernel the vocoder plan runs an upsampler on (PlanBuilder::add_conv_phased: upsample16_ok and not
+    VFX_TUNE_NO_FUSED_UPSAMPLERS): k_up16 in the 16-bit mode for Cin = 128 and 256 only; never in the split-bf16 or fp32 modes, never
+    with VFX_TUNE_NO_FUSED_UPSAMPLERS."""
+    from voicefixer_main_amd import _lib
+    lib = _lib.load_test()
+    for s in (2, 3, 4, 5, 7, 9):
+        for T in (1, 127, 128, 129, 7546):
+            for cin in (128, 256, 512, 1024):
+                assert lib.vfx_plan_voc_upsampler_kernel(cin, cin // 2, s, T, 2, 0) == (1 if cin in (128, 256) else 0), (cin, s, T)
+                for precision in (0, 1):
+                    assert lib.vfx_plan_voc_upsampler_kernel(cin, cin // 2, s, T, precision, 0) == 0, (precision, cin, s, T)
+                for precision in (0, 1, 2):
+                    assert lib.vfx_plan_voc_upsampler_kernel(cin, cin // 2, s, T, precision, _lib.TUNE_NO_FUSED_UPSAMPLERS) == 0
+    assert lib.vfx_plan_voc_upsampler_kernel(128, 128, 3, 10, 2, 0) == -1  # Cout != Cin / 2
 
 
 def test_committed_bench_line_follows_the_contract():

@@ -88,6 +88,13 @@ TEST_SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "vfx_op_block2d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "vfx_op_voc_upsample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_int,
+                                    c_float, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "vfx_op_voc_conv1d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_float, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfx_op_voc_final": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
+    "vfx_plan_voc_upsampler_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

@@ -594,7 +594,7 @@ void PlanBuilder::add_conv_phased(TapConvParams p, const std::vector<TapSeg>& ph
   const double fl = 2.0 * (double)hp.M * hp.cout_phase * k;
   plan->conv_flops += fl - conv_flops(hp);
   hp.flops_override = fl;
-  hp.up16 = (!(h->cfg.tuning & VFX_TUNE_NO_FUSED_UPSAMPLERS) && upsample16_ok(hp)) ? 1 : 0;
+  hp.up16 = upsample16_selected(hp, phases) ? 1 : 0;
 }
 
 void PlanBuilder::add_resblock(ResBlockParams p) {

@@ -2,6 +2,7 @@
 // They pack PyTorch-layout weights on the fly, run one kernel family of libvfx.so and synchronise.  Not part of the product
 // library: built into its own shared object that resolves the internals it uses from libvfx.so.
 #include <cmath>
+#include <cstring>
 
 #include "vfx_internal.h"
 #include "vfx_test.h"
@@ -666,4 +667,213 @@ extern "C" int vfx_op_conv_transpose(vfx_handle* h, const float* x, int B, int H
     return 1;
   }
   return 0;
+}
+
+// ---- the vocoder's launches as the plan builds them (vocoder.cpp: voc_upsample_params, voc_conv1d_params, launch_voc_final) --------
+namespace {
+uint16_t bf16_rne_host(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+float bf16_to_f32_host(uint16_t b) {
+  const uint32_t u = (uint32_t)b << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+float act_host(float v, int act, float slope) {
+  if (act == ACT_ELU) return v > 0.f ? v : expm1f(v);
+  if (act == ACT_LEAKY) return v > 0.f ? v : v * slope;
+  return v;
+}
+
+// Device fp32 tensor (npix, C) -> its ACTIVATED form act(x) in the handle's operand form (TapConvParams::out_act): 16-bit mode an fp16
+// tensor, split-bf16 per pixel and 32-channel chunk [32 hi bf16 | 32 lo bf16] (lo = bf16(v - hi)), fp32 the activated floats.
+float* to_device_act(const vfx_handle* h, DeviceBlob& blob, const float* dx, size_t npix, int C, int act, float slope) {
+  const size_t n = npix * C;
+  std::vector<float> hx(n);
+  VFX_HIP(hipMemcpy(hx.data(), dx, n * sizeof(float), hipMemcpyDeviceToHost));
+  for (float& v : hx) v = act_host(v, act, slope);
+  if (h->cfg.precision == 2) {
+    std::vector<_Float16> hh(n);
+    for (size_t i = 0; i < n; ++i) hh[i] = (_Float16)std::min(std::max(hx[i], -65504.f), 65504.f);
+    void* d = blob.alloc(n * sizeof(_Float16));
+    VFX_HIP(hipMemcpy(d, hh.data(), n * sizeof(_Float16), hipMemcpyHostToDevice));
+    return static_cast<float*>(d);
+  }
+  if (h->cfg.precision == 1) {
+    std::vector<uint16_t> q(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const size_t base = i / 32 * 64, c = i % 32;  // (C % 32 == 0: a chunk never straddles two pixels)
+      const uint16_t hi = bf16_rne_host(hx[i]);
+      q[base + c] = hi;
+      q[base + 32 + c] = bf16_rne_host(hx[i] - bf16_to_f32_host(hi));
+    }
+    void* d = blob.alloc(q.size() * sizeof(uint16_t));
+    VFX_HIP(hipMemcpy(d, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return static_cast<float*>(d);
+  }
+  return blob.upload(hx.data(), n);
+}
+// bytes of an activated tensor of n elements in the handle's operand form
+size_t act_bytes(const vfx_handle* h, size_t n) { return h->cfg.precision == 2 ? n * 2 : n * 4; }
+// ... and back: the caller's fp32 tensor receives the stored values (fp16 widened, hi + lo, fp32), NaN patterns included
+void act_to_f32(const vfx_handle* h, const float* dact, size_t n, float* dy) {
+  std::vector<float> hy(n);
+  if (h->cfg.precision == 2) {
+    std::vector<_Float16> hh(n);
+    VFX_HIP(hipMemcpy(hh.data(), dact, n * sizeof(_Float16), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) hy[i] = (float)hh[i];
+  } else if (h->cfg.precision == 1) {
+    std::vector<uint16_t> q(2 * n);
+    VFX_HIP(hipMemcpy(q.data(), dact, q.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+      const size_t base = i / 32 * 64, c = i % 32;
+      hy[i] = bf16_to_f32_host(q[base + c]) + bf16_to_f32_host(q[base + 32 + c]);
+    }
+  } else {
+    VFX_HIP(hipMemcpy(hy.data(), dact, n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  VFX_HIP(hipMemcpy(dy, hy.data(), n * sizeof(float), hipMemcpyHostToDevice));
+}
+const int* upload_lens(DeviceBlob& blob, const int* lens, int B) {
+  return lens ? blob.upload_i(std::vector<int>(lens, lens + B)) : nullptr;
+}
+// a tap convolution set up the way PlanBuilder::add_conv does it for the vocoder (no split-K: PlanBuilder::no_splitk)
+void run_voc_conv(vfx_handle* h, TapConvParams& p, DeviceBlob& blob, hipStream_t s) {
+  p.split = h->cfg.precision != 0;
+  p.flags = h->d_flags;
+  p.tuning = h->cfg.tuning;
+  finish_params(p);
+  std::vector<ConvStage> st(p.nstages);
+  build_stages(p, h->d_ones, h->d_zeros, st.data());
+  ConvStage* ds = static_cast<ConvStage*>(blob.alloc(st.size() * sizeof(ConvStage)));
+  VFX_HIP(hipMemcpy(ds, st.data(), st.size() * sizeof(ConvStage), hipMemcpyHostToDevice));
+  p.stages = ds;
+  p.ksplit = 0;
+  TapConvParams* d = static_cast<TapConvParams*>(blob.alloc(sizeof(TapConvParams)));
+  VFX_HIP(hipMemcpy(d, &p, sizeof(p), hipMemcpyHostToDevice));
+  launch_conv(p, d, s);
+}
+}  // namespace
+
+extern "C" int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, int Cin, const float* weight, const float* bias, int stride,
+                                   float up_slope, int src_act, int want_raw, int want_act, float act_slope, const int* lens, float* y,
+                                   float* ya, int* used_up16, void* stream) {
+  try {
+    VFX_CHECK(h && x && weight && bias && B > 0 && T > 0 && stride >= 1 && Cin % 64 == 0 && (want_raw || want_act) && (!want_raw || y) &&
+                  (!want_act || ya),
+              "vfx_op_voc_upsample: bad argument");
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    vfx_config cfg = h->cfg;
+    cfg.voc_up_slope = up_slope;
+    const int Cout = Cin / 2;
+    const size_t nout = (size_t)B * T * stride * Cout;
+    const VocConvW up = pack_voc_upsampler(cfg, sc.blob, weight, bias, Cin, stride, src_act != 0);
+    const float* src = src_act ? to_device_act(h, sc.blob, x, (size_t)B * T, Cin, ACT_LEAKY, up_slope) : x;
+    float* dact = nullptr;
+    if (want_act) {  // NaN patterns (0xff bytes in every form): what the launch leaves unwritten stays NaN
+      dact = static_cast<float*>(sc.blob.alloc(act_bytes(h, nout)));
+      VFX_HIP(hipMemset(dact, 0xff, act_bytes(h, nout)));
+    }
+    std::vector<TapSeg> phases;
+    TapConvParams p = voc_upsample_params(cfg, up, stride, B, T, src, src_act != 0, want_raw ? y : nullptr, dact, act_slope,
+                                          upload_lens(sc.blob, lens, B), 1, phases);
+    // the rest of PlanBuilder::add_conv_phased + bind_plan, with the plan's kernel choice
+    p.split = h->cfg.precision != 0;
+    p.flags = h->d_flags;
+    p.tuning = h->cfg.tuning;
+    p.nphase = stride;
+    p.cout_phase = Cout;
+    finish_params(p);
+    VFX_CHECK(!p.per_tap, "phased conv: the union of the phases' taps does not fit one patch");
+    p.ksplit = 0;
+    p.up16 = upsample16_selected(p, phases) ? 1 : 0;
+    std::vector<ConvStage> st((size_t)p.nstages * p.nphase);
+    for (int r = 0; r < p.nphase; ++r) {
+      TapConvParams q = p;
+      q.seg[0] = phases[r];
+      build_stages(q, h->d_ones, h->d_zeros, st.data() + (size_t)r * p.nstages);
+    }
+    ConvStage* ds = static_cast<ConvStage*>(sc.blob.alloc(st.size() * sizeof(ConvStage)));
+    VFX_HIP(hipMemcpy(ds, st.data(), st.size() * sizeof(ConvStage), hipMemcpyHostToDevice));
+    p.stages = ds;
+    TapConvParams* d = static_cast<TapConvParams*>(sc.blob.alloc(sizeof(TapConvParams)));
+    VFX_HIP(hipMemcpy(d, &p, sizeof(p), hipMemcpyHostToDevice));
+    launch_conv(p, d, s);
+    VFX_HIP(hipStreamSynchronize(s));
+    if (dact) act_to_f32(h, dact, nout, ya);
+    if (used_up16) *used_up16 = p.up16;
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, int Cin, const float* weight, const float* bias, int Cout,
+                                 int K, int dil, int reflect, int src_act, int act, float slope, const float* residual, int residual_act,
+                                 int want_raw, int next_act, float next_slope, const int* lens, float* y, float* ya, void* stream) {
+  try {
+    VFX_CHECK(h && x && weight && bias && B > 0 && T > 0 && (K == 3 || K == 7) && dil >= 1 && (want_raw || next_act != ACT_NONE) &&
+                  (!want_raw || y) && (next_act == ACT_NONE || ya) && (!residual_act || residual),
+              "vfx_op_voc_conv1d: bad argument");
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const vfx_config& cfg = h->cfg;
+    const size_t nout = (size_t)B * T * Cout;
+    const VocConvW cw = pack_voc_conv1d(cfg, sc.blob, weight, bias, Cin, Cout, K, src_act != 0);
+    const float* src = src_act ? to_device_act(h, sc.blob, x, (size_t)B * T, Cin, act, slope) : x;
+    // residual_act: the activated fp16 trunk fp16(LeakyReLU(residual, res_slope)) of the 16-bit mode
+    const float* res = residual && residual_act ? to_device_f16(sc.blob, residual, nout, cfg.voc_res_slope) : residual;
+    float* dact = nullptr;
+    if (next_act != ACT_NONE) {
+      dact = static_cast<float*>(sc.blob.alloc(act_bytes(h, nout)));
+      VFX_HIP(hipMemset(dact, 0xff, act_bytes(h, nout)));
+    }
+    TapConvParams p = voc_conv1d_params(cfg, cw, B, T, K, dil, reflect != 0, src, src_act != 0, act, slope, res, residual_act != 0,
+                                        want_raw ? y : nullptr, dact, next_act, next_slope, upload_lens(sc.blob, lens, B), 1);
+    run_voc_conv(h, p, sc.blob, s);
+    VFX_HIP(hipStreamSynchronize(s));
+    if (dact) act_to_f32(h, dact, nout, ya);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const float* weight, float bias, float slope, int x_f16,
+                                const int* lens, float* wav, void* stream) {
+  try {
+    VFX_CHECK(h && x && weight && wav && B > 0 && T > 0, "vfx_op_voc_final: bad argument");
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    std::vector<float> wt(7 * (size_t)C);  // (1, C, 7) -> [7][C], as build_vocoder_weights packs the final conv
+    for (int k = 0; k < 7; ++k)
+      for (int ch = 0; ch < C; ++ch) wt[k * C + ch] = weight[ch * 7 + k];
+    const float* src = x_f16 ? to_device_f16(sc.blob, x, (size_t)B * T * C, 1.f) : x;
+    launch_voc_final(src, x_f16 ? 1 : 0, B, T, C, sc.blob.upload(wt), bias, slope, wav, nullptr, s, upload_lens(sc.blob, lens, B), 1);
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, int precision, int tuning) {
+  try {
+    VFX_CHECK(Cin > 0 && Cin % 64 == 0 && Cout == Cin / 2 && s >= 1 && T > 0 && precision >= 0 && precision <= 2, "bad argument");
+    vfx_config cfg{};
+    VFX_CHECK(vfx_default_config(&cfg) == 0, "no default config");
+    cfg.precision = precision;
+    cfg.tuning = tuning;
+    return voc_plan_upsampler_kernel(cfg, Cin, s, T);
+  } catch (const vfx::Error&) {
+    return -1;
+  }
 }

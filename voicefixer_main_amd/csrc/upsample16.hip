@@ -4,7 +4,7 @@
 //     out[b, s q + r, :] = act( sum_t  W_r,t  x[b, q + dw(r, t), :]  + bias )        r < s output phases, two taps each
 //
 // (oracle/vocoder.py: F.conv_transpose1d(k = 2 s, stride s, padding s / 2 + s % 2, output_padding s % 2); the phases and their taps:
-// vocoder.cpp, phase_taps).  k_conv runs this as a phased launch: one block per (spatial tile, phase, 128-cout range), each of
+// vocoder.cpp, voc_phase_taps).  k_conv runs this as a phased launch: one block per (spatial tile, phase, 128-cout range), each of
 // which fetches the patch, walks Cin / 64 stages with a barrier each and stages its tile through LDS for the stores.  With K = 2 Cin
 // that is a launch of prologues and epilogues: the 128 -> 64 upsampler (x3) ran at 0.16 of the MFMA peak and 1.9 TB/s, the 256 -> 128
 // one at 0.30 and 1.9 TB/s (round 5, profiles/r05_pmc.txt) -- under both roofs.  Here
@@ -196,6 +196,15 @@ bool upsample16_ok(const TapConvParams& hp) {
   if (hp.lens && hp.lens_mul_in != hp.lens_mul_out) return false;
   // 32-bit byte offsets inside one clip
   return (int64_t)hp.Wi * hp.nphase * hp.cout_phase * 2 < ((int64_t)1 << 30) && (int64_t)hp.Wi * Cin * 2 < ((int64_t)1 << 30);
+}
+
+bool upsample16_selected(const TapConvParams& hp, const std::vector<TapSeg>& phases) {
+  if ((hp.tuning & VFX_TUNE_NO_FUSED_UPSAMPLERS) || !upsample16_ok(hp) || (int)phases.size() != hp.nphase) return false;
+  // k_up16 multiplies every phase by exactly two taps (its stage's poff[0] and poff[1], whatever the stage's ntaps says): a phase with
+  // another tap count runs on k_conv
+  for (const TapSeg& S : phases)
+    if (S.ntaps != 2) return false;
+  return true;
 }
 
 template <int NCH, int TM>

@@ -594,6 +594,31 @@ struct VocoderWeights {
   bool needs_strict = false;    // 16-bit mode: a weight tensor does not fit fp16 operands (f16_weight_issue)
 };
 
+// The vocoder's launches (vocoder.cpp), built by the plan (build_vocoder) and by the parity entry points of libvfx_test.so from the
+// same functions: buffer pointers are the caller's (arena-relative rel_ptr() offsets in a plan, device pointers in a test).
+// Taps (e, k) of output phase r of ConvTranspose1d(k = 2s, stride s, padding pad): out[s q + r] += x[q - e] W[:, :, k]
+std::vector<std::pair<int, int>> voc_phase_taps(int s, int pad, int r);
+// PyTorch-layout weights (Conv1d (cout, cin, K); ConvTranspose1d (cin, cin / 2, 2 s)) and biases on the host -> packed for a source
+// in activated form (src_act) or raw
+VocConvW pack_voc_conv1d(const vfx_config& cfg, DeviceBlob& blob, const float* w, const float* bias, int cin, int cout, int K, bool src_act);
+VocConvW pack_voc_upsampler(const vfx_config& cfg, DeviceBlob& blob, const float* w, const float* bias, int cin, int s, bool src_act);
+// Conv1d (K, dilation dil, 'same' zero padding or reflect) on (B, T, cin): src activated (no prologue) or raw with prologue `act`
+// (slope); residual raw, or -- residual_act -- the activated fp16 form LeakyReLU(res_slope) of the residual, inverted in the epilogue;
+// raw output `out` and / or activated output `out_act` (next_act, next_slope); lens: per-clip lengths in units of `rate` positions.
+TapConvParams voc_conv1d_params(const vfx_config& cfg, const VocConvW& cw, int B, int T, int K, int dil, bool reflect, const float* src,
+                                bool src_act, int act, float slope, const float* residual, bool residual_act, float* out, float* out_act,
+                                int next_act, float next_slope, const int* lens, int rate);
+// ConvTranspose1d(k = 2s, stride s) on (B, T, cin) as ONE phased launch (PlanBuilder::add_conv_phased): returns p with seg[0] = the
+// union window of the phases' taps, phases[r] = phase r.  Output (B, T, s * cout): raw `out` and / or activated `out_act` (act_slope;
+// 1 = the fp16 trunk of the 16-bit mode); lens in INPUT positions per unit of `rate`.
+TapConvParams voc_upsample_params(const vfx_config& cfg, const VocConvW& up, int s, int B, int T, const float* src, bool src_act,
+                                  float* out, float* out_act, float act_slope, const int* lens, int rate, std::vector<TapSeg>& phases);
+// 1 when the plan runs the upsampler of a cin-channel stage (behind the first, not the last) on k_up16, 0 on the phased k_conv
+int voc_plan_upsampler_kernel(const vfx_config& cfg, int cin, int s, int T);
+// The phased launch hp (after finish_params, with tuning set) with the phase segments `phases` runs on k_up16: upsample16_ok, two
+// taps per phase and not VFX_TUNE_NO_FUSED_UPSAMPLERS (upsample16.hip)
+bool upsample16_selected(const TapConvParams& hp, const std::vector<TapSeg>& phases);
+
 // Conv weights -> MFMA fragment order [C/chunk][ntaps][Cout/32][1024 floats] (conv.hip); mode: 0 fp32, 1 split-bf16
 // (hi | lo), 2 fp16 in the hi fragments (32-channel chunks, raw sources of the 16-bit mode), 3 fp16 with 64-channel
 // chunks (activated fp16 sources of the 16-bit mode); conv_chunk(mode) = input channels per chunk.

@@ -73,22 +73,39 @@ bool stack_trunk_f16(const vfx_config& cfg, int channels, bool last_stage) {
 VocConvW load_conv1d(vfx_handle* h, const std::string& p, int cin, int cout, int K, bool src_act) {
   const HostTensor& w = staged(h, p + ".weight");
   VFX_CHECK(w.shape == std::vector<int64_t>({cout, cin, K}), "vocoder tensor '%s.weight' has an unexpected shape", p.c_str());
-  std::vector<std::pair<int, int>> taps;
-  for (int k = 0; k < K; ++k) taps.push_back({0, k});
-  VocConvW c;
-  c.cin = cin;
-  c.cout = cout;
-  c.mode = pack_mode(h->cfg, src_act);
-  c.w = h->blob.upload(pack_conv(w.data.data(), cout, cin, 1, K, 0, cin, taps, c.mode));
   const HostTensor& b = staged(h, p + ".bias");
   VFX_CHECK((int)b.data.size() == cout, "vocoder tensor '%s.bias' has an unexpected shape", p.c_str());
-  c.bias = h->blob.upload(b.data);
-  return c;
+  return pack_voc_conv1d(h->cfg, h->blob, w.data.data(), b.data.data(), cin, cout, K, src_act);
 }
+
+// The tensors an upsampler writes (build_vocoder): the fp16 trunk alone in front of a stack fused on it; otherwise the raw fp32
+// tensor unless the trunk is fp16, and the activated form (LeakyReLU(res_slope)) for an unfused stack that has one.
+struct UpOutputs {
+  bool f16_trunk = false, raw = false, act = false;
+};
+UpOutputs up_outputs(const vfx_config& cfg, int cout, bool last_stage) {
+  UpOutputs o;
+  const bool fuse = stack_fused(cfg, cout), t16 = stack_trunk_f16(cfg, cout, last_stage);
+  if (t16 && fuse) {
+    o.f16_trunk = true;
+  } else {
+    o.raw = !t16;
+    o.act = !fuse && act_form_ok(cfg, cout);
+  }
+  return o;
+}
+
+// The upsampler of stage `st` (c input channels) reads the activated trunk, unless the stack in front of it is fused on the raw trunk
+// only (in the 16-bit mode the last fused layer also writes the activated fp16 form)
+bool up_src_act(const vfx_config& cfg, int c, int st) {
+  return (st == 0 || !stack_fused(cfg, c) || cfg.precision == 2) && act_form_ok(cfg, c);
+}
+
+}  // namespace
 
 // Taps of output phase r of ConvTranspose1d(k = 2s, stride s, padding p): out[s*q + r] +=
 // x[q - e] * W[:, :, s*e + r + p] for every e with 0 <= s*e + r + p < 2s.
-std::vector<std::pair<int, int>> phase_taps(int s, int pad, int r) {
+std::vector<std::pair<int, int>> voc_phase_taps(int s, int pad, int r) {
   std::vector<std::pair<int, int>> t;  // (e, k)
   for (int e = -2; e <= 2; ++e) {
     const int k = s * e + r + pad;
@@ -97,7 +114,144 @@ std::vector<std::pair<int, int>> phase_taps(int s, int pad, int r) {
   return t;
 }
 
-}  // namespace
+VocConvW pack_voc_conv1d(const vfx_config& cfg, DeviceBlob& blob, const float* w, const float* bias, int cin, int cout, int K,
+                         bool src_act) {
+  std::vector<std::pair<int, int>> taps;
+  for (int k = 0; k < K; ++k) taps.push_back({0, k});
+  VocConvW c;
+  c.cin = cin;
+  c.cout = cout;
+  c.mode = pack_mode(cfg, src_act);
+  c.w = blob.upload(pack_conv(w, cout, cin, 1, K, 0, cin, taps, c.mode));
+  c.bias = blob.upload(bias, cout);
+  return c;
+}
+
+VocConvW pack_voc_upsampler(const vfx_config& cfg, DeviceBlob& blob, const float* w, const float* bias, int cin, int s, bool src_act) {
+  const int pad = s / 2 + s % 2;
+  VocConvW up;
+  up.cin = cin;
+  up.cout = cin / 2;
+  up.mode = pack_mode(cfg, src_act);
+  for (int r = 0; r < s; ++r) {
+    std::vector<std::pair<int, int>> taps;
+    for (auto& ek : voc_phase_taps(s, pad, r)) taps.push_back({0, ek.second});
+    up.w_phase.push_back(blob.upload(pack_conv_transposed(w, cin, cin / 2, 1, 2 * s, taps, up.mode)));
+  }
+  // the phased launch sees the output as (B, T, stride * cout): one bias copy per phase
+  std::vector<float> rep;
+  for (int r = 0; r < s; ++r) rep.insert(rep.end(), bias, bias + cin / 2);
+  up.bias = blob.upload(rep);
+  return up;
+}
+
+TapConvParams voc_conv1d_params(const vfx_config& cfg, const VocConvW& cw, int B, int T, int K, int dil, bool reflect, const float* src,
+                                bool src_act, int act, float slope, const float* residual, bool residual_act, float* out, float* out_act,
+                                int next_act, float next_slope, const int* lens, int rate) {
+  VFX_CHECK(cw.mode == pack_mode(cfg, src_act), "vocoder plan: weights of a %d -> %d convolution are packed for another source form", cw.cin, cw.cout);
+  TapConvParams p{};
+  set_conv1d_geometry(p, B, T, K, dil, reflect);
+  p.hionly = cfg.precision == 2;
+  p.Cout = cw.cout;
+  p.bias = cw.bias;
+  if (residual && residual_act) {
+    p.residual_act = residual;
+    p.residual_inv_slope = 1.f / cfg.voc_res_slope;
+  } else {
+    p.residual = residual;
+  }
+  p.act_slope = 1.f;
+  p.out = out;
+  if (next_act != ACT_NONE) {
+    p.out_act = out_act;
+    p.act_slope = next_slope;
+    p.act_elu = next_act == ACT_ELU;
+  }
+  p.lens = lens;
+  p.lens_mul_in = p.lens_mul_out = rate;
+  p.nseg = 1;
+  TapSeg& S = p.seg[0];
+  S.src = src;
+  S.C = cw.cin;
+  S.act = src_act ? ACT_NONE : act;
+  S.slope = src_act ? 1.f : slope;
+  S.src_act = src_act ? 1 : 0;
+  S.wt = cw.w;
+  return p;
+}
+
+TapConvParams voc_upsample_params(const vfx_config& cfg, const VocConvW& up, int s, int B, int T, const float* src, bool src_act,
+                                  float* out, float* out_act, float act_slope, const int* lens, int rate, std::vector<TapSeg>& phases) {
+  VFX_CHECK(up.mode == pack_mode(cfg, src_act) && (int)up.w_phase.size() == s, "vocoder plan: a %d -> %d upsampler is packed for another source form",
+            up.cin, up.cout);
+  const int pad = s / 2 + s % 2;
+  // ConvTranspose1d(k = 2s, stride s) as ONE phased launch: output phase r (samples s*q + r) is a 2-tap
+  // convolution of the input, and (B, T * s, cout) viewed as (B, T, s * cout) makes the phases plain cout
+  // ranges -- the input patch is read from HBM once for all of them (it was read s times as s launches).
+  TapConvParams p{};
+  p.hionly = cfg.precision == 2;
+  p.B = B;
+  p.Hi = p.Hg = p.Ho = 1;
+  p.Wi = p.Wg = p.Wo = T;
+  p.Cout = s * up.cout;
+  p.sh = p.sw = 1;
+  p.bias = up.bias;
+  p.act_slope = out_act ? act_slope : 1.f;
+  p.lens = lens;  // (the phased launch addresses its output in INPUT positions: (B, T, s * cout))
+  p.lens_mul_in = p.lens_mul_out = rate;
+  p.out = out;
+  p.out_act = out_act;
+  p.nseg = 1;
+  phases.assign(s, TapSeg{});
+  int e_lo = 1 << 30, e_hi = -(1 << 30);
+  for (int r = 0; r < s; ++r) {
+    TapSeg& S = phases[r];
+    S.src = src;
+    S.C = up.cin;
+    S.act = src_act ? ACT_NONE : ACT_LEAKY;
+    S.slope = src_act ? 1.f : cfg.voc_up_slope;
+    S.src_act = src_act ? 1 : 0;
+    S.wt = up.w_phase[r];
+    for (auto& ek : voc_phase_taps(s, pad, r)) {
+      S.dh[S.ntaps] = 0;
+      S.dw[S.ntaps] = -ek.first;
+      ++S.ntaps;
+      e_lo = std::min(e_lo, -ek.first);
+      e_hi = std::max(e_hi, -ek.first);
+    }
+  }
+  TapSeg& U = p.seg[0];  // union of the phases' taps: fixes the patch window
+  U = phases[0];
+  U.ntaps = 0;
+  for (int dw = e_lo; dw <= e_hi; ++dw) {
+    U.dh[U.ntaps] = 0;
+    U.dw[U.ntaps] = dw;
+    ++U.ntaps;
+  }
+  return p;
+}
+
+int voc_plan_upsampler_kernel(const vfx_config& cfg, int cin, int s, int T) {
+  // a stage behind the first, not the last one: the forms build_vocoder gives such an upsampler
+  const bool src_act = up_src_act(cfg, cin, 1);
+  const UpOutputs o = up_outputs(cfg, cin / 2, false);
+  static float dummy;  // never dereferenced: host-side planning only
+  VocConvW up;
+  up.cin = cin;
+  up.cout = cin / 2;
+  up.mode = pack_mode(cfg, src_act);
+  up.w_phase.assign(s, &dummy);
+  std::vector<TapSeg> phases;
+  TapConvParams p = voc_upsample_params(cfg, up, s, 1, T, &dummy, src_act, o.raw ? &dummy : nullptr,
+                                        (o.f16_trunk || o.act) ? &dummy : nullptr, o.f16_trunk ? 1.f : cfg.voc_res_slope, nullptr, 1, phases);
+  p.split = cfg.precision != 0;
+  p.tuning = cfg.tuning;
+  p.nphase = s;
+  p.cout_phase = up.cout;
+  finish_params(p);
+  p.ksplit = 0;  // (build_vocoder: PlanBuilder::no_splitk)
+  return upsample16_selected(p, phases) ? 1 : 0;
+}
 
 std::shared_ptr<VocoderWeights> build_vocoder_weights(vfx_handle* h) {
   const vfx_config& cfg = h->cfg;
@@ -113,28 +267,13 @@ std::shared_ptr<VocoderWeights> build_vocoder_weights(vfx_handle* h) {
   W->pre = load_conv1d(h, "generator.1", cin, cfg.voc_channels, 7, /*src_act=*/true);
   int c = cfg.voc_channels, idx = 3;
   for (int st = 0; st < cfg.voc_n_stages; ++st) {
-    const int s = cfg.voc_scales[st], pad = s / 2 + s % 2;
+    const int s = cfg.voc_scales[st];
     snprintf(name, sizeof(name), "generator.%d.layer", idx);
     const HostTensor& w = staged(h, std::string(name) + ".weight");
     VFX_CHECK(w.shape == std::vector<int64_t>({c, c / 2, 2 * s}), "vocoder tensor '%s.weight' has an unexpected shape", name);
-    VocConvW up;
-    up.cin = c;
-    up.cout = c / 2;
-    // the upsampler reads the activated trunk, unless the stack in front of it is fused on the raw trunk only (in the
-    // 16-bit mode the last fused layer also writes the activated fp16 form)
-    up.mode = pack_mode(cfg, (st == 0 || !stack_fused(cfg, c) || cfg.precision == 2) && act_form_ok(cfg, c));
-    for (int r = 0; r < s; ++r) {
-      std::vector<std::pair<int, int>> taps;
-      for (auto& ek : phase_taps(s, pad, r)) taps.push_back({0, ek.second});
-      up.w_phase.push_back(h->blob.upload(pack_conv_transposed(w.data.data(), c, c / 2, 1, 2 * s, taps, up.mode)));
-    }
-    {  // the phased launch sees the output as (B, T, stride * cout): one bias copy per phase
-      const std::vector<float>& b = staged(h, std::string(name) + ".bias").data;
-      VFX_CHECK((int)b.size() == c / 2, "vocoder tensor '%s.bias' has an unexpected shape", name);
-      std::vector<float> rep;
-      for (int r = 0; r < s; ++r) rep.insert(rep.end(), b.begin(), b.end());
-      up.bias = h->blob.upload(rep);
-    }
+    const std::vector<float>& b = staged(h, std::string(name) + ".bias").data;
+    VFX_CHECK((int)b.size() == c / 2, "vocoder tensor '%s.bias' has an unexpected shape", name);
+    const VocConvW up = pack_voc_upsampler(cfg, h->blob, w.data.data(), b.data(), c, s, up_src_act(cfg, c, st));
     W->up.push_back(up);
     c /= 2;
     std::vector<std::pair<VocConvW, VocConvW>> stack;
@@ -217,40 +356,11 @@ void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_
                     const size_t* residual, bool src_act, bool want_raw, int next_act, float next_slope,
                     bool residual_act = false) -> Forms {
     Forms out;
-    TapConvParams p{};
-    set_conv1d_geometry(p, B, Tlen, K, dil, reflect);
-    p.hionly = cfg.precision == 2;
-    p.Cout = cw.cout;
-    p.bias = cw.bias;
-    if (residual && residual_act) {
-      p.residual_act = rel_ptr(*residual);
-      p.residual_inv_slope = 1.f / cfg.voc_res_slope;
-    } else {
-      p.residual = residual ? rel_ptr(*residual) : nullptr;
-    }
-    p.act_slope = 1.f;
-    VFX_CHECK(cw.mode == pack_mode(cfg, src_act), "vocoder plan: weights of a %d -> %d convolution are packed for another source form", cw.cin, cw.cout);
-    if (want_raw) {
-      out.raw = pb.alloc_f((int64_t)B * Tlen * cw.cout);
-      p.out = const_cast<float*>(rel_ptr(out.raw));
-    }
-    if (next_act != ACT_NONE) {
-      out.act = pb.alloc_f(act_floats((int64_t)B * Tlen * cw.cout));
-      p.out_act = const_cast<float*>(rel_ptr(out.act));
-      p.act_slope = next_slope;
-      p.act_elu = next_act == ACT_ELU;
-    }
-    p.lens = lens_tp;
-    p.lens_mul_in = p.lens_mul_out = rate;
-    p.nseg = 1;
-    TapSeg& S = p.seg[0];
-    S.src = rel_ptr(src);
-    S.C = cw.cin;
-    S.act = src_act ? ACT_NONE : act;
-    S.slope = src_act ? 1.f : slope;
-    S.src_act = src_act ? 1 : 0;
-    S.wt = cw.w;
-    pb.add_conv(p);
+    if (want_raw) out.raw = pb.alloc_f((int64_t)B * Tlen * cw.cout);
+    if (next_act != ACT_NONE) out.act = pb.alloc_f(act_floats((int64_t)B * Tlen * cw.cout));
+    pb.add_conv(voc_conv1d_params(cfg, cw, B, Tlen, K, dil, reflect, rel_ptr(src), src_act, act, slope, residual ? rel_ptr(*residual) : nullptr,
+                                  residual_act, want_raw ? const_cast<float*>(rel_ptr(out.raw)) : nullptr,
+                                  out.act != kNone ? const_cast<float*>(rel_ptr(out.act)) : nullptr, next_act, next_slope, lens_tp, rate));
     return out;
   };
 
@@ -273,7 +383,7 @@ void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_
   int Tlen = Tp;
   bool trunk_is_f16 = false;  // form of the current stack's raw trunk
   for (int st = 0; st < cfg.voc_n_stages; ++st) {
-    const int s = cfg.voc_scales[st], pad = s / 2 + s % 2;
+    const int s = cfg.voc_scales[st];
     const VocConvW& up = W->up[st];
     const int Tout = Tlen * s;
     const bool fuse = stack_fused(cfg, up.cout);
@@ -285,65 +395,19 @@ void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_
     const bool t16 = stack_trunk_f16(cfg, up.cout, last_stage);
     trunk_is_f16 = t16 && fuse;
     const int64_t nel = (int64_t)B * Tout * up.cout;
+    const UpOutputs uo = up_outputs(cfg, up.cout, last_stage);
     Forms y;
-    if (t16 && fuse) y.raw = pb.alloc_f(act_floats(nel));
-    else if (!t16) y.raw = pb.alloc_f(nel);
+    if (uo.f16_trunk) y.raw = pb.alloc_f(act_floats(nel));
+    else if (uo.raw) y.raw = pb.alloc_f(nel);
     const bool act_ok = act_form_ok(cfg, up.cout);  // (false: a 32-channel stack of the 16-bit mode -- raw fp32 tensors throughout)
-    if (!fuse && act_ok) y.act = pb.alloc_f(act_floats(nel));
-    const bool up_src_act = cur.act != kNone;  // the producer already applied LeakyReLU(up_slope)
-    VFX_CHECK(up.mode == pack_mode(cfg, up_src_act), "vocoder plan: upsampler %d is packed for another source form", st);
+    if (uo.act) y.act = pb.alloc_f(act_floats(nel));
+    const bool src_act = cur.act != kNone;  // the producer already applied LeakyReLU(up_slope)
     {
-      // ConvTranspose1d(k = 2s, stride s) as ONE phased launch: output phase r (samples s*q + r) is a 2-tap
-      // convolution of the input, and (B, Tlen * s, cout) viewed as (B, Tlen, s * cout) makes the phases plain cout
-      // ranges -- the input patch is read from HBM once for all of them (it was read s times as s launches).
-      TapConvParams p{};
-      p.hionly = cfg.precision == 2;
-      p.B = B;
-      p.Hi = p.Hg = p.Ho = 1;
-      p.Wi = p.Wg = p.Wo = Tlen;
-      p.Cout = s * up.cout;
-      p.sh = p.sw = 1;
-      p.bias = up.bias;
-      p.act_slope = 1.f;
-      p.lens = lens_tp;  // (the phased launch addresses its output in INPUT positions: (B, Tlen, s * cout))
-      p.lens_mul_in = p.lens_mul_out = rate;
-      if (t16 && fuse) {
-        p.out_act = const_cast<float*>(rel_ptr(y.raw));  // fp16(y): LeakyReLU with slope 1
-      } else {
-        if (!t16) p.out = const_cast<float*>(rel_ptr(y.raw));
-        if (!fuse && act_ok) {
-          p.out_act = const_cast<float*>(rel_ptr(y.act));
-          p.act_slope = cfg.voc_res_slope;
-        }
-      }
-      p.nseg = 1;
-      std::vector<TapSeg> phases(s);
-      int e_lo = 1 << 30, e_hi = -(1 << 30);
-      for (int r = 0; r < s; ++r) {
-        TapSeg& S = phases[r];
-        S = TapSeg{};
-        S.src = rel_ptr(up_src_act ? cur.act : cur.raw);
-        S.C = up.cin;
-        S.act = up_src_act ? ACT_NONE : ACT_LEAKY;
-        S.slope = up_src_act ? 1.f : cfg.voc_up_slope;
-        S.src_act = up_src_act ? 1 : 0;
-        S.wt = up.w_phase[r];
-        for (auto& ek : phase_taps(s, pad, r)) {
-          S.dh[S.ntaps] = 0;
-          S.dw[S.ntaps] = -ek.first;
-          ++S.ntaps;
-          e_lo = std::min(e_lo, -ek.first);
-          e_hi = std::max(e_hi, -ek.first);
-        }
-      }
-      TapSeg& U = p.seg[0];  // union of the phases' taps: fixes the patch window
-      U = phases[0];
-      U.ntaps = 0;
-      for (int dw = e_lo; dw <= e_hi; ++dw) {
-        U.dh[U.ntaps] = 0;
-        U.dw[U.ntaps] = dw;
-        ++U.ntaps;
-      }
+      std::vector<TapSeg> phases;
+      const TapConvParams p = voc_upsample_params(
+          cfg, up, s, B, Tlen, rel_ptr(src_act ? cur.act : cur.raw), src_act, uo.raw ? const_cast<float*>(rel_ptr(y.raw)) : nullptr,
+          uo.f16_trunk ? const_cast<float*>(rel_ptr(y.raw)) : uo.act ? const_cast<float*>(rel_ptr(y.act)) : nullptr,  // f16 trunk: fp16(y), slope 1
+          uo.f16_trunk ? 1.f : cfg.voc_res_slope, lens_tp, rate, phases);
       pb.add_conv_phased(p, phases);
     }
     free_forms(cur);

@@ -475,3 +475,55 @@ class Engine:
                                                   cp(scale), cp(shift), act, float(slope), cp(bias), _ptr(y), self._stream()),
                    "vfx_op_conv_transpose")
         return y
+
+    # the vocoder's launches as its plan builds them (include/vfx_test.h: vfx_op_voc_*)
+    def op_voc_upsample(self, x, weight, bias, stride, up_slope=0.2, src_act=True, want_raw=False, act_slope=None, lens=None):
+        """One upsampler on x (B, T, Cin): -> (y raw or None, ya activated or None, ran_on_k_up16).  act_slope None: no activated
+        output; 1.0: the fp16 trunk of the 16-bit mode.  y starts as NaN, so do unwritten elements of ya."""
+        x = _dev_f32(x, self.device)
+        B, T, Cin = x.shape
+        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+        w, b = hp(weight), hp(bias)
+        Cout = w.shape[1]
+        shape = (B, T * stride, Cout)
+        y = torch.full(shape, float("nan"), device=self.device) if want_raw else None
+        ya = torch.empty(shape, device=self.device) if act_slope is not None else None
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        up16 = ctypes.c_int(-1)
+        _lib.check(_lib.load_test().vfx_op_voc_upsample(
+            self.h, _ptr(x), B, T, Cin, w.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), int(stride), float(up_slope),
+            int(bool(src_act)), int(bool(want_raw)), int(act_slope is not None), float(act_slope if act_slope is not None else 1.0),
+            None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(y), _ptr(ya), ctypes.byref(up16), self._stream()),
+            "vfx_op_voc_upsample")
+        return y, ya, bool(up16.value)
+
+    def op_voc_conv1d(self, x, weight, bias, dil=1, reflect=False, src_act=False, act=0, slope=1.0, residual=None, residual_act=False,
+                      want_raw=True, next_act=0, next_slope=1.0, lens=None):
+        """Conv1d of the vocoder plan on x (B, T, Cin): -> (y raw or None, ya activated or None); both start as NaN."""
+        x = _dev_f32(x, self.device)
+        B, T, Cin = x.shape
+        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+        w, b = hp(weight), hp(bias)
+        Cout, _, K = w.shape
+        y = torch.full((B, T, Cout), float("nan"), device=self.device) if want_raw else None
+        ya = torch.empty((B, T, Cout), device=self.device) if next_act else None
+        res = None if residual is None else _dev_f32(residual, self.device)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        _lib.check(_lib.load_test().vfx_op_voc_conv1d(
+            self.h, _ptr(x), B, T, Cin, w.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), Cout, K, int(dil),
+            int(bool(reflect)), int(bool(src_act)), int(act), float(slope), _ptr(res), int(bool(residual_act)), int(bool(want_raw)),
+            int(next_act), float(next_slope), None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(y), _ptr(ya),
+            self._stream()), "vfx_op_voc_conv1d")
+        return y, ya
+
+    def op_voc_final(self, x, weight, bias, slope=0.2, x_f16=False, lens=None):
+        """The vocoder tail on x (B, T, C): -> wav (B, T), NaN where nothing was written."""
+        x = _dev_f32(x, self.device)
+        B, T, C = x.shape
+        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32))
+        wav = torch.full((B, T), float("nan"), device=self.device)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        _lib.check(_lib.load_test().vfx_op_voc_final(
+            self.h, _ptr(x), B, T, C, w.ctypes.data_as(ctypes.c_void_p), float(bias), float(slope), int(bool(x_f16)),
+            None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(wav), self._stream()), "vfx_op_voc_final")
+        return wav
