@@ -26,13 +26,19 @@ ResUNet on split-bf16 operands (it carries the log-mel L1 <= 1e-3 bar), the voco
 product; 1 = split-bf16 everywhere (3 MFMAs per product), timed as well at N = 1 and reported beside `value` as
 `split_bf16_mode`; 0 = exact fp32 MFMA.
 
-Rank 0 prints ONE JSON line.  At N = 1 the default run also times configs[2] and configs[4] for a few steps in the same
-process and nests their value / ms_per_step / parity (vs the float64 oracle) / roofline under `aux_workloads`, together
-with `varlen_vctk`: 128 clips of 2 .. 8 s, no two of one length, through the padded-batch entry point (--no-aux skips them).  Measured in the same run: `parity` (HIP outputs of the benched batch vs the CPU oracle on
-the clips the oracle was run on; the run FAILS when the log-mel L1 exceeds the 1e-3 bar), `roofline` (HIP events around
-every convolution launch on its own stream over K more steps; `traffic` from two rocprofv3 PMC passes of a child run of
-the same workload), `roofline_hbm` (the HBM-bound front-end / back-end kernels), `cpu_baseline` (the CPU oracle, a port
-of the reference algorithm, on a bounded sample of the same clips on this box's host cores).
+Rank 0 prints ONE JSON line.  A plain run does what that line's headline needs and nothing more: it sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line (value, ms_per_step, per-step statistics, power and clock over
+the timed region, the device flags of the timed steps -- a saturated fp16 range or a negative mel fails the run).
+
+--full adds everything that takes work of its own after the timed region.  At N = 1: `parity` (HIP outputs of the benched
+batch vs the CPU oracle on the clips the oracle was run on; the run FAILS when the log-mel L1 exceeds the 1e-3 bar),
+`roofline` (HIP events around every convolution launch on its own stream over K more steps; `traffic` from two rocprofv3
+PMC passes of a child run of the same workload), `roofline_hbm` (the HBM-bound front-end / back-end kernels),
+`cpu_baseline` (the CPU oracle, a port of the reference algorithm, on a bounded sample of the same clips on this box's host
+cores), `split_bf16_mode` / `f32_trunk_mode` (the default workload in two other arithmetic modes), and `aux_workloads`:
+configs[2] and configs[4] timed for a few steps in the same process with their value / ms_per_step / parity (vs the
+float64 oracle) / roofline, together with `varlen_vctk`: 128 clips of 2 .. 8 s, no two of one length, through the
+padded-batch entry point (--no-aux skips them).  At any N, sharded1024 checks two gathered clips against a direct restore.
 """
 import argparse
 import json
@@ -68,17 +74,21 @@ def parse():
     ap.add_argument("--workload", choices=WORKLOADS, default="gsr16x10")
     ap.add_argument("--clips", type=int, default=0, help="clips per GPU per step (default: the workload's)")
     ap.add_argument("--seconds", type=float, default=0.0, help="clip length (default: the workload's)")
-    ap.add_argument("--cpu-baseline-clips", type=int, default=-1, help="clips in the CPU-oracle sample (0 = skip; default per workload)")
-    ap.add_argument("--cpu-threads", type=int, default=32)
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison (needs the cpu baseline sample)")
-    ap.add_argument("--traffic", choices=("live", "off"), default="live",
-                    help="live: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of a child run of the same workload")
     ap.add_argument("--dist-selfcheck", action="store_true", help="N > 1: round-trip a tensor through dist.scatter_clips / gather_clips first")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra all-split-bf16 (precision 1) timing at N = 1")
-    ap.add_argument("--no-aux", action="store_true", help="skip the nested ssr_sr64 / stream1s measurements of the default run")
-    ap.add_argument("--aux-steps", type=int, default=3)
-    ap.add_argument("--cpu-repeats", type=int, default=3, help="timed calls of the CPU oracle (the median is reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check what the headline does not need: parity vs the CPU "
+                         "oracle, roofline, PMC traffic, CPU baseline, the other arithmetic modes, the aux workloads")
+    full = ap.add_argument_group("what --full measures (ignored without it)")
+    full.add_argument("--cpu-baseline-clips", type=int, default=-1, help="clips in the CPU-oracle sample (0 = skip; default per workload)")
+    full.add_argument("--cpu-threads", type=int, default=32)
+    full.add_argument("--no-roofline", action="store_true")
+    full.add_argument("--no-parity", action="store_true", help="skip the oracle comparison (needs the cpu baseline sample)")
+    full.add_argument("--traffic", choices=("live", "off"), default="live",
+                      help="live: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of a child run of the same workload")
+    full.add_argument("--no-alt", action="store_true", help="skip the extra all-split-bf16 (precision 1) timing at N = 1")
+    full.add_argument("--no-aux", action="store_true", help="skip the nested ssr_sr64 / stream1s measurements of the default run")
+    full.add_argument("--aux-steps", type=int, default=3)
+    full.add_argument("--cpu-repeats", type=int, default=3, help="timed calls of the CPU oracle (the median is reported)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="TEST ONLY (tests/test_host.py): run this script's own rank plumbing -- process group, weight broadcast, "
                          "sharding, barrier + max-over-ranks clock, the JSON line -- on CPU over gloo with the engine replaced by "
@@ -379,8 +389,8 @@ def live_traffic(args):
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "VFX_PROFILE_DUMP"):
         env.pop(k, None)
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-roofline", "--no-alt",
-             "--cpu-baseline-clips", "0", "--traffic", "off", "--no-parity", "--no-aux", "--workload", args.workload,
+    # a plain run (no --full): the launches after the last k_stft_mel are those of its one timed step
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--workload", args.workload,
              "--precision", str(args.precision), "--clips", str(args.clips), "--seconds", str(args.seconds)]
     try:
         dbs = {}
@@ -904,26 +914,26 @@ def main():
         if gsr and args.precision == 2:
             res["caveat"] = ("precision 2 runs the vocoder on fp16 operands; its waveform parity is established on seeded "
                              "synthetic vocoder weights (the pretrained TFGAN checkpoint is not obtainable offline) -- "
-                             "`split_bf16_mode` is the conservative figure")
+                             "`split_bf16_mode` of a --full run is the conservative figure")
 
-    # ---- outputs of the benched batch (for parity), oracle sample --------------------------------------
-    if rank == 0 and wl == "gsr16x10":
+        # what the last timed step returned (before anything below reuses the output buffers)
+        res["outputs_finite"] = all(bool(torch.isfinite(t).all().item()) for t in w.outputs().values())
+        if wl == "sharded1024":
+            res["outputs_finite"] = res["outputs_finite"] and tuple(w.gathered[0].shape) == (w.n_total, L)
+            for k in w.phases:
+                res[k] = round(w.phases[k] / args.steps, 3)
+            res["clips_total"] = w.n_total
+            res["sub_batches_per_rank"] = -(-B // 37)        # 32-bit tensor addressing: <= 37 clips of 10 s per launch
+
+    # ---- --full: outputs of the benched batch (for parity), oracle sample, roofline, other modes, aux workloads -----------
+    if rank == 0 and args.full and wl == "gsr16x10":
         out_p, logmel_p = eng.restore_gsr(w.wav, want_logmel=True)
-        res["outputs_finite"] = bool(torch.isfinite(out_p).all().item())
-    elif rank == 0 and wl == "sharded1024":
-        gathered = w.gathered
-        res["outputs_finite"] = bool(torch.isfinite(gathered[0]).all().item()) and tuple(gathered[0].shape) == (w.n_total, L)
-        for k in w.phases:
-            res[k] = round(w.phases[k] / args.steps, 3)
-        res["clips_total"] = w.n_total
-        res["sub_batches_per_rank"] = -(-B // 37)        # 32-bit tensor addressing: <= 37 clips of 10 s per launch
+    elif rank == 0 and args.full and wl == "sharded1024":
         # the gathered result is the restore of the scattered clips: check two clips against a direct call
         chk = eng.restore_gsr(w.full[:2])
-        res["gather_matches_direct_restore"] = bool(torch.equal(chk, gathered[0][:2]))
-    elif rank == 0:
-        res["outputs_finite"] = bool(torch.isfinite(w.holder[0]).all().item())
+        res["gather_matches_direct_restore"] = bool(torch.equal(chk, w.gathered[0][:2]))
 
-    if rank == 0 and world == 1 and not args.dry_run_cpu:
+    if rank == 0 and world == 1 and args.full and not args.dry_run_cpu:
         traffic = None
         if not args.no_roofline:
             if args.traffic == "live" and gsr:

@@ -9,7 +9,7 @@
 #   smoke                      __graft_entry__.smoke()
 #   tests[:K]                  pytest tests -m gpu [-k K]               -> tests[_K].log
 #   tfile:F[:K]                pytest tests/F -m gpu -x [-k K]           -> tfile_F.log
-#   bench[:ARGS]               python bench.py --steps 20 --warmup 5 ARGS  (the judged line; no poller beside it) -> bench[_ARGS].json
+#   bench[:ARGS]               python bench.py --full --steps 20 --warmup 5 ARGS  (the full line; no poller beside it) -> bench[_ARGS].json
 #   quick[:ARGS]               bench.py without parity / roofline / aux / alt / cpu baseline (timing only)       -> quick.jsonl (appended)
 #   ab:DIR[:N]                 DIR (a built tree of another commit, e.g. _ab_r04/) and this tree alternating N times (default 2),
 #                              `quick` flags, on this one box                                                      -> same_box_ab.jsonl
@@ -43,7 +43,7 @@ run_step() {
     tfile) local f=${rest%%:*} k=""; [ "$f" != "$rest" ] && k=$(args "${rest#*:}")
            timeout 900 python -m pytest tests/$f -m gpu -x -q ${k:+-k "$k"} > $O/tfile_$(slug "$f").log 2>&1; tail -n 6 $O/tfile_$(slug "$f").log ;;
     bench) local a=$(args "$rest"); local f=$O/bench$( [ -n "$a" ] && echo _$(slug "$a") )
-           timeout 900 python bench.py --steps 20 --warmup 5 $a > $f.json 2> $f.err; cut -c1-220 $f.json; tail -n 2 $f.err ;;
+           timeout 900 python bench.py --full --steps 20 --warmup 5 $a > $f.json 2> $f.err; cut -c1-220 $f.json; tail -n 2 $f.err ;;
     quick) timeout 300 python bench.py --steps 20 --warmup 5 $QUICK $(args "$rest") 2>/dev/null | line "${VFX_LIB_PATH:-this tree} $rest" >> $O/quick.jsonl; tail -n 1 $O/quick.jsonl | cut -c1-200 ;;
     ab) local d=${rest%%:*} n=2; [ "$d" != "$rest" ] && n=${rest#*:}
         for i in $(seq $n); do

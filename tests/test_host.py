@@ -436,12 +436,13 @@ def test_bench_rank_plumbing_dry_run_two_ranks(workload, launcher):
     """bench.py's OWN N > 1 branch has never run on hardware (no multi-GPU box in rounds 1-4): `--dry-run-cpu` runs exactly
     that code -- process group, one-flat-broadcast of the weights, per-rank clips / scatter + gather, barrier + max-over-ranks
     clock, rank 0's JSON line -- over gloo with an identity stub where the libvfx handle stands, launched the way the driver
-    launches it (`python -m torch.distributed.run ... bench.py --gpus N`) and the way `bench.py --gpus N` spawns itself."""
+    launches it (`python -m torch.distributed.run ... bench.py --gpus N`) and the way `bench.py --gpus N` spawns itself.
+    sharded1024 runs with --full, which checks the gathered clips against a direct restore."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MASTER_ADDR"] = "127.0.0.1"
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run-cpu", "--workload", workload,
-            "--clips", "3", "--seconds", "0.2"]
+            "--clips", "3", "--seconds", "0.2"] + (["--full"] if workload == "sharded1024" else [])
     port = {"gsr16x10": 29641, "sharded1024": 29643}[workload]
     cmd = [sys.executable] + ((["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                 "--master-port", str(port)]) if launcher == "torchrun" else []) + tail
@@ -482,6 +483,27 @@ def test_bench_dump_outputs_dry_run(tmp_path):
         got.append(np.load(d / "wav.npy"))
     assert got[0].dtype == np.float32 and np.array_equal(got[0], got[1])
     assert np.array_equal(got[0], synth.make_clips(3, 0.2, seed=1234)[:, 0])
+
+
+def test_bench_plain_run_leaves_the_checks_to_full(tmp_path):
+    """A plain run stops after the result line of its timed steps; the check of the gathered clips against a direct restore
+    (like parity, roofline, CPU baseline and the other modes on a GPU) runs with --full only."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = {}
+    for mode in ("plain", "full"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--dry-run-cpu", "--workload", "sharded1024", "--clips", "3", "--seconds", "0.2"]
+                             + (["--full"] if mode == "full" else []),
+                             capture_output=True, text=True, env=env, timeout=300, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+        lines[mode] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["outputs_finite"] is True
+        assert d["clips_total"] == 3 and all(d[k] >= 0 for k in ("scatter_ms", "restore_ms", "gather_ms"))
+    assert "gather_matches_direct_restore" not in plain and full["gather_matches_direct_restore"] is True
+    assert set(full) - set(plain) == {"gather_matches_direct_restore"}
 
 
 def test_bench_dump_outputs_samples_large_outputs(tmp_path):
