@@ -241,6 +241,27 @@ int vfx_chunk_ola(vfx_handle* h, const float* frames, const float* window, float
                   int n_chunks, int win, int hop, int lead, int L, float* y, void* stream);
 
 /*
+ * Polyphase resampling to the library's rate: librosa.load(path, sr=44100) (tools/utils.py:46-48), i.e.
+ * scipy.signal.resample_poly(x, up, down) on float32 input, bit for bit.  up / down are reduced by their gcd first; with
+ * M = max(up, down), hl = 10 M, the filter has ntaps = 2 hl + 1 taps, `taps` (DEVICE, fp32) = the taps resample_poly builds:
+ * float32(firwin(2 hl + 1, 1 / M, window=('kaiser', 5.0))) * float32(up).  Output n of a clip of n_in samples is
+ *   y[n] = sum over ascending k, 0 <= k < n_in, 0 <= n down + hl - k up <= 2 hl, of x[k] * taps[n down + hl - k up]
+ * with one fp32 rounding per product and per sum (no FMA), for n < vfx_resample_out_len(n_in) = ceil(n_in up / down).
+ *
+ * vfx_resample_out_len: -1 for rates <= 0 or a pair whose filter does not fit the kernel (larger than the pairs of 8 .. 96 kHz
+ *   <-> 44.1 kHz need; the caller resamples such a pair elsewhere); n_in for the same rate.
+ * vfx_resample_window: the input indices [*k0, *k1) that outputs [o0, o0 + n) of a clip of n_in samples read (k0 = k1 = 0 when
+ *   none: outputs past the clip's end are zeros); every index in it is read by one of those outputs.
+ * vfx_resample: x (B, ldx) holds global input indices [x0, x0 + Lx) of each clip; lens_in (HOST, B) = each clip's whole length
+ *   (indices outside [0, lens_in[b]) count as zero); writes global outputs [o0, o0 + n_out) of every clip to y (B, ldy), zeros at
+ *   or past a clip's own output length.  Fails when the window lacks an index vfx_resample_window asks for, or for the same rate.
+ */
+int64_t vfx_resample_out_len(int64_t n_in, int up, int down);
+int vfx_resample_window(int64_t n_in, int up, int down, int64_t o0, int64_t n, int64_t* k0, int64_t* k1);
+int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx, const int64_t* lens_in, int up, int down,
+                 const float* taps, int ntaps, float* y, int64_t ldy, int64_t o0, int64_t n_out, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

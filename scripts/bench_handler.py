@@ -3,7 +3,10 @@
 segments, the per-stage calls of the reference surface with their host syncs: to_log's assert, the peak compare,
 wav file I/O) timed on a 150-s file, next to the fused `VoiceFixer.restore` on the same segments.
 
-    python scripts/bench_handler.py [--precision 1|2] > gpurun_out/handler.json
+    python scripts/bench_handler.py [--precision 1|2] [--rates=48000,16000] > handler.json
+
+--rates: also time handler() (no target) on the same 150-s signal stored at each of these rates, with the device resampler
+(handlers.DEVICE_RESAMPLE = True) and with the host path (False), median of five calls each: handler_sr<rate>_<device|host>_s.
 """
 import json
 import os
@@ -59,6 +62,26 @@ def main():
         buf = io.StringIO()
         pstats.Stats(pr, stream=buf).sort_stats("tottime").print_stats(18)
         sys.stderr.write(buf.getvalue())
+    rates = [int(r) for a in sys.argv[1:] if a.startswith("--rates=") for r in a.split("=")[1].split(",") if r]
+    for rate in rates:
+        from math import gcd
+        from scipy.signal import resample_poly
+        g = gcd(rate, 44100)
+        src_r = os.path.join(tmp, "in_%d.wav" % rate)
+        handlers.save_wave(resample_poly(wav, rate // g, 44100 // g).astype(np.float32) if rate != 44100 else wav, src_r, sample_rate=rate)
+        for mode, on in (("device", True), ("host", False)):
+            handlers.DEVICE_RESAMPLE = on
+            handlers.handler(src_r, dst, None, ckpt=None, device=dev, needrefresh=False, meta={"unify_energy": False})   # warm-up
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                handlers.handler(src_r, dst, None, ckpt=None, device=dev, needrefresh=False, meta={"unify_energy": False})
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            res["handler_sr%d_%s_s" % (rate, mode)] = round(float(np.median(ts)), 4)
+            res["handler_sr%d_%s_calls_s" % (rate, mode)] = [round(t, 4) for t in ts]
+        handlers.DEVICE_RESAMPLE = True
     # the same three segments through the fused entry point, resident in HBM (no file I/O)
     x = torch.from_numpy(wav).to(dev)
     segs = [x[i * 2646000:(i + 1) * 2646000][None] for i in range(3)]

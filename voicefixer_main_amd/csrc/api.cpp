@@ -1073,6 +1073,47 @@ int vfx_chunk_ola(vfx_handle* h, const float* frames, const float* window, float
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// polyphase resampling (librosa.load(path, sr=44100) / scipy.signal.resample_poly on the device: resample.hip)
+// ---------------------------------------------------------------------------------------------
+int64_t vfx_resample_out_len(int64_t n_in, int up, int down) {
+  ResamplePair p;
+  if (n_in < 0 || !resample_reduce(up, down, &p) || (p.up != p.down && p.R == 0)) return -1;
+  return resample_out_len(n_in, p);
+}
+
+int vfx_resample_window(int64_t n_in, int up, int down, int64_t o0, int64_t n, int64_t* k0, int64_t* k1) {
+  VFX_API_BEGIN
+  ResamplePair p;
+  VFX_CHECK(resample_reduce(up, down, &p), "vfx_resample_window: bad rates %d/%d", up, down);
+  VFX_CHECK(n_in >= 0 && o0 >= 0 && n >= 0 && k0 && k1, "vfx_resample_window: bad argument");
+  resample_window(n_in, p, o0, n, k0, k1);
+  VFX_API_END
+}
+
+int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx, const int64_t* lens_in, int up, int down,
+                 const float* taps, int ntaps, float* y, int64_t ldy, int64_t o0, int64_t n_out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  ResamplePair p;
+  VFX_CHECK(resample_reduce(up, down, &p), "vfx_resample: bad rates %d/%d", up, down);
+  VFX_CHECK(p.up != p.down, "vfx_resample: up / down = %d / %d is the same rate (nothing to filter)", up, down);
+  VFX_CHECK(p.R > 0, "vfx_resample: the filter of %d/%d (%d taps) does not fit the kernel's LDS budget", p.up, p.down, 2 * p.hl + 1);
+  VFX_CHECK(ntaps == 2 * p.hl + 1, "vfx_resample: %d taps given, %d/%d needs 2*10*%d + 1 = %d", ntaps, p.up, p.down,
+            std::max(p.up, p.down), 2 * p.hl + 1);
+  VFX_CHECK(x && taps && y && lens_in && B > 0 && B <= 65535 * kResampleMaxClips, "vfx_resample: bad argument");
+  VFX_CHECK(x0 >= 0 && Lx >= 0 && ldx >= Lx && o0 >= 0 && n_out > 0 && ldy >= n_out, "vfx_resample: bad window or row stride");
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lens_in[b] >= 0, "vfx_resample: clip %d has a negative length", b);
+    int64_t k0, k1;
+    resample_window(lens_in[b], p, o0, n_out, &k0, &k1);
+    VFX_CHECK(k1 <= k0 || (x0 <= k0 && k1 <= x0 + Lx),
+              "vfx_resample: clip %d: outputs [%lld, %lld) need input samples [%lld, %lld), the window holds [%lld, %lld)", b,
+              (long long)o0, (long long)(o0 + n_out), (long long)k0, (long long)k1, (long long)x0, (long long)(x0 + Lx));
+  }
+  launch_resample(x, B, ldx, x0, Lx, lens_in, p, taps, y, ldy, o0, n_out, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(h && re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

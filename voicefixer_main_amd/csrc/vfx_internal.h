@@ -439,6 +439,35 @@ void launch_chunk_ola(const float* frames, const float* window, float scale, int
                       int lead, int L, float* y, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// polyphase resampler (resample.hip): scipy.signal.resample_poly's arithmetic, bit for bit
+// ---------------------------------------------------------------------------------------------
+struct ResamplePair {
+  int up, down;  // reduced by their gcd
+  int hl;        // half filter length, 10 * max(up, down): the filter has 2 hl + 1 taps
+  int R;         // outputs per lane of k_resample_poly; 0 = the filter does not fit the LDS budget (the pair is refused)
+};
+// false for up or down <= 0 (or beyond 2^20 after the reduction)
+bool resample_reduce(int64_t up, int64_t down, ResamplePair* out);
+int64_t resample_out_len(int64_t n_in, const ResamplePair& p);  // ceil(n_in up / down) = len(resample_poly(x[:n_in]))
+// The one rule of the output-window form: the input indices [k0, k1) that outputs [o0, o0 + n) of a clip of n_in samples read
+// (0 <= k0 <= k1 <= n_in; every index in it is read by one of those outputs; k0 = k1 = 0 when none is -- outputs past the clip's
+// end are zeros)
+void resample_window(int64_t n_in, const ResamplePair& p, int64_t o0, int64_t n, int64_t* k0, int64_t* k1);
+
+constexpr int kResampleMaxClips = 64;  // clips per launch: their lengths are kernel arguments
+struct ResampleArgs {
+  const float* x;     // (clips, ldx): global input indices [x0, x0 + Lx) of each clip
+  const float* taps;  // 2 hl + 1
+  float* y;           // (clips, ldy): global output indices [o0, o0 + n_out)
+  int64_t ldx, x0, Lx, ldy, o0, n_out;
+  int up, down, hl, span_max;
+  int64_t lens_in[kResampleMaxClips], lens_out[kResampleMaxClips];
+};
+// x, y, taps: device; lens_in: HOST (B).  The caller has checked that [x0, x0 + Lx) holds what resample_window asks for.
+void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx, const int64_t* lens_in, const ResamplePair& p,
+                     const float* taps, float* y, int64_t ldy, int64_t o0, int64_t n_out, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {

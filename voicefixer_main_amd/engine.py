@@ -4,6 +4,7 @@ All compute happens in the HIP library; this file only allocates outputs with to
 passes raw device pointers + the current HIP stream, and raises on any failure.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -57,6 +58,7 @@ class Engine:
         self._state = {}        # model id -> (state_dict, prefix) as loaded, for the stricter-arithmetic twin
         self._strict = None
         self.analysis_model = MODEL_UNET_MEL   # what restore_gsr(_varlen) runs (select_analysis)
+        self._resample_taps = {}   # (up, down) -> the filter of resample_poly on the device
 
     def close(self):
         if getattr(self, "_strict", None) is not None:
@@ -239,6 +241,88 @@ class Engine:
                                           float(scale), B, n_chunks, win, hop, lead, length, _ptr(y),
                                           self._stream()), "vfx_chunk_ola")
         return y
+
+    # ------------------------------------------------------------------ resampling (librosa.load(path, sr) = scipy resample_poly)
+    @staticmethod
+    def resample_ratio(sr_in, sr_out):
+        """(up, down) of resample_poly for sr_in -> sr_out, reduced by their gcd."""
+        g = math.gcd(int(sr_in), int(sr_out))
+        return int(sr_out) // g, int(sr_in) // g
+
+    @staticmethod
+    def resample_out_len(n_in, sr_in, sr_out):
+        """len(resample_poly(x[:n_in], up, down)) = ceil(n_in * up / down); -1 for a pair the kernel does not take."""
+        up, down = Engine.resample_ratio(sr_in, sr_out)
+        return int(_lib.load().vfx_resample_out_len(int(n_in), up, down))
+
+    @staticmethod
+    def resample_supported(sr_in, sr_out):
+        """True when `resample` takes sr_in -> sr_out on the device (the same rate included)."""
+        return int(sr_in) > 0 and int(sr_out) > 0 and Engine.resample_out_len(1, sr_in, sr_out) >= 0
+
+    @staticmethod
+    def resample_window(n_in, sr_in, sr_out, o0, n):
+        """The input indices [k0, k1) that outputs [o0, o0 + n) of a clip of n_in samples read (vfx_resample_window): what the
+        window form of `resample` must be handed.  (0, 0) when none is (outputs past the clip's end are zeros)."""
+        up, down = Engine.resample_ratio(sr_in, sr_out)
+        k0, k1 = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().vfx_resample_window(int(n_in), up, down, int(o0), int(n), ctypes.byref(k0), ctypes.byref(k1)),
+                   "vfx_resample_window")
+        return k0.value, k1.value
+
+    def resample_taps(self, sr_in, sr_out):
+        """The float32 taps resample_poly builds for the pair (scipy's own firwin call), cached on the device per (up, down)."""
+        key = self.resample_ratio(sr_in, sr_out)
+        taps = self._resample_taps.get(key)
+        if taps is None:
+            from scipy.signal import firwin
+            up, down = key
+            m = max(up, down)
+            h = firwin(2 * 10 * m + 1, 1.0 / m, window=("kaiser", 5.0)).astype(np.float32)
+            h *= up                                  # in float32, as resample_poly does
+            taps = torch.from_numpy(h).to(self.device)
+            self._resample_taps[key] = taps
+        return taps
+
+    def resample(self, x, sr_in, sr_out, lengths=None, x0=0, o0=0, n_out=None):
+        """scipy.signal.resample_poly(x, up, down) of float32 clips on the device, bit for bit: x (B, L) or (L,) -> (y, out_lengths).
+
+        lengths: each clip's true length (default: x0 + L); samples past it count as zero, and y is zero at or past a clip's output
+        length out_lengths[b] = ceil(lengths[b] * up / down).  Window form (streamed input): x holds input indices [x0, x0 + L) of
+        every clip, and y (B, n_out) receives outputs [o0, o0 + n_out) (default: up to the longest clip's output length); the window
+        must hold what `resample_window` asks for, or the call raises.  1-D x gives a 1-D y and an int out length."""
+        x = _dev_f32(x, self.device)
+        squeeze = x.dim() == 1
+        if squeeze:
+            x = x[None]
+        B, L = x.shape
+        x0, o0 = int(x0), int(o0)
+        lengths = [x0 + L] * B if lengths is None else [int(v) for v in lengths]
+        if len(lengths) != B:
+            raise ValueError("resample: %d lengths for %d clips" % (len(lengths), B))
+        up, down = self.resample_ratio(sr_in, sr_out)
+        out_lengths = [self.resample_out_len(n, sr_in, sr_out) for n in lengths]
+        if any(n < 0 for n in out_lengths):
+            raise RuntimeError("resample: %d Hz -> %d Hz is not supported on the device (its filter does not fit the kernel)"
+                               % (sr_in, sr_out))
+        if n_out is None:
+            n_out = max(0, max(out_lengths) - o0)
+        if up == down:      # the same rate: resample_poly returns a copy
+            y = torch.zeros((B, int(n_out)), device=self.device, dtype=torch.float32)
+            for b in range(B):
+                k0, k1 = self.resample_window(lengths[b], sr_in, sr_out, o0, n_out)
+                if k1 > k0:
+                    if k0 < x0 or k1 > x0 + L:
+                        raise RuntimeError("resample: the window [%d, %d) lacks samples [%d, %d)" % (x0, x0 + L, k0, k1))
+                    y[b, k0 - o0:k1 - o0] = x[b, k0 - x0:k1 - x0]
+        else:               # (the kernel writes every element of y: zeros at or past a clip's output length)
+            y = torch.empty((B, int(n_out)), device=self.device, dtype=torch.float32)
+            if n_out > 0:
+                taps = self.resample_taps(sr_in, sr_out)
+                lens = (ctypes.c_int64 * B)(*lengths)
+                _lib.check(self.lib.vfx_resample(self.h, _ptr(x), B, L, x0, L, lens, up, down, _ptr(taps), taps.numel(), _ptr(y),
+                                                 int(n_out), o0, int(n_out), self._stream()), "vfx_resample")
+        return (y[0], out_lengths[0]) if squeeze else (y, out_lengths)
 
     def resunet_mel(self, mel_linear):
         """Generator.forward: linear mel (B,T,128) -> log10 mel (B,T,128)."""

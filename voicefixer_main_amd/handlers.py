@@ -7,7 +7,8 @@ normalisation, trim_center, concatenation), with the models of `voicefixer_main_
 
 Wav I/O uses the stdlib `wave` module + numpy (the reference needs librosa / soundfile, which
 are outside the hot path and not installed here): PCM16 mono/stereo in, PCM16 out, polyphase
-resampling (scipy) when the file's rate is not 44.1 kHz.
+resampling when the file's rate is not 44.1 kHz: on the device in the handlers (Engine.resample, DEVICE_RESAMPLE), with scipy in
+`load_wav` -- the same values bit for bit.
 """
 import wave
 
@@ -21,6 +22,9 @@ EPS = 1e-12        # evaluation_proc/metrics.py:16
 EPS_UNIFY = 1e-8   # evaluation_proc/utils.py:8 (energy_unify)
 SEG_SECONDS = 60
 MAX_SEGMENT_BATCH = 4   # full segments of one file per call when no per-segment metrics are asked for (4 x 60 s: 3 GB of workspace)
+# input and target files at another rate than 44.1 kHz are resampled on the device (Engine.resample: resample_poly's values bit for
+# bit, the input streamed segment by segment); False: the whole-file host path (load_wav, scipy) -- the same values, for comparisons
+DEVICE_RESAMPLE = True
 
 
 # ----------------------------------------------------------------------------------------
@@ -204,18 +208,45 @@ def _staged_upload(host, n, device):
     return out
 
 
+def _pcm16_upload(frames, ch, device):
+    """PCM16 frames (n * ch int16, host) -> mono float32 on `device`, the values `load_wav` computes.  Mono travels as the file's
+    2-byte samples into pinned memory and is widened on the device (int16 -> float32 -> / 32768 is exact in both places); stereo
+    is widened and down-mixed on the host exactly as `load_wav` does (the float32 channel mean) and travels as float32."""
+    if ch == 1:
+        n = frames.shape[0]
+        host = _PINNED.take(n, torch.int16)
+        host[:n].numpy()[:] = frames      # one copy, into page-locked memory
+        return _staged_upload(host, n, device).to(torch.float32) / 32768.0
+    x = (frames.astype(np.float32) / 32768.0).reshape(-1, ch).mean(axis=1)
+    host = _PINNED.take(x.shape[0], torch.float32)
+    host[:x.shape[0]].numpy()[:] = x
+    return _staged_upload(host, x.shape[0], device)
+
+
 class _WavReader:
     """librosa.load(path, 44100) semantics of `load_wav`, streamed: the PCM16 frames of a 44.1 kHz file are read one segment
-    at a time, so the GPU starts on the first 60 s while the host is still reading the rest.  Anything else (other sample
-    widths, other rates: polyphase resampling needs the whole signal) falls back to `load_wav`, then slices."""
+    at a time, so the GPU starts on the first 60 s while the host is still reading the rest.  Given an `engine`, a PCM16 file at
+    another rate the device resampler takes streams as well: `read_device` reads the input span a segment's outputs need plus the
+    filter's halo (Engine.resample_window) and resamples that window on the device -- resample_poly's values bit for bit, so
+    the same values `load_wav` returns.  Anything else (other sample widths, rate pairs the kernel does not take, no engine)
+    falls back to `load_wav`, then slices."""
 
-    def __init__(self, path, sample_rate=44100):
+    def __init__(self, path, sample_rate=44100, engine=None):
+        self.path, self.sample_rate = path, sample_rate
         self.f = wave.open(path, "rb")
         self.ch, width, sr = self.f.getnchannels(), self.f.getsampwidth(), self.f.getframerate()
         self.n = self.f.getnframes()
         self.whole = None
         self.pos = 0
-        if width != 2 or sr != sample_rate:
+        self.engine = None
+        if width == 2 and sr != sample_rate and engine is not None and engine.resample_supported(sr, sample_rate):
+            # device resampling: len() from the header, the input frames read on demand
+            self.engine, self.sr = engine, sr
+            self.n_in = self.n                                 # input frames (the header's count until a short read says otherwise)
+            self.n = engine.resample_out_len(self.n_in, sr, sample_rate)
+            self.buf = np.empty((0,), dtype="<i2")           # input frames [buf0, buf0 + len(buf) / ch) already read
+            self.buf0 = 0
+        elif width != 2 or sr != sample_rate:
             self.f.close()
             self.f = None
             self.whole = load_wav(path, sample_rate)
@@ -226,6 +257,12 @@ class _WavReader:
 
     def read(self, count):
         """next `count` samples (fewer at the end of the file) as mono float32, the values `load_wav` returns"""
+        if self.whole is None and self.engine is not None:      # (host reads of a device-resampled file: the whole file, once)
+            self.f.close()
+            self.f = None
+            self.engine = None
+            self.whole = load_wav(self.path, self.sample_rate)
+            self.n = self.whole.shape[0]
         if self.whole is not None:
             x = self.whole[self.pos:self.pos + count]
         else:
@@ -239,11 +276,44 @@ class _WavReader:
             self.n = self.pos
         return x
 
+    def _read_resampled(self, count, device):
+        """read_device of a device-resampled file: outputs [pos, pos + count) from the input window they need."""
+        eng, sr, ch = self.engine, self.sr, self.ch
+        n = min(count, self.n - self.pos)
+        if n <= 0:
+            self.n = self.pos
+            return torch.empty((0,), dtype=torch.float32, device=device)
+        k0, k1 = eng.resample_window(self.n_in, sr, self.sample_rate, self.pos, n)
+        have = self.buf0 + self.buf.shape[0] // ch
+        if k1 > have:
+            raw = self.f.readframes(k1 - have)
+            got = len(raw) // (2 * ch)
+            self.buf = np.concatenate([self.buf, np.frombuffer(raw[:got * 2 * ch], dtype="<i2")])
+            if got < k1 - have:
+                # the data chunk ended early: `load_wav` resamples the frames that are there -- the clip is that long.  Earlier
+                # windows read real frames only, so what they gave is what the shorter clip gives (the missing frames are the
+                # zeros past its end)
+                self.n_in = have + got
+                self.n = eng.resample_out_len(self.n_in, sr, self.sample_rate)
+                n = min(count, self.n - self.pos)
+                if n <= 0:
+                    self.n = self.pos
+                    return torch.empty((0,), dtype=torch.float32, device=device)
+                k0, k1 = eng.resample_window(self.n_in, sr, self.sample_rate, self.pos, n)
+        # the window [k0, k1) of the input, widened and down-mixed as load_wav does, then resampled on the device
+        x = _pcm16_upload(self.buf[(k0 - self.buf0) * ch:(k1 - self.buf0) * ch], ch, device)
+        y, _ = eng.resample(x, sr, self.sample_rate, lengths=[self.n_in], x0=k0, o0=self.pos, n_out=n)
+        self.buf, self.buf0 = self.buf[(k0 - self.buf0) * ch:], k0     # later windows start at or after k0
+        self.pos += n
+        return y
+
     def read_device(self, count, device):
         """`read` for the handlers: the same float32 values as a tensor on `device`.  Mono PCM16 at the target rate (what the
         evaluation sets hold) travels as the file's 2-byte samples and is widened on the device -- int16 -> float32 -> / 32768 is exact
         in both places, so the values are bit-identical to `read`'s -- which leaves the host one copy into pinned memory instead
         of two float32 passes over twice the bytes (round 5: the host's part of a 150-s file was 3-25 ms depending on the box)."""
+        if self.engine is not None:
+            return self._read_resampled(count, device)
         if self.whole is None and self.ch == 1:
             raw = self.f.readframes(count)
             n = len(raw) // 2
@@ -252,9 +322,7 @@ class _WavReader:
                 self.n = self.pos
             if n == 0:
                 return torch.empty((0,), dtype=torch.float32, device=device)
-            host = _PINNED.take(n, torch.int16)
-            host[:n].numpy()[:] = np.frombuffer(raw, dtype="<i2")      # one copy, into page-locked memory
-            return _staged_upload(host, n, device).to(torch.float32) / 32768.0
+            return _pcm16_upload(np.frombuffer(raw, dtype="<i2"), 1, device)
         x = self.read(count)
         host = _PINNED.take(x.shape[0], torch.float32)
         host[:x.shape[0]].numpy()[:] = x
@@ -263,6 +331,23 @@ class _WavReader:
     def close(self):
         if self.f is not None:
             self.f.close()
+
+
+def _open_input(path, model):
+    """The handlers' reader of an input file: streamed, and resampled on the device when DEVICE_RESAMPLE is set."""
+    return _WavReader(path, 44100, engine=model.engine if DEVICE_RESAMPLE else None)
+
+
+def _load_target(path, model, device):
+    """The whole target file at 44.1 kHz, the values of load_wav(path, 44100): resampled on the device when DEVICE_RESAMPLE is set
+    (a device tensor), on the host otherwise (a numpy array, as before)."""
+    if not DEVICE_RESAMPLE:
+        return load_wav(path, sample_rate=44100)
+    reader = _open_input(path, model)
+    try:
+        return reader.read_device(len(reader), device)
+    finally:
+        reader.close()
 
 
 class _WavWriter:
@@ -361,8 +446,8 @@ def handler_gsr_voicefixer(input, output, target, ckpt, device, needrefresh=Fals
         # every file starts with clean flags: an exception in the middle of the previous file (frame mismatch, a short tail
         # segment, out of memory) skipped its flag check and would otherwise hand this file a stale saturation / negative bit
         model.engine.take_flags()
-        reader = _WavReader(input, 44100)
-        tgt = load_wav(target, sample_rate=44100) if target is not None else None
+        reader = _open_input(input, model)
+        tgt = _load_target(target, model, device) if target is not None else None
         writer = _WavWriter(output, 44100)
         peaks = []
         seg_length = 44100 * SEG_SECONDS
@@ -460,8 +545,8 @@ def handler_ssr_unet(input, output, target, ckpt, device, needrefresh=False, met
         # every file starts with clean flags: an exception in the middle of the previous file (frame mismatch, a short tail
         # segment, out of memory) skipped its flag check and would otherwise hand this file a stale saturation / negative bit
         model.engine.take_flags()
-        reader = _WavReader(input, 44100)
-        tgt = load_wav(target, sample_rate=44100) if target is not None else None
+        reader = _open_input(input, model)
+        tgt = _load_target(target, model, device) if target is not None else None
         writer = _WavWriter(output, 44100)
         peaks = []
         seg_length = 44100 * SEG_SECONDS

@@ -301,6 +301,21 @@ def read_checkpoint(path):
     return _state_dict_of(_load_checkpoint_obj(path), path)
 
 
+def _resample_list(engine, wavs, sample_rate):
+    """A list of 1-D clips at `sample_rate` -> the same clips at the engine's rate (44.1 kHz), resampled on the device as ONE padded
+    batch with their lengths (every clip's values are those of its own resample_poly call).  An empty list (the ranks other
+    than the source of a distributed restore_list) and clips already at 44.1 kHz pass through."""
+    sr_out = engine.cfg.sample_rate
+    if int(sample_rate) == sr_out or not wavs:
+        return wavs
+    lengths = [int(w.shape[-1]) for w in wavs]
+    batch = torch.zeros((len(wavs), max(max(lengths), 1)), device=engine.device, dtype=torch.float32)
+    for i, w in enumerate(wavs):
+        batch[i, :lengths[i]] = w.reshape(-1).to(device=engine.device, dtype=torch.float32)
+    y, out_lengths = engine.resample(batch, sample_rate, sr_out, lengths=lengths)
+    return [y[i, :n] for i, n in enumerate(out_lengths)]
+
+
 class _Base:
     def __init__(self, hp=None, channels=1, type_target="vocals", device="cuda:0", engine=None):
         self.hp = hp
@@ -462,23 +477,28 @@ class VoiceFixer(_Base):
 
     __call__ = forward
 
-    def restore(self, wav, unify_energy=False):
-        """Fused handler() segment body: wav (B,1,L) or (B,L) -> restored wav of the same shape."""
+    def restore(self, wav, unify_energy=False, sample_rate=44100):
+        """Fused handler() segment body: wav (B,1,L) or (B,L) -> restored wav of the same shape, at 44.1 kHz.  Input at another
+        `sample_rate` is resampled on the device first (Engine.resample: resample_poly's values, as librosa.load(path, 44100))."""
         squeeze = wav.dim() == 3
         x = wav[:, 0] if squeeze else wav
+        if int(sample_rate) != self.engine.cfg.sample_rate:
+            x, _ = self.engine.resample(x, sample_rate, self.engine.cfg.sample_rate)
         out = self.engine.restore_gsr(x, unify_energy=unify_energy)
         out = _rerun_if_saturated(self.engine, out, lambda e: e.restore_gsr(x, unify_energy=unify_energy))
         return out[:, None] if squeeze else out
 
-    def restore_list(self, wavs, unify_energy=False, max_batch=128):
+    def restore_list(self, wavs, unify_energy=False, max_batch=128, sample_rate=44100):
         """A test set of clips of ARBITRARY lengths (what the reference's harness iterates, one handler call per file:
         evaluation_proc/eval.py:119-134): list of 1-D tensors -> list of restored 1-D tensors in the same order.  The clips go
         through the library sorted by length, up to `max_batch` per call, as padded batches with their lengths
         (vfx_restore_gsr_varlen: every clip's result is the one its own batch-of-one call gives; inside a call the mel ResUNet
         runs once per padded frame count over all its clips, the vocoder per run of clips of similar length); with
         torch.distributed initialised the list is dealt over the ranks by length and gathered on rank 0
-        (dist.restore_sharded_lengths).  The 16-bit mode's re-run guarantee holds per batch."""
+        (dist.restore_sharded_lengths).  The 16-bit mode's re-run guarantee holds per batch.  Clips at another `sample_rate` are
+        resampled to 44.1 kHz on the device first, as one batch with their lengths (_resample_list); the results are at 44.1 kHz."""
         from . import dist as vdist
+        wavs = _resample_list(self.engine, wavs, sample_rate)
         fn = vdist.checked_restore(self.engine, unify_energy=unify_energy)
         return vdist.restore_sharded_lengths(fn, wavs, self.device, max_batch=max_batch)
 
@@ -507,13 +527,15 @@ class SSR_UNet(_Base):
 
     __call__ = forward
 
-    def restore_list(self, wavs, max_batch=16):
+    def restore_list(self, wavs, max_batch=16, sample_rate=44100):
         """A test set of clips of ARBITRARY lengths through `pre` + `forward` (eval_ssr_unet.py:77-114, one handler call per file
         in the reference): list of 1-D tensors -> list of restored 1-D tensors in the same order.  Clips whose frame counts pad
         to the same multiple of 64 share one call of the library as a padded batch with their lengths (vfx_restore_ssr_varlen);
-        with torch.distributed initialised the list is dealt over the ranks (dist.restore_sharded_lengths)."""
+        with torch.distributed initialised the list is dealt over the ranks (dist.restore_sharded_lengths).  Clips at another
+        `sample_rate` are resampled to 44.1 kHz on the device first (_resample_list); the results are at 44.1 kHz."""
         from . import dist as vdist
         eng = self.engine
+        wavs = _resample_list(eng, wavs, sample_rate)
 
         def fn(x, lengths=None):
             if lengths is None:
