@@ -272,6 +272,27 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
 int vfx_spectral_metrics(vfx_handle* h, const float* est, const float* target, int B, int T, int F,
                          float* out, void* stream);
 
+/*
+ * The scores of AudioMetrics.evaluation (evaluation_proc/metrics.py:25-106) for a padded batch of (est, target) waveform pairs at
+ * 44.1 kHz: est, target (B, Lmax) device, pair b = the first lengths[b] samples of row b; lengths is a HOST array int[B] with
+ * 2646 <= lengths[b] <= Lmax (at least 7 STFT frames: skimage rejects a smaller SSIM image).  out (B, 9) device doubles, in this order:
+ *   0 sisdr                     speechmetrics sisdr over the whole clip (metrics.py:59): a = (eps + <t,e>) / (<t,t> + eps),
+ *                               10 log10((eps + |a t|^2) / (eps + |e - a t|^2)), eps = DBL_EPSILON
+ *   1 lsd                       AudioMetrics.lsd (metrics.py:83-87) of the magnitude spectrograms (metrics.py:75)
+ *   2 non_log_sispec            AudioMetrics.sispec (metrics.py:89-95) of the magnitudes (metrics.py:76)
+ *   3 sispec                    ... of to_log of the magnitudes, log10(max(x, 1e-8)) (metrics.py:77, utils.py:60-61)
+ *   4 ssim                      AudioMetrics.ssim (metrics.py:97-106): skimage structural_similarity(win_size=7) of the (T, 1025) image
+ *   5-8 final_mel_lsd, final_non_log_mel_sispec, final_mel_sispec, final_mel_ssim: the same four of the (T, 128) mel images
+ *                               (metrics.py:80-83; MelScale(n_mels=128, sample_rate=44100, n_stft=1025) of the magnitudes)
+ * The magnitude is |STFT| with n_fft 2048, hop 441, periodic Hann, centre reflect padding and no eps clamp (librosa.stft,
+ * metrics.py:45): T = 1 + lengths[b] / 441 frames per clip.  Every per-clip sum is in float64, in an order fixed by the clip alone:
+ * a clip's nine numbers do not depend on the batch it is in nor on Lmax.  The call sub-batches its clips so that its workspace,
+ * owned by the handle and grown only when needed, stays under 256 MiB (more only when ONE clip needs more).
+ */
+#define VFX_N_AUDIO_METRICS 9
+int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
+                      void* stream);
+
 /* Read-and-clear the sticky device flags (synchronises `stream`). */
 int vfx_take_flags(vfx_handle* h, void* stream, int* flags_out);
 /* ... only the bits in `mask` (VFX_FLAG_*): the others stay raised for a later check. */

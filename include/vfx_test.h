@@ -103,6 +103,14 @@ int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const f
  * -1 = bad arguments. */
 int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, int precision, int tuning);
 
+/* The SSIM of vfx_audio_metrics alone (k_ssim_tiles + k_score_final): skimage structural_similarity(win_size=7) of the images
+ * est[b], target[b] of (B, T, F) device tensors, clip b = its first rows[b] rows; rows HOST int[B], 7 <= rows[b] <= T, F >= 7
+ * -> out (B) device doubles.  Synchronises. */
+int vfx_op_ssim(vfx_handle* h, const float* est, const float* target, int B, int T, int F, const int* rows, double* out, void* stream);
+/* The SI-SDR of vfx_audio_metrics alone (k_sisdr_slabs + k_score_final): est[b, :lens[b]] against target[b, :lens[b]] of (B, L)
+ * device tensors; lens HOST int[B], 1 <= lens[b] <= L -> out (B) device doubles.  Synchronises. */
+int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, int L, const int* lens, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

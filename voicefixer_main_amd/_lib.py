@@ -22,6 +22,7 @@ TUNE_NO_FUSED_STACKS, TUNE_NO_FUSED_WIDE, TUNE_NO_FUSED_UNET, TUNE_NO_PERSISTENT
 FLAG_NEGATIVE_INPUT = 1
 FLAG_F16_SATURATED = 2   # precision 2: an activation of the vocoder left the fp16 range and was clamped
 FLAG_PEAK_NORMALISED = 4  # vfx_restore_gsr divided a clip by its peak (the reference's "Exceed energy limit" warning)
+N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metrics
 
 
 class VfxConfig(ctypes.Structure):
@@ -55,6 +56,7 @@ SIGNATURES = {
     "vfx_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_int,
                              c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_chunk_ola": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_void_p, c_void_p]),
@@ -99,6 +101,8 @@ TEST_SIGNATURES = {
     "vfx_op_voc_final": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p,
                                  c_void_p]),
     "vfx_plan_voc_upsampler_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vfx_op_ssim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -889,9 +889,10 @@ int vfx_create(int device, const vfx_config* cfg, vfx_handle** out) {
   }
   h->d_flags = static_cast<int*>(h->blob.alloc(sizeof(int)));
   VFX_HIP(hipMemset(h->d_flags, 0, sizeof(int)));
-  // rows 0-2: the batch; 3-5: the ResUNet group, 6-8: the vocoder run in flight; 9: frames of a vfx_analysis_mel call
-  h->d_lens = static_cast<int*>(h->blob.alloc(10 * kMaxVarlenClips * sizeof(int)));
-  VFX_HIP(hipMemset(h->d_lens, 0, 10 * kMaxVarlenClips * sizeof(int)));
+  // rows 0-2: the batch; 3-5: the ResUNet group, 6-8: the vocoder run in flight; 9: frames of a vfx_analysis_mel call;
+  // 10-11: samples / frames of a vfx_audio_metrics sub-batch
+  h->d_lens = static_cast<int*>(h->blob.alloc(12 * kMaxVarlenClips * sizeof(int)));
+  VFX_HIP(hipMemset(h->d_lens, 0, 12 * kMaxVarlenClips * sizeof(int)));
   *out = h.release();
   VFX_API_END
 }
@@ -906,6 +907,7 @@ int vfx_destroy(vfx_handle* h) {
   h->retired.clear();
   if (h->arena) (void)hipFree(h->arena);
   if (h->scratch) (void)hipFree(h->scratch);
+  if (h->score_ws) (void)hipFree(h->score_ws);
   delete h;
   if (prev >= 0) (void)hipSetDevice(prev);
   return 0;
@@ -1052,6 +1054,110 @@ int vfx_spectral_metrics(vfx_handle* h, const float* est, const float* target, i
   if (tmp.arena_bytes > h->arena_bytes) h->plans.clear();  // plans hold absolute pointers into the old arena
   bind_plan(h, tmp);
   launch_spectral_metrics(est, target, B, T, F, reinterpret_cast<double*>(h->arena), out, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// AudioMetrics.evaluation (score.hip)
+// ---------------------------------------------------------------------------------------------
+// byte offsets of vfx_audio_metrics' workspace for n clips of at most T frames and nslab SI-SDR slabs
+struct ScoreLayout {
+  size_t sp[2], mel[2], fr[2], ss[2], sisdr, end;
+};
+static ScoreLayout score_layout(int n, int T, int nslab, int nbins, int nmels) {
+  auto up = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+  ScoreLayout l{};
+  const size_t nsp = (size_t)n * T * nbins * sizeof(float), nmel = (size_t)n * T * nmels * sizeof(float);
+  const size_t nfr = (size_t)n * T * 7 * sizeof(double);
+  size_t o = 0;
+  for (int i = 0; i < 2; ++i) l.sp[i] = o, o += up(nsp);
+  for (int i = 0; i < 2; ++i) l.mel[i] = o, o += up(nmel);
+  for (int i = 0; i < 2; ++i) l.fr[i] = o, o += up(nfr);
+  l.ss[0] = o, o += up((size_t)n * ssim_tiles(T, nbins) * sizeof(double));
+  l.ss[1] = o, o += up((size_t)n * ssim_tiles(T, nmels) * sizeof(double));
+  l.sisdr = o, o += up((size_t)n * nslab * 3 * sizeof(double));
+  l.end = o;
+  return l;
+}
+
+static char* ensure_score_ws(vfx_handle* h, size_t bytes) {
+  if (bytes <= h->score_ws_bytes) return h->score_ws;
+  VFX_HIP(hipDeviceSynchronize());   // the previous buffer may still be read by launches in flight
+  if (h->score_ws) VFX_HIP(hipFree(h->score_ws));
+  h->score_ws = nullptr;
+  h->score_ws_bytes = 0;
+  void* p = nullptr;
+  VFX_HIP(hipMalloc(&p, bytes));
+  h->score_ws = static_cast<char*>(p);
+  h->score_ws_bytes = bytes;
+  return h->score_ws;
+}
+
+int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
+                      void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(est && target && lengths && out && B > 0 && Lmax > 0, "vfx_audio_metrics: bad argument");
+  const int hop = h->cfg.hop, nbins = h->cfg.n_fft / 2 + 1, nmels = h->cfg.n_mels;
+  VFX_CHECK(h->cfg.n_fft == 2048 && nmels == 128, "vfx_audio_metrics: needs the 44.1 kHz front end (n_fft 2048, 128 mel bands)");
+  const int min_len = 6 * hop;  // 7 frames: the smallest image skimage's 7 x 7 SSIM accepts
+  for (int b = 0; b < B; ++b)
+    VFX_CHECK(lengths[b] >= min_len && lengths[b] <= Lmax, "vfx_audio_metrics: clip %d has %d samples (need %d <= length <= Lmax = %d)", b,
+              lengths[b], min_len, Lmax);
+  // sub-batches of consecutive clips: each as many as keep its workspace (spectra of ITS longest clip) under the cap
+  struct Sub { int b0, n, T, nslab; };
+  std::vector<Sub> subs;
+  size_t need = 0;
+  for (int b0 = 0; b0 < B;) {
+    Sub s{b0, 0, 0, 0};
+    while (b0 + s.n < B && s.n < kMaxVarlenClips) {
+      const int Tn = std::max(s.T, frames_of(h, lengths[b0 + s.n])), nsn = std::max(s.nslab, sisdr_slabs(lengths[b0 + s.n]));
+      if (s.n > 0 && score_layout(s.n + 1, Tn, nsn, nbins, nmels).end > kScoreWorkspaceBytes) break;
+      s.T = Tn;
+      s.nslab = nsn;
+      ++s.n;
+    }
+    need = std::max(need, score_layout(s.n, s.T, s.nslab, nbins, nmels).end);
+    subs.push_back(s);
+    b0 += s.n;
+  }
+  char* const ws = ensure_score_ws(h, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_l = h->d_lens + 10 * kMaxVarlenClips;
+  int* const d_t = h->d_lens + 11 * kMaxVarlenClips;
+  std::vector<int> frames(B);
+  for (int b = 0; b < B; ++b) frames[b] = frames_of(h, lengths[b]);
+  for (const Sub& sb : subs) {
+    const ScoreLayout l = score_layout(sb.n, sb.T, sb.nslab, nbins, nmels);
+    auto f32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+    auto f64 = [&](size_t o) { return reinterpret_cast<double*>(ws + o); };
+    launch_set_frames(d_l, lengths + sb.b0, sb.n, s);
+    launch_set_frames(d_t, frames.data() + sb.b0, sb.n, s);
+    const float* src[2] = {est + (int64_t)sb.b0 * Lmax, target + (int64_t)sb.b0 * Lmax};
+    // librosa.stft magnitudes (eps 0) and their mel projection, every clip framed at its own length; rows past it are zeros
+    for (int i = 0; i < 2; ++i)
+      launch_stft_mel(h->fe, src[i], sb.n, Lmax, sb.T, f32(l.mel[i]), f32(l.sp[i]), nullptr, nullptr, 0, hop, 0.f, s, d_l);
+    launch_sisdr_slabs(src[0], src[1], sb.n, Lmax, d_l, sb.nslab, f64(l.sisdr), s);
+    launch_score_frames(f32(l.sp[0]), f32(l.sp[1]), sb.n, sb.T, nbins, d_t, f64(l.fr[0]), s);
+    launch_score_frames(f32(l.mel[0]), f32(l.mel[1]), sb.n, sb.T, nmels, d_t, f64(l.fr[1]), s);
+    launch_ssim_tiles(f32(l.sp[0]), f32(l.sp[1]), sb.n, sb.T, nbins, d_t, f64(l.ss[0]), s);
+    launch_ssim_tiles(f32(l.mel[0]), f32(l.mel[1]), sb.n, sb.T, nmels, d_t, f64(l.ss[1]), s);
+    ScoreFinalArgs a;
+    a.lens = d_l;
+    a.frames = d_t;
+    a.sisdr_ws = f64(l.sisdr);
+    a.nslab = sb.nslab;
+    a.frames_ws[0] = f64(l.fr[0]);
+    a.frames_ws[1] = f64(l.fr[1]);
+    a.T = sb.T;
+    a.ssim_ws[0] = f64(l.ss[0]);
+    a.ssim_ws[1] = f64(l.ss[1]);
+    a.ssim_stride[0] = ssim_tiles(sb.T, nbins);
+    a.ssim_stride[1] = ssim_tiles(sb.T, nmels);
+    a.F[0] = nbins;
+    a.F[1] = nmels;
+    a.out = out + (int64_t)sb.b0 * VFX_N_AUDIO_METRICS;
+    launch_score_final(a, sb.n, s);
+  }
   VFX_API_END
 }
 

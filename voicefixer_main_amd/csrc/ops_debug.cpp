@@ -877,3 +877,59 @@ extern "C" int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, in
     return -1;
   }
 }
+
+// one column of k_score_final's (B, 9) output -> out (B)
+static void score_column(const ScoreFinalArgs& a0, int B, int col, DeviceBlob& blob, double* out, hipStream_t s) {
+  ScoreFinalArgs a = a0;
+  a.out = static_cast<double*>(blob.alloc((size_t)B * VFX_N_AUDIO_METRICS * sizeof(double)));
+  launch_score_final(a, B, s);
+  VFX_HIP(hipMemcpy2DAsync(out, sizeof(double), a.out + col, VFX_N_AUDIO_METRICS * sizeof(double), sizeof(double), B,
+                           hipMemcpyDeviceToDevice, s));
+  VFX_HIP(hipStreamSynchronize(s));
+}
+
+extern "C" int vfx_op_ssim(vfx_handle* h, const float* est, const float* target, int B, int T, int F, const int* rows, double* out,
+                           void* stream) {
+  try {
+    VFX_CHECK(h && est && target && rows && out && B > 0 && B <= 65535 && T >= 7 && F >= 7, "vfx_op_ssim: bad argument");
+    for (int b = 0; b < B; ++b) VFX_CHECK(rows[b] >= 7 && rows[b] <= T, "vfx_op_ssim: image %d has %d rows (need 7 .. T = %d)", b, rows[b], T);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const int* d_rows = upload_lens(sc.blob, rows, B);
+    const int64_t stride = ssim_tiles(T, F);
+    double* ws = static_cast<double*>(sc.blob.alloc((size_t)B * stride * sizeof(double)));
+    launch_ssim_tiles(est, target, B, T, F, d_rows, ws, s);
+    ScoreFinalArgs a;
+    a.frames = d_rows;
+    a.ssim_ws[0] = ws;
+    a.ssim_stride[0] = stride;
+    a.F[0] = F;
+    score_column(a, B, 4, sc.blob, out, s);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, int L, const int* lens, double* out, void* stream) {
+  try {
+    VFX_CHECK(h && est && target && lens && out && B > 0 && B <= 65535 && L > 0, "vfx_op_sisdr: bad argument");
+    for (int b = 0; b < B; ++b) VFX_CHECK(lens[b] >= 1 && lens[b] <= L, "vfx_op_sisdr: clip %d has %d samples (need 1 .. L = %d)", b, lens[b], L);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const int* d_lens = upload_lens(sc.blob, lens, B);
+    const int nslab = sisdr_slabs(L);
+    double* ws = static_cast<double*>(sc.blob.alloc((size_t)B * nslab * 3 * sizeof(double)));
+    launch_sisdr_slabs(est, target, B, L, d_lens, nslab, ws, s);
+    ScoreFinalArgs a;
+    a.lens = d_lens;
+    a.sisdr_ws = ws;
+    a.nslab = nslab;
+    score_column(a, B, 0, sc.blob, out, s);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}

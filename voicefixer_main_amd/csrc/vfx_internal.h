@@ -432,6 +432,32 @@ void launch_from_log(const float* logmel, const float* mel_in, int B, int T, int
 void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, float* ws, bool have_peak, float* out,
                       hipStream_t s, int* flags = nullptr);  // flags: VFX_FLAG_PEAK_NORMALISED when a clip was divided by its peak
 void launch_spectral_metrics(const float* est, const float* tgt, int B, int T, int F, double* ws, float* out, hipStream_t s);
+
+// score.hip: the scores of vfx_audio_metrics.  Per-clip partial sums (float64) in ws; lens = samples, frames = rows per clip (device)
+constexpr int kSisdrSlab = 16384;                    // samples per partial sum of the SI-SDR inner products
+constexpr int kSsimTileH = 32, kSsimTileW = 64;      // window positions per SSIM workgroup
+constexpr size_t kScoreWorkspaceBytes = 256u << 20;  // vfx_audio_metrics sub-batches its clips under this (vfx_handle::score_ws)
+inline int sisdr_slabs(int64_t len) { return (int)((len + kSisdrSlab - 1) / kSisdrSlab); }
+inline int ssim_tiles(int rows, int F) {  // the tiles of a (rows, F) image, rows and F >= 7
+  return (rows - 6 + kSsimTileH - 1) / kSsimTileH * ((F - 6 + kSsimTileW - 1) / kSsimTileW);
+}
+struct ScoreFinalArgs {
+  const int* lens = nullptr;              // samples per clip (the SI-SDR slabs)
+  const int* frames = nullptr;            // rows per clip (the frame and SSIM sums)
+  const double* sisdr_ws = nullptr;       // [B][nslab][3] or null (column 0 not written)
+  int nslab = 0;
+  const double* frames_ws[2] = {};        // [B][T][7] of the STFT rows, of the mel rows, or null (columns 1-3, 5-7)
+  int T = 0;
+  const double* ssim_ws[2] = {};          // [B][ssim_stride] tile sums of the two images, or null (columns 4, 8)
+  int64_t ssim_stride[2] = {};
+  int F[2] = {};
+  double* out = nullptr;                  // [B][VFX_N_AUDIO_METRICS]
+};
+void launch_sisdr_slabs(const float* est, const float* tgt, int B, int64_t ld, const int* lens, int nslab, double* ws, hipStream_t s);
+void launch_score_frames(const float* est, const float* tgt, int B, int T, int F, const int* frames, double* ws, hipStream_t s);
+// ws [B][ssim_tiles(T, F)]
+void launch_ssim_tiles(const float* est, const float* tgt, int B, int T, int F, const int* frames, double* ws, hipStream_t s);
+void launch_score_final(const ScoreFinalArgs& a, int B, hipStream_t s);
 int64_t count_nonfinite(const float* p, int64_t n, hipStream_t s);  // debug aid, synchronises
 void launch_chunk_gather(const float* x, int B, int L, int win, int hop, int lead, int n_chunks, float* chunks,
                          hipStream_t s);
@@ -681,11 +707,14 @@ struct vfx_handle {
   char* arena = nullptr;
   size_t arena_bytes = 0;
   int* d_flags = nullptr;
-  int* d_lens = nullptr;     // [10][kMaxVarlenClips]: rows 0-2 samples / frames / vocoder frames per clip of the varlen call in flight;
+  int* d_lens = nullptr;     // [12][kMaxVarlenClips]: rows 0-2 samples / frames / vocoder frames per clip of the varlen call in flight;
                              // rows 3-4 frames / batch index of the clips of its ResUNet group in flight (5 unused); rows 6-8 samples /
-                             // frames / vocoder frames of its vocoder run in flight; row 9 frames per clip of a vfx_analysis_mel call
+                             // frames / vocoder frames of its vocoder run in flight; row 9 frames per clip of a vfx_analysis_mel call;
+                             // rows 10-11 samples / frames per clip of the vfx_audio_metrics sub-batch in flight
   char* scratch = nullptr;   // the tensors between the plans of a varlen call (api.cpp: ensure_scratch), grow-only
   size_t scratch_bytes = 0;
+  char* score_ws = nullptr;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more), grow-only
+  size_t score_ws_bytes = 0;
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;

@@ -220,6 +220,24 @@ class Engine:
                    "vfx_spectral_metrics")
         return out
 
+    def audio_metrics(self, est, target, lengths=None):
+        """AudioMetrics.evaluation's nine scores (metrics.METRIC_KEYS order) of waveform pairs at 44.1 kHz: est, target (B, L) or
+        (L,), pair b = the first lengths[b] samples of row b (default: all L; 2646 <= lengths[b] <= L) -> (B, 9) float64 on the
+        device (vfx_audio_metrics)."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        if est.shape != target.shape or est.dim() != 2:
+            raise ValueError("audio_metrics: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
+        B, L = est.shape
+        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+        if len(lengths) != B:
+            raise ValueError("audio_metrics: %d lengths for %d clips" % (len(lengths), B))
+        out = torch.empty((B, _lib.N_AUDIO_METRICS), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_audio_metrics(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
+                                              self._stream()), "vfx_audio_metrics")
+        return out
+
     def chunk_gather(self, x, win, hop, lead, n_chunks):
         """F.unfold with zero padding: x (B, L) -> (B, n_chunks, win), chunk k = x[k*hop - lead : ... + win]."""
         x = _dev_f32(x, self.device)
@@ -611,3 +629,23 @@ class Engine:
             self.h, _ptr(x), B, T, C, w.ctypes.data_as(ctypes.c_void_p), float(bias), float(slope), int(bool(x_f16)),
             None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(wav), self._stream()), "vfx_op_voc_final")
         return wav
+
+    def op_ssim(self, est, target, rows=None):
+        """The SSIM kernels of audio_metrics alone: (B, T, F) images, image b = its first rows[b] rows -> (B,) float64."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        B, T, F = est.shape
+        rows = [T] * B if rows is None else [int(v) for v in rows]
+        out = torch.empty(B, device=self.device, dtype=torch.float64)
+        _lib.check(_lib.load_test().vfx_op_ssim(self.h, _ptr(est), _ptr(target), B, T, F, (ctypes.c_int * B)(*rows), _ptr(out),
+                                                self._stream()), "vfx_op_ssim")
+        return out
+
+    def op_sisdr(self, est, target, lengths=None):
+        """The SI-SDR kernels of audio_metrics alone: (B, L), clip b = its first lengths[b] samples -> (B,) float64 dB."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        B, L = est.shape
+        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+        out = torch.empty(B, device=self.device, dtype=torch.float64)
+        _lib.check(_lib.load_test().vfx_op_sisdr(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
+                                                 self._stream()), "vfx_op_sisdr")
+        return out

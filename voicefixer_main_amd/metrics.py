@@ -1,0 +1,226 @@
+"""Scoring of restored test sets: the drop-in for evaluation_proc.metrics.AudioMetrics and eval.py's aggregate_score / gather_score.
+
+`AudioMetrics.evaluation` (evaluation_proc/metrics.py:55-81) returns these keys, computed on the GPU by vfx_audio_metrics
+(include/vfx.h; Engine.audio_metrics):
+
+    sisdr, lsd, non_log_sispec, sispec, ssim, final_mel_lsd, final_non_log_mel_sispec, final_mel_sispec, final_mel_ssim
+
+What differs from the reference, on purpose:
+  * STOI, PESQ and the bsseval scores are not computed, and their keys are absent (no implementation to pin them against).
+  * Only 44.1 kHz targets: any other rate raises ValueError, like the reference's "Bad Samplerate" for rates it has no STFT for
+    (its 16 kHz branch is not implemented).  An est file at another rate than its target, or of another length, makes that pair
+    an error: speechmetrics would zero-pad the shorter signal and librosa.load would resample est.
+  * aggregate_score leaves a pair that fails out of the table and its mean; the reference records the previous pair's scores
+    under the failed pair's name again.
+"""
+import csv
+import json
+import logging
+import os
+import wave
+
+import numpy as np
+import torch
+
+from . import handlers
+
+METRIC_KEYS = ("sisdr", "lsd", "non_log_sispec", "sispec", "ssim",
+               "final_mel_lsd", "final_non_log_mel_sispec", "final_mel_sispec", "final_mel_ssim")
+SAMPLE_RATE = 44100
+MIN_SAMPLES = 6 * 441   # 7 STFT frames: skimage's 7 x 7 SSIM rejects a smaller spectrogram
+
+
+def read_list(fname):
+    """evaluation_proc/utils.py:73-79."""
+    with open(fname, "r") as f:
+        return [line.strip("\n") for line in f.readlines()]
+
+
+def write_json(d, fname):
+    with open(fname, "w") as f:
+        f.write(json.dumps(d))
+
+
+def load_json(fname):
+    with open(fname, "r") as f:
+        return json.load(f)
+
+
+def _wav_info(path):
+    with wave.open(path, "rb") as f:
+        return f.getnframes(), f.getframerate()
+
+
+class AudioMetrics:
+    """evaluation_proc/metrics.py:20-106 at 44.1 kHz.  `engine`: an Engine (or anything with `device` and
+    `audio_metrics(est, target, lengths)`); default: a new Engine on cuda:0."""
+
+    def __init__(self, rate, engine=None):
+        if int(rate) != SAMPLE_RATE:
+            raise ValueError("Bad Samplerate: %s (only %d Hz test sets are scored)" % (rate, SAMPLE_RATE))
+        self.rate = int(rate)
+        if engine is None:
+            from .engine import Engine
+            engine = Engine("cuda:0")
+        self.engine = engine
+
+    # ------------------------------------------------------------------ files
+    def evaluation(self, est, target):
+        """est, target: .wav paths -> {key: float} (METRIC_KEYS); {} when target is None."""
+        if target is None:
+            return {}
+        r = self.evaluation_list([(est, target)])[0]
+        if isinstance(r, Exception):
+            raise r
+        return r
+
+    def _check_pair(self, est, target):
+        (n_e, sr_e), (n_t, sr_t) = _wav_info(est), _wav_info(target)
+        if sr_t != SAMPLE_RATE:
+            raise ValueError("Bad Samplerate: %s is at %d Hz" % (target, sr_t))
+        if sr_e != sr_t:
+            raise ValueError("%s is at %d Hz, its target %s at %d Hz" % (est, sr_e, target, sr_t))
+        if n_e != n_t:
+            raise ValueError("%s has %d samples, its target %s %d" % (est, n_e, target, n_t))
+        if n_t < MIN_SAMPLES:
+            raise ValueError("%s has %d samples: SSIM needs at least %d (7 STFT frames)" % (target, n_t, MIN_SAMPLES))
+        return n_t
+
+    def evaluation_list(self, pairs, max_batch=128):
+        """[(est_path, target_path), ...] -> one entry per pair, in order: the {key: float} dict, or the exception that pair
+        raised.  The pairs are read and scored sorted by length, up to `max_batch` per padded batch (one vfx_audio_metrics call)."""
+        results = [None] * len(pairs)
+        ok = []
+        for i, (est, target) in enumerate(pairs):
+            try:
+                ok.append((self._check_pair(est, target), i))
+            except Exception as e:  # noqa: BLE001 -- reported per pair
+                results[i] = e
+        ok.sort()
+        dev = getattr(self.engine, "device", torch.device("cpu"))
+        for at in range(0, len(ok), max_batch):
+            chunk = ok[at:at + max_batch]
+            Lmax = chunk[-1][0]
+            est = np.zeros((len(chunk), Lmax), np.float32)
+            tgt = np.zeros((len(chunk), Lmax), np.float32)
+            lengths, idx = [], []
+            for j, (n, i) in enumerate(chunk):
+                try:
+                    e = handlers.load_wav(pairs[i][0], SAMPLE_RATE)
+                    t = handlers.load_wav(pairs[i][1], SAMPLE_RATE)
+                except Exception as ex:  # noqa: BLE001
+                    results[i] = ex
+                    continue
+                est[len(idx), :n], tgt[len(idx), :n] = e, t
+                lengths.append(n)
+                idx.append(i)
+            if not idx:
+                continue
+            k = len(idx)
+            scores = self.engine.audio_metrics(torch.from_numpy(est[:k]).to(dev), torch.from_numpy(tgt[:k]).to(dev), lengths)
+            scores = scores.cpu().numpy().tolist()
+            for j, i in enumerate(idx):
+                results[i] = {key: float(v) for key, v in zip(METRIC_KEYS, scores[j])}
+        return results
+
+    # ------------------------------------------------------------------ tensors (metrics.py:83-106)
+    def lsd(self, est, target):
+        """(B, C, T, F) linear magnitudes -> (B, C, 1, 1)."""
+        return handlers.lsd(est, target)
+
+    def sispec(self, est, target):
+        """(B, C, T, F) -> the batch mean, a 0-d tensor."""
+        return handlers.sispec(est, target)
+
+    def ssim(self, est, target):
+        """(B, C, T, F) -> (B, C, 1, 1) float64: skimage structural_similarity(win_size=7) per (batch, channel) image."""
+        if est.shape[-1] < 7 or est.shape[-2] < 7:
+            raise ValueError("ssim: an image of %s is smaller than the 7 x 7 window" % (tuple(est.shape[-2:]),))
+        return handlers.ssim(est, target)
+
+
+def _parse(line):
+    parts = line.split(" ")
+    return (parts[0], None) if len(parts) == 1 else (parts[0], parts[1])
+
+
+def _means(rows):
+    """Column means over the rows that hold a number in that column (pandas DataFrame.mean)."""
+    cols, sums, counts = [], {}, {}
+    for r in rows.values():
+        for k, v in r.items():
+            if k not in sums:
+                cols.append(k)
+                sums[k], counts[k] = 0.0, 0
+            if isinstance(v, (int, float)) and not isinstance(v, bool):
+                sums[k] += float(v)
+                counts[k] += 1
+    return cols, {k: (sums[k] / counts[k] if counts[k] else float("nan")) for k in cols}
+
+
+def _write_table(path, rows, cols, mean_row=None):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow([""] + cols)
+        for name, r in rows.items():
+            w.writerow([name] + [repr(r[c]) if isinstance(r.get(c), float) else r.get(c, "") for c in cols])
+        if mean_row is not None:
+            w.writerow(["mean"] + [repr(mean_row[c]) for c in cols])
+
+
+def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=None):
+    """evaluation_proc/eval.py:25-86.  metas[testset] = {"rate": ..., "list": path of the `source [target]` list}; the restored
+    file of a line is save_dir/testset/basename(source).  Per pair with a target: the scores, updated with the handler's JSON
+    beside the restored file (save_dir/testset/<name>.json, when it exists), are written back to that JSON.  Per test set:
+    <testset>.csv (one row per target basename and a `mean` row) and result.json (the means).  A pair that fails is logged and
+    left out.  Returns {testset: {target basename: scores}}."""
+    if metas is None:
+        raise ValueError("aggregate_score: metas ({testset: {'rate', 'list'}}) is required (the reference's Config is not part of "
+                         "this package)")
+    result = {}
+    for n, testset in enumerate(testsets):
+        logging.info("scoring %s (%d / %d)", testset, n + 1, len(testsets))
+        res_dir = os.path.join(save_dir, testset)
+        os.makedirs(res_dir, exist_ok=True)
+        meta = metas[testset]
+        lst = read_list(meta["list"])
+        if limit_number is not None:
+            lst = lst[:limit_number]
+        judger = AudioMetrics(rate=meta["rate"], engine=engine)
+        pairs, names = [], []
+        for line in lst:
+            source, target = _parse(line)
+            if target is None:
+                continue
+            pairs.append((os.path.join(res_dir, os.path.basename(source)), target))
+            names.append(os.path.basename(target))
+        rows = {}
+        for (est, target), name, r in zip(pairs, names, judger.evaluation_list(pairs)):
+            if isinstance(r, Exception):
+                logging.error("scoring %s against %s failed: %r", est, target, r)
+                continue
+            js = est[:-4] + ".json"
+            if os.path.exists(js):
+                r.update(load_json(js))
+            write_json(r, js)
+            rows[name] = r
+        result[testset] = rows
+        if pairs:
+            cols, mean = _means(rows)
+            _write_table(os.path.join(res_dir, testset + ".csv"), rows, cols, mean)
+            write_json(mean, os.path.join(res_dir, "result.json"))
+            logging.info("%s: %s", testset, mean)
+    return result
+
+
+def gather_score(output_path, testsets):
+    """evaluation_proc/eval.py:224-230: output_path/result.csv, one row per test set that has a result.json."""
+    final = {}
+    for t in testsets:
+        p = os.path.join(output_path, t, "result.json")
+        if os.path.exists(p):
+            final[t] = load_json(p)
+    if final:
+        cols, _ = _means(final)
+        _write_table(os.path.join(output_path, "result.csv"), final, cols)
+    return final
