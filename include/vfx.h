@@ -262,6 +262,21 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
                  const float* taps, int ntaps, float* y, int64_t ldy, int64_t o0, int64_t n_out, void* stream);
 
 /*
+ * Zero-phase IIR filtering of a padded batch of clips: scipy.signal.sosfiltfilt(sos, x) per clip (the degradation simulator's
+ * low-pass and band-pass, tools/dsp/lowpass.py:58-133), bit for bit, for float32 and float64 input.
+ *   x (B, ldx) device, float32 (x_f64 = 0) or float64 (x_f64 = 1); clip b = the first lengths[b] samples of row b (HOST int64[B]);
+ *   sos (S, 6) HOST doubles, rows b0 b1 b2 1 a1 a2, 1 <= S <= 16;  zi (S, 2) HOST doubles = scipy.signal.sosfilt_zi(sos);
+ *   padlen = 3 * (2 S + 1 - min(#{b2 == 0}, #{a2 == 0})), sosfiltfilt's default; every clip must be longer than padlen;
+ *   y (B, ldy) device float64: row b receives the lengths[b] filtered samples, and zeros from there up to ldy.
+ * Each clip is extended oddly by padlen samples at both ends in ITS dtype, widened to float64, filtered forward from the state
+ * zi * ext[0] and backward from zi * (last forward sample) with x_c = b0 x_n + z0, z0 = (b1 x_n - a1 x_c) + z1, z1 = b2 x_n - a2 x_c
+ * per section -- every product and sum rounded on its own -- and trimmed.  Fails, launching nothing, for S or padlen out of range or a
+ * clip that is not longer than padlen.  The forward pass lives in a scratch buffer of the handle, grown on demand.
+ */
+int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S,
+                    const double* zi, int padlen, double* y, int64_t ldy, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

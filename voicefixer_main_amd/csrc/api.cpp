@@ -908,6 +908,7 @@ int vfx_destroy(vfx_handle* h) {
   if (h->arena) (void)hipFree(h->arena);
   if (h->scratch) (void)hipFree(h->scratch);
   if (h->score_ws) (void)hipFree(h->score_ws);
+  if (h->sos_ws) (void)hipFree(h->sos_ws);
   delete h;
   if (prev >= 0) (void)hipSetDevice(prev);
   return 0;
@@ -1217,6 +1218,44 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
               (long long)o0, (long long)(o0 + n_out), (long long)k0, (long long)k1, (long long)x0, (long long)(x0 + Lx));
   }
   launch_resample(x, B, ldx, x0, Lx, lens_in, p, taps, y, ldy, o0, n_out, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// zero-phase IIR filter (scipy.signal.sosfiltfilt on the device: sosfilt.hip)
+// ---------------------------------------------------------------------------------------------
+static char* ensure_sos_ws(vfx_handle* h, size_t bytes) {
+  if (bytes <= h->sos_ws_bytes) return h->sos_ws;
+  VFX_HIP(hipDeviceSynchronize());   // the previous buffer may still be read by launches in flight
+  if (h->sos_ws) VFX_HIP(hipFree(h->sos_ws));
+  h->sos_ws = nullptr;
+  h->sos_ws_bytes = 0;
+  void* p = nullptr;
+  VFX_HIP(hipMalloc(&p, bytes));
+  h->sos_ws = static_cast<char*>(p);
+  h->sos_ws_bytes = bytes;
+  return h->sos_ws;
+}
+
+int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S,
+                    const double* zi, int padlen, double* y, int64_t ldy, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(S >= 1 && S <= kSosMaxSections, "vfx_sosfiltfilt: %d sections (need 1 <= S <= %d)", S, kSosMaxSections);
+  VFX_CHECK(x && lengths && sos && zi && y && B > 0 && (x_f64 == 0 || x_f64 == 1), "vfx_sosfiltfilt: bad argument");
+  VFX_CHECK(padlen >= 0 && padlen <= 3 * (2 * kSosMaxSections + 1), "vfx_sosfiltfilt: padlen %d (need 0 <= padlen <= %d)", padlen,
+            3 * (2 * kSosMaxSections + 1));
+  for (int i = 0; i < S; ++i) VFX_CHECK(sos[i * 6 + 3] == 1.0, "vfx_sosfiltfilt: sos[%d][3] = %g, should be 1", i, sos[i * 6 + 3]);
+  int64_t lmax = 0;
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] > padlen, "vfx_sosfiltfilt: clip %d has %lld samples: the length must be greater than padlen, which is %d", b,
+              (long long)lengths[b], padlen);
+    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 1024,
+              "vfx_sosfiltfilt: clip %d has %lld samples, the rows hold %lld and %lld", b, (long long)lengths[b], (long long)ldx, (long long)ldy);
+    lmax = std::max(lmax, lengths[b]);
+  }
+  const int64_t ldf = (lmax + 2 * padlen + 63) / 64 * 64;
+  double* const f = reinterpret_cast<double*>(ensure_sos_ws(h, (size_t)std::min(B, kSosMaxClips) * ldf * sizeof(double)));
+  launch_sosfiltfilt(x, x_f64, B, ldx, lengths, sos, S, zi, padlen, f, ldf, y, ldy, static_cast<hipStream_t>(stream));
   VFX_API_END
 }
 

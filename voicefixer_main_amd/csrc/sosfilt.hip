@@ -1,0 +1,226 @@
+// sosfilt.hip -- batched zero-phase IIR filter (gfx950), bit-identical to scipy.signal.sosfiltfilt(sos, x) on float32 / float64 input.
+//
+// sosfiltfilt extends a clip oddly by padlen samples at each end IN THE CLIP'S DTYPE (ext = [2 x[0] - x[padlen:0:-1], x,
+// 2 x[-1] - x[-2:-padlen-2:-1]]), widens to float64, runs the cascade of S second-order sections forward over ext from the state
+// zi * ext[0], runs it again over the forward result read from its last sample to its first from the state zi * (that last sample),
+// reverses, and drops the padlen samples at each end.  Per sample and section (transposed direct form II, a0 = 1), in float64 with
+// every product and sum rounded on its own:
+//
+//   x_c = b0 x_n + z0;   z0 = (b1 x_n - a1 x_c) + z1;   z1 = b2 x_n - a2 x_c;   the section's output is x_c
+//
+// Contraction is off in this file, so the kernel does exactly those roundings (tests/test_gpu_sosfiltfilt.py compares with
+// torch.equal).
+//
+// Lane mapping: one lane per (clip, section).  A clip's S sections sit in consecutive lanes of one 16-lane row, 16 / S clips per row
+// (at most 8), four rows per wave.  The cascade is skewed: at step n the lane of section s works on sample n - s, and takes its input
+// from the lane below it (a row_shr:1 DPP move of the previous step's x_c); section 0 reads its sample from LDS, the last section
+// writes its output over it.  A block is two waves: wave 0 runs the recurrence over one 64-sample tile of every clip while wave 1
+// writes the previous tile's outputs to global memory and fetches the next tile's inputs -- one coalesced row of 64 samples per
+// clip -- into the other LDS buffer; the waves meet at one barrier per tile.  The loop-carried chain per step is the four dependent
+// float64 operations of the z0 update, whatever the batch size: the pass is latency-bound, parallel over clips x sections only.
+#include "vfx_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace vfx {
+
+constexpr int kSosRow = kSosTile + 1;  // doubles per LDS row: the pad spreads the clips' rows over the banks
+
+struct SosArgs {
+  const void* x;  // (clips, ldx) float32 or float64
+  double* f;      // (clips, ldf): the forward pass over the extended clips
+  double* y;      // (clips, ldy)
+  int64_t ldx, ldf, ldy;
+  int x_f64, bwd, B, S, cpr, C, padlen;
+  double sos[kSosMaxSections][5];  // b0 b1 b2 a1 a2
+  double zi[kSosMaxSections][2];
+  int len[kSosMaxClips];
+};
+
+// the value one lane below within the 16-lane row (row_shr:1); lane 0 of a row gets 0
+__device__ inline double row_shr1(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, 0x111, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+// sample n of the odd extension of x[0 .. len), 0 <= n < len + 2 padlen, len > padlen: computed in T, then widened
+template <typename T>
+__device__ inline double ext_at(const T* x, int64_t len, int padlen, int64_t n) {
+  if (n < padlen) return (double)(T(2) * x[0] - x[padlen - n]);
+  n -= padlen;
+  if (n < len) return (double)x[n];
+  n -= len;
+  return (double)(T(2) * x[len - 1] - x[len - 2 - n]);
+}
+
+struct SosLane {
+  double b0, b1, b2, a1, a2;  // the lane's section
+  double z0, z1, xc;          // its state and its last output
+  int s;
+  bool first, last;
+};
+
+// kSosTile steps of the skewed cascade over one LDS row per clip.  WARM: the tile that starts a pass -- the lane of section s
+// starts at step s.
+template <bool WARM>
+__device__ __forceinline__ void sos_tile(double* row, SosLane& L) {
+  double xl = row[0];
+#pragma unroll 4
+  for (int i = 0; i < kSosTile; ++i) {
+    const double below = row_shr1(L.xc);  // every lane takes part: a DPP move reads nothing from a lane that is masked off
+    const double xin = L.first ? xl : below;
+    xl = row[i + 1];  // (i = kSosTile - 1 reads the row's pad)
+    const double xc = L.b0 * xin + L.z0;
+    const double z0 = (L.b1 * xin - L.a1 * xc) + L.z1;
+    const double z1 = L.b2 * xin - L.a2 * xc;
+    if (!WARM || i >= L.s) {
+      L.xc = xc;
+      L.z0 = z0;
+      L.z1 = z1;
+    }
+    if (L.last) row[i] = L.xc;
+  }
+}
+
+__global__ __launch_bounds__(128) void k_sosfilt(const SosArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sos_smem[];  // [2][C][kSosRow]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int S = a.S, C = a.C, padlen = a.padlen;
+  const bool bwd = a.bwd != 0;
+  const int c0 = blockIdx.x * C;
+  const int nc = min(C, a.B - c0);
+  int maxlen = 0;
+  for (int c = 0; c < nc; ++c) maxlen = max(maxlen, a.len[c0 + c]);
+  // steps of the skewed cascade over the longest clip; the backward pass stops where its last kept output is done
+  const int64_t steps = (int64_t)maxlen + (bwd ? padlen : 2 * padlen) + S - 1;
+  const int ntiles = (int)((steps + kSosTile - 1) / kSosTile);
+
+  // wave 1: one row of kSosTile samples per clip, lane i <-> sample i of the tile
+  auto load_tile = [&](int t, int which) {
+    double* const buf = sos_smem + which * C * kSosRow;
+    const int64_t n = (int64_t)t * kSosTile + lane;
+#pragma unroll 4
+    for (int c = 0; c < nc; ++c) {
+      const int64_t len = a.len[c0 + c], lext = len + 2 * padlen;
+      double v = 0.0;
+      if (n < lext) {
+        if (bwd)
+          v = a.f[(int64_t)(c0 + c) * a.ldf + (lext - 1 - n)];
+        else if (a.x_f64)
+          v = ext_at(static_cast<const double*>(a.x) + (int64_t)(c0 + c) * a.ldx, len, padlen, n);
+        else
+          v = ext_at(static_cast<const float*>(a.x) + (int64_t)(c0 + c) * a.ldx, len, padlen, n);
+      }
+      buf[c * kSosRow + lane] = v;
+    }
+  };
+  // slot i of tile t holds the cascade's output for position t kSosTile + i - (S - 1) of the pass
+  auto flush_tile = [&](int t, int which) {
+    const double* const buf = sos_smem + which * C * kSosRow;
+    const int64_t p = (int64_t)t * kSosTile + lane - (S - 1);
+#pragma unroll 4
+    for (int c = 0; c < nc; ++c) {
+      const int64_t len = a.len[c0 + c], lext = len + 2 * padlen;
+      const double v = buf[c * kSosRow + lane];
+      if (bwd) {
+        const int64_t q = lext - 1 - p - padlen;  // index in the clip
+        if (p >= 0 && q >= 0 && q < len) a.y[(int64_t)(c0 + c) * a.ldy + q] = v;
+      } else if (p >= 0 && p < lext) {
+        a.f[(int64_t)(c0 + c) * a.ldf + p] = v;
+      }
+    }
+  };
+
+  // wave 0: lane -> (clip, section)
+  const int r = lane & 15;
+  const int cin = r / S, s = r - cin * S;
+  const int lc = (lane >> 4) * a.cpr + cin;
+  const bool active = cin < a.cpr && lc < nc;
+  const int lcc = active ? lc : 0;
+  SosLane L;
+  L.s = s;
+  L.first = s == 0;
+  L.last = active && s == S - 1;
+  L.b0 = a.sos[s][0], L.b1 = a.sos[s][1], L.b2 = a.sos[s][2], L.a1 = a.sos[s][3], L.a2 = a.sos[s][4];
+  L.z0 = L.z1 = L.xc = 0.0;
+  if (wave == 0) {
+    const int64_t len = a.len[c0 + lcc], lext = len + 2 * padlen;
+    double x0;
+    if (bwd)
+      x0 = a.f[(int64_t)(c0 + lcc) * a.ldf + lext - 1];
+    else if (a.x_f64)
+      x0 = ext_at(static_cast<const double*>(a.x) + (int64_t)(c0 + lcc) * a.ldx, len, padlen, 0);
+    else
+      x0 = ext_at(static_cast<const float*>(a.x) + (int64_t)(c0 + lcc) * a.ldx, len, padlen, 0);
+    L.z0 = a.zi[s][0] * x0;
+    L.z1 = a.zi[s][1] * x0;
+  } else {
+    load_tile(0, 0);
+  }
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    if (wave == 0) {
+      double* const row = sos_smem + ((t & 1) * C + lcc) * kSosRow;
+      if (t == 0)
+        sos_tile<true>(row, L);
+      else
+        sos_tile<false>(row, L);
+    } else {
+      if (t >= 1) flush_tile(t - 1, (t + 1) & 1);
+      if (t + 1 < ntiles) load_tile(t + 1, (t + 1) & 1);
+    }
+    __syncthreads();
+  }
+  if (wave == 1) flush_tile(ntiles - 1, (ntiles - 1) & 1);
+  if (bwd) {  // zeros past each clip's end
+    for (int c = 0; c < nc; ++c) {
+      double* const yr = a.y + (int64_t)(c0 + c) * a.ldy;
+      for (int64_t j = (int64_t)a.len[c0 + c] + tid; j < a.ldy; j += 128) yr[j] = 0.0;
+    }
+  }
+}
+
+int sosfilt_clips_per_wave(int S) { return 4 * std::min(16 / S, 8); }
+
+void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S, const double* zi,
+                        int padlen, double* f, int64_t ldf, double* y, int64_t ldy, hipStream_t s) {
+  VFX_CHECK(S >= 1 && S <= kSosMaxSections, "sosfiltfilt: %d sections (1 .. %d)", S, kSosMaxSections);
+  SosArgs a{};
+  a.ldx = ldx;
+  a.ldf = ldf;
+  a.ldy = ldy;
+  a.x_f64 = x_f64;
+  a.S = S;
+  a.cpr = std::min(16 / S, 8);
+  a.C = 4 * a.cpr;
+  a.padlen = padlen;
+  for (int i = 0; i < S; ++i) {
+    a.sos[i][0] = sos[i * 6 + 0];
+    a.sos[i][1] = sos[i * 6 + 1];
+    a.sos[i][2] = sos[i * 6 + 2];
+    a.sos[i][3] = sos[i * 6 + 4];
+    a.sos[i][4] = sos[i * 6 + 5];
+    a.zi[i][0] = zi[i * 2 + 0];
+    a.zi[i][1] = zi[i * 2 + 1];
+  }
+  const size_t lds = (size_t)2 * a.C * kSosRow * sizeof(double);  // at most 33 280 bytes
+  const size_t elt = x_f64 ? sizeof(double) : sizeof(float);
+  for (int b0 = 0; b0 < B; b0 += kSosMaxClips) {  // the clips' lengths travel as kernel arguments, kSosMaxClips per launch
+    a.B = std::min(B - b0, kSosMaxClips);
+    a.x = static_cast<const char*>(x) + (size_t)b0 * ldx * elt;
+    a.f = f;  // the scratch is reused: the launches are ordered on the stream
+    a.y = y + (int64_t)b0 * ldy;
+    for (int i = 0; i < a.B; ++i) a.len[i] = (int)lengths[b0 + i];
+    const dim3 grid((unsigned)((a.B + a.C - 1) / a.C));
+    for (int bwd = 0; bwd < 2; ++bwd) {
+      a.bwd = bwd;
+      hipLaunchKernelGGL(k_sosfilt, grid, dim3(128), lds, s, a);
+      VFX_HIP(hipGetLastError());
+    }
+  }
+}
+
+}  // namespace vfx

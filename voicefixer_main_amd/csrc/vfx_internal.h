@@ -494,6 +494,19 @@ void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx,
                      const float* taps, float* y, int64_t ldy, int64_t o0, int64_t n_out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// zero-phase IIR filter (sosfilt.hip): scipy.signal.sosfiltfilt's arithmetic, bit for bit
+// ---------------------------------------------------------------------------------------------
+constexpr int kSosTile = 64;          // samples per LDS tile of a clip (one wave-wide row)
+constexpr int kSosMaxSections = 16;
+constexpr int kSosMaxClips = 128;     // clips per launch: their lengths are kernel arguments
+int sosfilt_clips_per_wave(int S);    // 4 rows of min(16 / S, 8) clips
+// x (float32 or float64), f, y: device; lengths, sos (S, 6), zi (S, 2): HOST.  f (min(B, kSosMaxClips), ldf) receives the forward pass
+// over the extended clips, ldf >= max length + 2 padlen.  The caller has checked padlen < lengths[b] <= min(ldx, ldy) and 1 <= S <= 16.
+// Both passes of every clip; y[b, lengths[b] .. ldy) = 0.
+void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S, const double* zi,
+                        int padlen, double* f, int64_t ldf, double* y, int64_t ldy, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {
@@ -715,6 +728,8 @@ struct vfx_handle {
   size_t scratch_bytes = 0;
   char* score_ws = nullptr;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more), grow-only
   size_t score_ws_bytes = 0;
+  char* sos_ws = nullptr;    // vfx_sosfiltfilt's forward pass over the extended clips (float64), grow-only
+  size_t sos_ws_bytes = 0;
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;

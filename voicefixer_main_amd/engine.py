@@ -342,6 +342,64 @@ class Engine:
                                                  int(n_out), o0, int(n_out), self._stream()), "vfx_resample")
         return (y[0], out_lengths[0]) if squeeze else (y, out_lengths)
 
+    # ------------------------------------------------------------------ zero-phase IIR filter (scipy.signal.sosfiltfilt)
+    MAX_SOS_SECTIONS = 16
+
+    @staticmethod
+    def _check_sos(sos):
+        """sos as SciPy validates it (its wording), float64 (S, 6) C-contiguous."""
+        sos = np.ascontiguousarray(np.atleast_2d(np.asarray(sos)), dtype=np.float64)
+        if sos.ndim != 2:
+            raise ValueError("sos array must be 2D")
+        if sos.shape[1] != 6:
+            raise ValueError("sos array must be shape (n_sections, 6)")
+        if not (sos[:, 3] == 1).all():
+            raise ValueError("sos[:, 3] should be all ones")
+        if not 1 <= sos.shape[0] <= Engine.MAX_SOS_SECTIONS:
+            raise ValueError("sosfiltfilt: %d sections, the device filter takes 1 .. %d" % (sos.shape[0], Engine.MAX_SOS_SECTIONS))
+        return sos
+
+    @staticmethod
+    def sosfiltfilt_padlen(sos):
+        """The default padlen of scipy.signal.sosfiltfilt(sos, x): 3 * (2 S + 1 - min(#{b2 == 0}, #{a2 == 0}))."""
+        sos = Engine._check_sos(sos)
+        ntaps = 2 * sos.shape[0] + 1 - min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum()))
+        return 3 * ntaps
+
+    def sosfiltfilt(self, x, sos, lengths=None):
+        """scipy.signal.sosfiltfilt(sos, x) of every clip on the device, bit for bit: x (B, L) or (L,), float32 or float64 (any other
+        dtype is converted to float64 first; SciPy extends an integer clip in its own dtype, where the extension can wrap) -> float64 tensor of the same shape.  lengths: each clip's true length (default L);
+        a row is zero past it.  ValueError, with SciPy's wording, for a clip that is not longer than padlen and for a malformed sos."""
+        sos = self._check_sos(sos)
+        padlen = self.sosfiltfilt_padlen(sos)
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        x = x.to(self.device).contiguous()
+        squeeze = x.dim() == 1
+        if squeeze:
+            x = x[None]
+        if x.dim() != 2:
+            raise ValueError("sosfiltfilt: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
+        B, L = x.shape
+        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+        if len(lengths) != B:
+            raise ValueError("sosfiltfilt: %d lengths for %d clips" % (len(lengths), B))
+        if B == 0 or min(lengths) <= padlen:
+            raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+        if max(lengths) > L:
+            raise ValueError("sosfiltfilt: a clip of %d samples in rows of %d" % (max(lengths), L))
+        from scipy.signal import sosfilt_zi
+        zi = np.ascontiguousarray(sosfilt_zi(sos), dtype=np.float64)
+        y = torch.empty((B, L), device=self.device, dtype=torch.float64)
+        dbl = ctypes.POINTER(ctypes.c_double)
+        lens = (ctypes.c_int64 * B)(*lengths)
+        _lib.check(self.lib.vfx_sosfiltfilt(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, lens, sos.ctypes.data_as(dbl),
+                                            sos.shape[0], zi.ctypes.data_as(dbl), padlen, _ptr(y), L, self._stream()),
+                   "vfx_sosfiltfilt")
+        return y[0] if squeeze else y
+
     def resunet_mel(self, mel_linear):
         """Generator.forward: linear mel (B,T,128) -> log10 mel (B,T,128)."""
         mel = _dev_f32(mel_linear, self.device)

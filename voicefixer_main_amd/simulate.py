@@ -150,6 +150,122 @@ def bandpass(data, lowcut, highcut, fs, order=5, _type="butter"):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# batch forms: a whole test set of clips per call, the IIR types on the device (Engine.sosfiltfilt, csrc/sosfilt.hip)
+# ------------------------------------------------------------------------------------------------------------------
+MAX_BATCH = 128     # clips per device call, as in restore_list / evaluation_list
+
+
+def _check_1d(clips):
+    for data in clips:
+        if len(list(data.shape)) != 1:
+            raise ValueError("Error (chebyshev_lowpass_filter): Data " + str(data.shape) +
+                             " should be type 1d time array, (samples,) , can not be (samples, 1)")
+
+
+def _is_f32(clip):
+    return str(clip.dtype).endswith("float32")
+
+
+def _results(ys, to_host):
+    """device tensors -> what the caller asked for"""
+    return [y.cpu().numpy() for y in ys] if to_host else ys
+
+
+def _sosfiltfilt_list(clips, sos, engine, to_host):
+    """scipy.signal.sosfiltfilt(sos, clip) of every clip: sorted by length, padded batches of up to MAX_BATCH clips of one dtype
+    (float32 clips are extended in float32, as SciPy does; every other dtype goes as float64), results in the caller's order."""
+    import torch
+    eng = engine if engine is not None else _get_engine()
+    padlen = eng.sosfiltfilt_padlen(sos)
+    if any(c.shape[0] <= padlen for c in clips):
+        raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+    out = [None] * len(clips)
+    for f32 in (True, False):
+        dtype = torch.float32 if f32 else torch.float64
+        order = sorted((i for i in range(len(clips)) if _is_f32(clips[i]) == f32), key=lambda i: clips[i].shape[0])
+        for k in range(0, len(order), MAX_BATCH):
+            idx = order[k:k + MAX_BATCH]
+            lengths = [clips[i].shape[0] for i in idx]
+            batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=dtype)
+            for j, i in enumerate(idx):
+                c = clips[i]
+                batch[j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(
+                    device=eng.device, dtype=dtype)
+            y = eng.sosfiltfilt(batch, sos, lengths=lengths)
+            if to_host:
+                y = y.cpu().numpy()
+            for j, i in enumerate(idx):
+                out[i] = y[j, :lengths[j]].copy() if to_host else y[j, :lengths[j]]
+    return out
+
+
+def _stft_list(clips, ratio, engine, to_host, fs_ori=44100):
+    """`_type="stft"` for a list: float32 clips whose two rate pairs the device resampler takes go down and up through
+    Engine.resample as padded batches (bit for bit `stft_hard_lowpass`); everything else takes the host function."""
+    import torch
+    from .engine import Engine
+    fs_down = int(ratio * fs_ori)
+    on_device = fs_down > 0 and fs_down != fs_ori and Engine.resample_supported(fs_ori, fs_down) and Engine.resample_supported(fs_down, fs_ori)
+    eng = engine if engine is not None else _get_engine()
+    out = [None] * len(clips)
+    dev = [i for i in range(len(clips)) if on_device and _is_f32(clips[i]) and clips[i].shape[0] > 0]
+    dev.sort(key=lambda i: clips[i].shape[0])
+    for k in range(0, len(dev), MAX_BATCH):
+        idx = dev[k:k + MAX_BATCH]
+        lengths = [clips[i].shape[0] for i in idx]
+        batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=torch.float32)
+        for j, i in enumerate(idx):
+            c = clips[i]
+            batch[j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(eng.device)
+        low, low_lengths = eng.resample(batch, fs_ori, fs_down, lengths=lengths)
+        y, y_lengths = eng.resample(low, fs_down, fs_ori, lengths=low_lengths)
+        for j, i in enumerate(idx):      # align_length: cut, or zero-padded at the end (rows are zero past their length)
+            n = lengths[j]
+            row = y[j, :n] if y.shape[1] >= n else torch.nn.functional.pad(y[j], (0, n - y.shape[1]))
+            out[i] = row.cpu().numpy() if to_host else row
+    for i in range(len(clips)):
+        if out[i] is None:
+            c = clips[i]
+            y = stft_hard_lowpass(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, lowpass_ratio=ratio, fs_ori=fs_ori)
+            out[i] = y if to_host else torch.from_numpy(np.ascontiguousarray(y)).to(eng.device)
+    return out
+
+
+def lowpass_list(clips, highcut, fs, order=5, _type="butter", engine=None, to_host=True):
+    """`lowpass` for a list of 1-D clips of any lengths: the same 1-D check, substring dispatch, int() of the cut-off and order
+    clamp, ONE filter design, and the IIR types as padded batches on the device -- every clip bit for bit what
+    scipy.signal.sosfiltfilt gives for it alone.  -> list in the caller's order: float64 NumPy arrays (to_host), or device tensors
+    that `restore_list` takes as they are."""
+    clips = list(clips)
+    _check_1d(clips)
+    for name in ("butter", "cheby1", "ellip", "bessel"):
+        if _type in name:
+            sos = _design(limit(order, high=10, low=2), int(highcut) / (0.5 * fs), "low", name, "lowpass")
+            return _sosfiltfilt_list(clips, sos, engine, to_host)
+    if _type in "stft":
+        return _stft_list(clips, highcut / int(fs / 2), engine, to_host)
+    if _type in "stft_hard":
+        import torch
+        eng = engine if engine is not None else _get_engine()
+        ys = [stft_hard_lowpass_v0(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, lowpass_ratio=highcut / int(fs / 2),
+                                   engine=eng) for c in clips]
+        return ys if to_host else [torch.from_numpy(y).to(eng.device) for y in ys]
+    raise ValueError("Error: Unexpected filter type " + _type)
+
+
+def bandpass_list(clips, lowcut, highcut, fs, order=5, _type="butter", engine=None, to_host=True):
+    """`bandpass` for a list of 1-D clips, as `lowpass_list` (IIR types only)."""
+    clips = list(clips)
+    _check_1d(clips)
+    for name in ("butter", "cheby1", "ellip", "bessel"):
+        if _type in name:
+            nyq = 0.5 * fs
+            sos = _design(limit(order, high=10, low=2), [int(lowcut) / nyq, int(highcut) / nyq], "band", name, "bandpass")
+            return _sosfiltfilt_list(clips, sos, engine, to_host)
+    raise ValueError("Error: Unexpected filter type " + _type)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # tools/others/audio_op.py:12-56 (peak-based "energy") and dataloaders/augmentation/base.py:33-118
 # ------------------------------------------------------------------------------------------------------------------
 def activelev(*args):
