@@ -155,19 +155,51 @@ def test_poisoned_arena_stays_finite(unet_sd, voc_sd, monkeypatch):
         assert bool(torch.isfinite(y).all())
 
 
-def test_sub_batches_match_single_launch(engine, monkeypatch):
-    """Batches whose activations would pass 4 GiB run as consecutive sub-batches (32-bit offsets in the
-    convolution kernels); forcing that path with VFX_MAX_CLIPS must not change a single bit."""
+@pytest.fixture(scope="module")
+def spec_engines():
+    """One handle per arithmetic mode with the spectrogram ResUNet (the session's `engine` carries the mel ResUNet and the vocoder)."""
     from voicefixer_main_amd import synth
-    wav = torch.from_numpy(synth.make_clips(3, 0.7, seed=51)[:, 0]).cuda()
-    whole = engine.restore_gsr(wav).clone()
+    from voicefixer_main_amd.engine import Engine, MODEL_UNET_SPEC
+    sd = synth.make_resunet_state_dict(2)
+    engines = {}
+
+    def get(precision):
+        if precision not in engines:
+            engines[precision] = Engine("cuda:0", config={"precision": precision})
+            engines[precision].load_state_dict(MODEL_UNET_SPEC, sd)
+        return engines[precision]
+    yield get
+    for eng in engines.values():
+        eng.close()
+
+
+@pytest.mark.parametrize("call", ["restore_gsr", "vocoder", "resunet_mel", "resunet_spec", "restore_ssr_varlen"])
+def test_sub_batches_match_single_launch(engine, spec_engines, monkeypatch, call):
+    """Batches whose activations would pass 4 GiB run as consecutive sub-batches (32-bit offsets in the
+    convolution kernels); forcing that path with VFX_MAX_CLIPS must not change a single bit -- in every entry point that
+    steps by it.  3 clips of 0.5 s (51 frames, one 64-frame pad) run as 2 + 1: the last sub-batch has another batch size,
+    so another plan, than the first."""
+    from voicefixer_main_amd import synth
+    wav = torch.from_numpy(synth.make_clips(3, 0.5, seed=51)[:, 0]).cuda()
+    if call == "restore_gsr":
+        run = lambda: engine.restore_gsr(wav)
+    elif call in ("vocoder", "resunet_mel"):
+        mel = engine.stft(wav)["mel"]
+        run = lambda: getattr(engine, call)(mel)
+    else:
+        eng = spec_engines(engine.precision)
+        if call == "resunet_spec":
+            sp = eng.stft(wav, want_mel=False, want_sp=True)["sp"]
+            run = lambda: eng.resunet_spec(sp, wav)
+        else:
+            lens = [wav.shape[1], wav.shape[1] - 4410, wav.shape[1]]     # 51, 41, 51 frames: one padded frame count
+            run = lambda: eng.restore_ssr_varlen(wav, lens)
+    whole = run().clone()
     monkeypatch.setenv("VFX_MAX_CLIPS", "2")
-    parts = engine.restore_gsr(wav)
-    mel = engine.stft(wav)["mel"]
-    voc_parts = engine.vocoder(mel)
+    parts = run()
     monkeypatch.delenv("VFX_MAX_CLIPS")
+    assert torch.isfinite(whole).all()
     assert torch.equal(parts, whole)
-    assert torch.equal(voc_parts, engine.vocoder(mel))
 
 
 def _sisdr(est, ref):

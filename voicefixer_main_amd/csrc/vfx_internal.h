@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -136,6 +137,16 @@ constexpr int kKC = 32;             // input channels per K step
 constexpr int kIdentityLen = 4096;  // length of the identity scale/shift tables
 constexpr int kPatchMaxRows = 192;
 constexpr int kMaxVarlenClips = 1024;  // clips per launch of a varlen batch (vfx_handle::d_lens)
+// The rows of vfx_handle::d_lens, kMaxVarlenClips ints each: per-clip lengths of the call in flight, written in stream order behind the
+// kernels of the previous call.  launch_set_lens fills three consecutive rows at once (which is why row 5 exists: nobody reads it).
+enum LensRow {
+  LENS_SAMPLES = 0, LENS_FRAMES = 1, LENS_VOC_FRAMES = 2,              // samples / frames / vocoder frames of the varlen batch
+  LENS_GROUP_FRAMES = 3, LENS_GROUP_INDEX = 4,                         // frames / batch index of the clips of its ResUNet group in flight
+  LENS_RUN_SAMPLES = 6, LENS_RUN_FRAMES = 7, LENS_RUN_VOC_FRAMES = 8,  // samples / frames / vocoder frames of its vocoder run in flight
+  LENS_ANALYSIS_FRAMES = 9,                                            // frames per clip of a vfx_analysis_mel call
+  LENS_SCORE_SAMPLES = 10, LENS_SCORE_FRAMES = 11,                     // samples / frames of the vfx_audio_metrics sub-batch in flight
+  kLensRows = 12
+};
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
 
@@ -534,17 +545,39 @@ struct ArenaPlanner {
   void free(size_t off);
 };
 
+// A device buffer of the handle that only grows.  Growing synchronises, frees and re-allocates, so nothing may keep a pointer into
+// it across a call that may grow it -- except the plans a hipGraph was captured from, which is why a buffer they point into refuses.
+struct GrowBuffer {
+  char* p = nullptr;
+  size_t bytes = 0;
+  // -> the buffer, at least `need` bytes; a buffer that has to grow takes need + need / slack_div bytes (0: no slack).  pinned_msg
+  // (format: old size, new size, plan key) or NULL: the error when it has to grow while a plan of `h` is pinned.  h->arena alone also
+  // drops the retired plans and takes the poison fill of VFX_TUNE_DEBUG_POISON_ARENA.
+  char* ensure(vfx_handle* h, size_t need, size_t slack_div, const char* pinned_msg = nullptr);
+  GrowBuffer() = default;
+  ~GrowBuffer() {
+    if (p) (void)hipFree(p);
+  }
+  GrowBuffer(const GrowBuffer&) = delete;
+  GrowBuffer& operator=(const GrowBuffer&) = delete;
+};
+
+// One launch of a profiled call (vfx_profile_*): HIP events around it, its work, and its row of the VFX_PROFILE_DUMP table.
+struct LaunchRecord {
+  hipEvent_t begin, end;
+  double flops;
+  double bytes;         // algorithmic HBM bytes of the launch
+  double design_bytes;  // what the kernel's data layout moves (two-form trunks carry their fp16 copies)
+  char kernel[64];
+  int M, Cout, K, nseg, ntaps0, C0, Wi, sw;
+};
+struct ConvProfile {  // HIP-event timing of every convolution launch
+  bool enabled = false;
+  std::vector<LaunchRecord> launches;
+};
+
 // A buffer is either a slice of the arena (resolved when the plan is bound to an arena base)
 // or one of the caller's tensors (resolved per call).
-struct ConvProfile {  // HIP-event timing of every convolution launch (vfx_profile_*)
-  bool enabled = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  std::vector<double> flops;
-  std::vector<double> bytes;  // algorithmic HBM bytes of the launch
-  std::vector<double> design_bytes;  // what the kernel's data layout moves (two-form trunks carry their fp16 copies)
-  std::vector<int> bn;
-  std::vector<TapConvParams> desc;  // fused ResStack layers are described as M = B*T, Cout = C, nseg = 0
-};
 
 struct RunCtx {
   hipStream_t stream;
@@ -570,7 +603,7 @@ struct Plan {
   std::map<std::string, size_t> named;  // named arena offsets (bytes) of stage-level buffers
   uint64_t last_use = 0;                // handle tick of the last call (LRU eviction, get_plan)
   bool pinned = false;                  // a hipGraph was captured from this plan: its parameter blocks must outlive the graph
-  void run(const RunCtx& ctx);  // api.cpp (debug hooks: VFX_POISON_ARENA=2, VFX_DEBUG_NAN)
+  void run(const RunCtx& ctx);  // plan.cpp (debug hooks: VFX_POISON_ARENA=2, VFX_DEBUG_NAN)
 };
 
 // Arena-relative pointer encoding used inside TapConvParams until bind_plan(): offset + 1
@@ -717,19 +750,13 @@ struct vfx_handle {
   std::map<std::string, std::shared_ptr<vfx::Plan>> plans;  // at most kMaxCachedPlans, least recently used evicted
   std::vector<std::shared_ptr<vfx::Plan>> retired;  // evicted plans whose device blocks are freed in batches (get_plan)
   uint64_t plan_tick = 0;
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
+  vfx::GrowBuffer arena;     // the workspace the plans place their buffers in (bind_plan)
   int* d_flags = nullptr;
-  int* d_lens = nullptr;     // [12][kMaxVarlenClips]: rows 0-2 samples / frames / vocoder frames per clip of the varlen call in flight;
-                             // rows 3-4 frames / batch index of the clips of its ResUNet group in flight (5 unused); rows 6-8 samples /
-                             // frames / vocoder frames of its vocoder run in flight; row 9 frames per clip of a vfx_analysis_mel call;
-                             // rows 10-11 samples / frames per clip of the vfx_audio_metrics sub-batch in flight
-  char* scratch = nullptr;   // the tensors between the plans of a varlen call (api.cpp: ensure_scratch), grow-only
-  size_t scratch_bytes = 0;
-  char* score_ws = nullptr;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more), grow-only
-  size_t score_ws_bytes = 0;
-  char* sos_ws = nullptr;    // vfx_sosfiltfilt's forward pass over the extended clips (float64), grow-only
-  size_t sos_ws_bytes = 0;
+  int* d_lens = nullptr;     // [kLensRows][kMaxVarlenClips]
+  int* lens_row(vfx::LensRow r) const { return d_lens + r * vfx::kMaxVarlenClips; }
+  vfx::GrowBuffer scratch;   // the tensors between the plans of a varlen call (vfx_restore_gsr_varlen)
+  vfx::GrowBuffer score_ws;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more)
+  vfx::GrowBuffer sos_ws;    // vfx_sosfiltfilt's forward pass over the extended clips (float64)
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;
@@ -739,6 +766,12 @@ namespace vfx {
 void init_front_end(vfx_handle* h);
 void set_mel_filterbank(vfx_handle* h, const float* fb /*1025x128*/);
 void bind_plan(vfx_handle* h, Plan& plan);  // ensures the arena is large enough and rebases the plan on it
+std::string key_of(const char* tag, int B, int T, int x = 0);  // key of a cached plan (vfx_handle::plans)
+// What a model-stage entry point does with a plan: take it from the handle's cache (building and binding it as needed: `build`),
+// poison its arena bytes on a VFX_TUNE_DEBUG_POISON_ARENA handle, then -- behind `before`, if given: launches of the call that write
+// the plan's named buffers -- run it on `stream` with the caller's tensors `ext` (RunCtx::ext).  Returns the plan (Plan::named).
+std::shared_ptr<Plan> run_plan(vfx_handle* h, const std::string& key, void* stream, std::initializer_list<const float*> ext,
+                               const std::function<void(PlanBuilder&)>& build, const std::function<void(Plan&)>& before = nullptr);
 std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model);
 std::shared_ptr<VocoderWeights> build_vocoder_weights(vfx_handle* h);
 std::shared_ptr<AnalysisWeights> build_analysis_weights(vfx_handle* h, int model);
