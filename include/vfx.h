@@ -277,6 +277,26 @@ int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx,
                     const double* zi, int padlen, double* y, int64_t ldy, void* stream);
 
 /*
+ * Reverberation of a padded batch of clips: MagicalEffects.reverb_rir (dataloaders/augmentation/magical_effects.py:158-167) per clip,
+ * the degradation of the `vctk_reverb` test set -- the full convolution of the clip with a room impulse response, the whole result
+ * scaled to a peak of 0.98 when its peak exceeds 0.99, cut back to the clip's length.
+ *   x (B, ldx) device float32, clip b = the first lengths[b] samples of row b (HOST int64[B], each >= 1);
+ *   rirs (R, ldr) device float32, RIR r = the first rir_lengths[r] taps of row r (HOST int64[R], 1 <= taps <= 2^20);
+ *   rir_index HOST int[B]: clip b is convolved with RIR rir_index[b] (NULL: b % R).  A RIR longer than its clip and a one-tap RIR are fine;
+ *   y (B, ldy) device float32, ldy >= max(lengths): row b receives lengths[b] samples, and zeros from there up to ldy;
+ *   peaks (B) device float32: max |sample| over all lengths[b] + taps - 1 samples of the convolution, tail included, before the
+ *   scaling (NaN when a sample is); may be NULL only when normalize is 0.
+ * The convolution is in direct form: per output, taps are summed in blocks of 1024 by a float32 fma chain from zero, the block sums
+ * are added in float64 in ascending order and rounded to float32 once, so |y - exact| <= (min(taps, 1024) + 2) 2^-24 sum |x||h| + 2^-149
+ * per sample, and a clip's result does not depend on the batch it is in.  normalize != 0: a row with (double)peak > 0.99 becomes
+ * (y / peak) * 0.98f, a correctly rounded float32 division and a float32 multiplication -- NumPy's arithmetic on a float32 array; a
+ * NaN peak leaves the row as it is.  Fails, launching nothing, for an empty clip or RIR, a RIR above 2^20 taps, an index outside
+ * [0, R), or ldy < max(lengths).
+ */
+int vfx_reverb_rir(vfx_handle* h, const float* x, int B, int64_t ldx, const int64_t* lengths, const float* rirs, int R, int64_t ldr,
+                   const int64_t* rir_lengths, const int* rir_index, int normalize, float* y, int64_t ldy, float* peaks, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

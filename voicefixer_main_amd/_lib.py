@@ -57,6 +57,8 @@ SIGNATURES = {
                              c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "vfx_sosfiltfilt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(ctypes.c_double), c_int,
                                 POINTER(ctypes.c_double), c_int, c_void_p, c_int64, c_void_p]),
+    "vfx_reverb_rir": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_void_p, c_int, c_int64, POINTER(c_int64),
+                               POINTER(c_int), c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

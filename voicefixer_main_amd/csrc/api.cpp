@@ -448,6 +448,34 @@ int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx,
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// room-impulse-response convolution (MagicalEffects.reverb_rir on the device: reverb.hip)
+// ---------------------------------------------------------------------------------------------
+int vfx_reverb_rir(vfx_handle* h, const float* x, int B, int64_t ldx, const int64_t* lengths, const float* rirs, int R, int64_t ldr,
+                   const int64_t* rir_lengths, const int* rir_index, int normalize, float* y, int64_t ldy, float* peaks, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && rirs && rir_lengths && y && B > 0 && R > 0, "vfx_reverb_rir: bad argument");
+  VFX_CHECK(peaks || !normalize, "vfx_reverb_rir: peaks may be NULL only when normalize is 0");
+  for (int r = 0; r < R; ++r) {
+    VFX_CHECK(rir_lengths[r] >= 1, "vfx_reverb_rir: RIR %d is empty (%lld taps)", r, (long long)rir_lengths[r]);
+    VFX_CHECK(rir_lengths[r] <= kReverbMaxTaps, "vfx_reverb_rir: RIR %d has %lld taps, at most %d are taken", r, (long long)rir_lengths[r],
+              kReverbMaxTaps);
+    VFX_CHECK(rir_lengths[r] <= ldr, "vfx_reverb_rir: RIR %d has %lld taps, the rows hold %lld", r, (long long)rir_lengths[r], (long long)ldr);
+  }
+  int64_t lmax = 0;
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] >= 1, "vfx_reverb_rir: clip %d is empty (%lld samples)", b, (long long)lengths[b]);
+    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= 0x7fffffff - kReverbMaxTaps - 2 * kReverbTile,
+              "vfx_reverb_rir: clip %d has %lld samples, the rows of x hold %lld", b, (long long)lengths[b], (long long)ldx);
+    VFX_CHECK(!rir_index || (rir_index[b] >= 0 && rir_index[b] < R), "vfx_reverb_rir: clip %d asks for RIR %d of %d", b,
+              rir_index ? rir_index[b] : 0, R);
+    lmax = std::max(lmax, lengths[b]);
+  }
+  VFX_CHECK(ldy >= lmax, "vfx_reverb_rir: ldy = %lld is too small for a clip of %lld samples", (long long)ldy, (long long)lmax);
+  launch_reverb_rir(x, B, ldx, lengths, rirs, ldr, rir_lengths, rir_index, R, normalize, y, ldy, peaks, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

@@ -518,6 +518,21 @@ void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int6
                         int padlen, double* f, int64_t ldf, double* y, int64_t ldy, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// room-impulse-response convolution (reverb.hip): direct form on the f32-input MFMA
+// ---------------------------------------------------------------------------------------------
+constexpr int kReverbTile = 8192;       // outputs per workgroup: 4 waves x 2 accumulators of 32 x 32
+constexpr int kReverbTapBlock = 1024;   // taps per f32 fma chain; the block sums are combined in float64
+constexpr int kReverbMaxTaps = 1 << 20; // longest RIR the entry point takes
+constexpr int kReverbMaxClips = 128;    // clips per launch: their lengths are kernel arguments
+// x, rirs, y, peaks: device; lengths (B), rir_lengths (R), rir_index (B, or NULL = b % R): HOST.  The caller has checked
+// 1 <= lengths[b] <= min(ldx, ldy), 1 <= rir_lengths[r] <= min(ldr, kReverbMaxTaps) and the indices.  Row b of y receives the first
+// lengths[b] samples of clip b * rir, zeros up to ldy; peaks[b] (NULL: not wanted, normalize = 0 only) the largest |sample| of the whole
+// convolution; normalize: rows whose peak exceeds 0.99 are scaled to a peak of 0.98.
+void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* lengths, const float* rirs, int64_t ldr,
+                       const int64_t* rir_lengths, const int* rir_index, int R, int normalize, float* y, int64_t ldy, float* peaks,
+                       hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {

@@ -14,7 +14,9 @@ same names, argument meaning and error behaviour:
 * ``bandpass_filter`` / ``align_length`` / ``limit``                       tools/dsp/lowpass.py:35-94,148-150
 * ``add_noise_and_scale`` / ``add_noise_and_scale_with_HQ`` / ``add_noise_and_scale_with_HQ_with_Aug``
                                                                            dataloaders/augmentation/base.py:33-118
-  with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56).
+  with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56);
+* ``reverb_rir(frames, rir)``                              dataloaders/augmentation/magical_effects.py:158-167
+  (the `vctk_reverb` test set: convolution with a room impulse response; ``reverb_rir_list`` is its batch form on the device).
 
 Everything is NumPy / SciPy on the host EXCEPT ``stft_hard``: its STFT -> mask -> ISTFT round trip is the hot path's own
 front-end and back-end (``vfx_stft_mel`` in its phase-emitting form and ``vfx_istft``), so it runs on the GPU through an
@@ -263,6 +265,77 @@ def bandpass_list(clips, lowcut, highcut, fs, order=5, _type="butter", engine=No
             sos = _design(limit(order, high=10, low=2), [int(lowcut) / nyq, int(highcut) / nyq], "band", name, "bandpass")
             return _sosfiltfilt_list(clips, sos, engine, to_host)
     raise ValueError("Error: Unexpected filter type " + _type)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# dataloaders/augmentation/magical_effects.py:158-167
+# ------------------------------------------------------------------------------------------------------------------
+def reverb_rir(frames, rir):
+    """MagicalEffects.reverb_rir: both inputs squeezed, convolved over the full length, the whole result scaled to a peak of 0.98
+    when its peak exceeds 0.99, cut to the first frames.shape[0] samples."""
+    from scipy.signal import convolve
+    orig_frames_shape = frames.shape
+    frames, filt = np.squeeze(frames), np.squeeze(rir)
+    frames = convolve(frames, filt)
+    actlev = np.max(np.abs(frames))
+    if actlev > 0.99:
+        frames = (frames / actlev) * 0.98
+    return frames[:orig_frames_shape[0]]
+
+
+def reverb_rir_list(clips, rirs, rir_index=None, engine=None, to_host=True):
+    """`reverb_rir` for a list of clips and a list of RIRs (or one RIR): clip i takes RIR rir_index[i] (default i % len(rirs)).
+    float32 clips with float32 RIRs are sorted by length and go through Engine.reverb_rir as padded batches of up to MAX_BATCH --
+    direct-form convolution, each clip bit for bit what its own device call gives; every other dtype takes the host function.
+    -> list in the caller's order: NumPy arrays (to_host), or device tensors that `restore_list` takes as they are."""
+    import torch
+    clips = list(clips)
+    rirs = [rirs] if isinstance(rirs, (np.ndarray, torch.Tensor)) else list(rirs)
+    if not rirs:
+        raise ValueError("reverb_rir_list: no RIR")
+    rir_index = [i % len(rirs) for i in range(len(clips))] if rir_index is None else [int(v) for v in rir_index]
+    if len(rir_index) != len(clips) or any(not 0 <= r < len(rirs) for r in rir_index):
+        raise ValueError("reverb_rir_list: %d indices for %d clips, each must be in [0, %d)" % (len(rir_index), len(clips), len(rirs)))
+    eng = engine if engine is not None else _get_engine()
+
+    def host(a):
+        return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    def flat(a):     # the 1-D device form of a clip or RIR that np.squeeze makes 1-D and non-empty, or None
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        t = t.squeeze()
+        return t if t.dim() == 1 and t.numel() > 0 else None
+
+    out = [None] * len(clips)
+    def on_device(clip, rir):      # (a clip that squeezes to another length than shape[0] is cut differently: host)
+        c, r = flat(clip), flat(rir)
+        return (_is_f32(clip) and _is_f32(rir) and c is not None and r is not None and c.numel() == clip.shape[0]
+                and r.numel() <= eng.MAX_RIR_TAPS)
+
+    dev = [i for i in range(len(clips)) if on_device(clips[i], rirs[rir_index[i]])]
+    dev.sort(key=lambda i: clips[i].shape[0])
+    for k in range(0, len(dev), MAX_BATCH):
+        idx = dev[k:k + MAX_BATCH]
+        lengths = [clips[i].shape[0] for i in idx]
+        used = sorted({rir_index[i] for i in idx})
+        taps = [flat(rirs[r]) for r in used]
+        bank = torch.zeros((len(used), max(t.numel() for t in taps)), device=eng.device, dtype=torch.float32)
+        for j, t in enumerate(taps):
+            bank[j, :t.numel()] = t.to(eng.device)
+        batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=torch.float32)
+        for j, i in enumerate(idx):
+            batch[j, :lengths[j]] = flat(clips[i]).to(eng.device)
+        y, _ = eng.reverb_rir(batch, bank, rir_index=[used.index(rir_index[i]) for i in idx], lengths=lengths,
+                              rir_lengths=[t.numel() for t in taps])
+        if to_host:
+            y = y.cpu().numpy()
+        for j, i in enumerate(idx):
+            out[i] = y[j, :lengths[j]].copy() if to_host else y[j, :lengths[j]]
+    for i in range(len(clips)):
+        if out[i] is None:
+            y = reverb_rir(host(clips[i]), host(rirs[rir_index[i]]))
+            out[i] = y if to_host else torch.from_numpy(np.ascontiguousarray(y)).to(eng.device)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------

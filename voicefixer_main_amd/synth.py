@@ -11,7 +11,8 @@ on seeded synthetic data of the reference's shapes:
 * speech-like 44.1 kHz clips: harmonic source (f0 random walk, 30 harmonics, 1/k
   roll-off) x syllabic envelope + noise bursts, degraded like the reference's
   simulator (additive noise SNR~U[-5,40] dB, optional cheby1 low-pass
-  tools/dsp/lowpass.py:96-133, optional hard clipping).
+  tools/dsp/lowpass.py:96-133, optional hard clipping);
+* room impulse responses (``make_rir``): a direct-path spike plus exponentially decaying noise.
 """
 from collections import OrderedDict
 
@@ -218,6 +219,18 @@ def make_clips(n_clips, seconds, seed=1234, mode="noise", distinct=8, sr=SAMPLE_
     for i in range(n_clips):
         out[i, 0] = degrade(bases[i % len(bases)], seed + i, mode, sr)
     return out
+
+
+def make_rir(seed, n_taps, sr=SAMPLE_RATE):
+    """float32 (n_taps,) synthetic room impulse response: a direct-path spike of 1 at tap 0 plus Gaussian noise under an
+    exponential envelope (-60 dB at a seeded RT60 of 0.3 .. 1.0 s) that starts after a short pre-delay."""
+    rng = np.random.default_rng(seed)
+    rt60 = rng.uniform(0.3, 1.0)
+    t = np.arange(n_taps) / sr
+    h = rng.normal(0, 1.0, n_taps) * np.exp(-6.907755278982137 * t / rt60) * 0.05
+    h[:min(n_taps, int(0.002 * sr))] = 0.0
+    h[0] = 1.0
+    return h.astype(np.float32)
 
 
 # ----------------------------------------------------------------------------
