@@ -297,6 +297,33 @@ int vfx_reverb_rir(vfx_handle* h, const float* x, int B, int64_t ldx, const int6
                    const int64_t* rir_lengths, const int* rir_index, int normalize, float* y, int64_t ldy, float* peaks, void* stream);
 
 /*
+ * Noise mixed into a padded batch of clips at a given SNR weight and scale: add_noise_and_scale (form 0), add_noise_and_scale_with_HQ
+ * (form 1) and add_noise_and_scale_with_HQ_with_Aug (form 2) of dataloaders/augmentation/base.py:33-118 per clip, the degradation of
+ * the noisy test sets and the per-item loop of the training pre-processing.
+ *   front, noise, hq, aug (B, ld) device float32, clip b = the first lengths[b] samples of row b of each (HOST int64[B], each >= 1;
+ *   what a row holds past them is never read); hq is NULL in form 0, aug is NULL in forms 0 and 1, and they are required otherwise;
+ *   noise_weight HOST double[B] = 10 ** (snr / 20) per clip, or NULL: the SNR step is skipped (the reference's snr_l is None);
+ *   scale HOST double[B]: the common scale of the clip;
+ *   front_out, noise_out, hq_out, aug_out, noisy (B, ld) device float32, each may be NULL when not wanted: row b receives lengths[b]
+ *   samples and zeros from there up to ld.  noisy = noise_out + speech_out, the speech being front (forms 0, 1) or aug (form 2).
+ * Per clip, in the reference's order: (1) p_x = max |x| of every input; (2) noise / p_noise, and front / p_front (form 0) or hq, front,
+ * aug times float(1.0 / max of their peaks) (forms 1, 2); (3) forms 1, 2: level = mean |speech|, and if level > 0.02 the noise is divided
+ * by float(mean |noise| / level); (4) noise / float(noise_weight[b]); (5) every returned signal times float(1.0 / peak), peak = max |.|
+ * over noise + speech and the returned signals; (6) times float(scale[b]); (7) noisy.
+ * Arithmetic: every elementwise step is ONE IEEE float32 operation per sample (a correctly rounded division, division, addition,
+ * multiplication, multiplication; never an FMA), and every per-clip scalar is computed in double and rounded to float32 once -- NumPy's
+ * arithmetic on a float32 array with a Python-float operand -- so form 0 equals the host function bit for bit.  The two means of step 3
+ * are float64 sums over chunks of 4096 samples combined in index order (NumPy sums them pairwise in float32: forms 1 and 2 agree to
+ * rounding, not bit for bit).  "max" over several peaks is Python's max() in the reference's argument order, and a NaN sample makes
+ * its signal's peak NaN, as np.max does.  A clip's result depends on the clip alone: not on the batch, the row stride or the alignment.
+ * Fails, launching nothing, for a form outside 0..2, a pointer the form requires and lacks (or takes and is given), an empty clip, a
+ * length above ld, or B above 1024.  Per-clip partial results live in a scratch buffer of the handle, grown on demand.
+ */
+int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* lengths, const float* front, const float* noise,
+                  const float* hq, const float* aug, const double* noise_weight, const double* scale, float* front_out, float* noise_out,
+                  float* hq_out, float* aug_out, float* noisy, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

@@ -59,6 +59,9 @@ SIGNATURES = {
                                 POINTER(ctypes.c_double), c_int, c_void_p, c_int64, c_void_p]),
     "vfx_reverb_rir": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_void_p, c_int, c_int64, POINTER(c_int64),
                                POINTER(c_int), c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "vfx_mix_noise": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p,
+                              POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -476,6 +476,34 @@ int vfx_reverb_rir(vfx_handle* h, const float* x, int B, int64_t ldx, const int6
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// noise mixing (add_noise_and_scale, _with_HQ, _with_HQ_with_Aug on the device: mix.hip)
+// ---------------------------------------------------------------------------------------------
+int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* lengths, const float* front, const float* noise,
+                  const float* hq, const float* aug, const double* noise_weight, const double* scale, float* front_out, float* noise_out,
+                  float* hq_out, float* aug_out, float* noisy, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(form >= 0 && form <= 2, "vfx_mix_noise: form %d (0 = plain, 1 = with HQ, 2 = with HQ and Aug)", form);
+  VFX_CHECK(front && noise && lengths && scale && B > 0, "vfx_mix_noise: bad argument");
+  VFX_CHECK(B <= kMaxVarlenClips, "vfx_mix_noise: %d clips, at most %d per call", B, kMaxVarlenClips);
+  VFX_CHECK((form >= 1) == (hq != nullptr), "vfx_mix_noise: form %d %s hq", form, form >= 1 ? "needs" : "takes no");
+  VFX_CHECK((form == 2) == (aug != nullptr), "vfx_mix_noise: form %d %s aug (aug goes with hq: form 2)", form, form == 2 ? "needs" : "takes no");
+  VFX_CHECK((hq || !hq_out) && (aug || !aug_out), "vfx_mix_noise: form %d returns no %s", form, hq_out && !hq ? "hq" : "aug");
+  VFX_CHECK(front_out || noise_out || hq_out || aug_out || noisy, "vfx_mix_noise: no output asked for");
+  int64_t lmax = 0;
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] >= 1, "vfx_mix_noise: clip %d is empty (%lld samples)", b, (long long)lengths[b]);
+    VFX_CHECK(lengths[b] <= ld && lengths[b] <= 0x7fffffff - 2 * kMixChunk, "vfx_mix_noise: clip %d has %lld samples, the rows hold %lld", b,
+              (long long)lengths[b], (long long)ld);
+    lmax = std::max(lmax, lengths[b]);
+  }
+  char* const ws = h->mix_ws.ensure(h, mix_workspace_bytes(B, lmax), 0);
+  const float* const in[4] = {front, noise, hq, aug};
+  float* const out[5] = {front_out, noise_out, hq_out, aug_out, noisy};
+  launch_mix_noise(form, B, ld, lengths, in, noise_weight, scale, out, ws, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

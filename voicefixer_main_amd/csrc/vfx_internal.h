@@ -533,6 +533,18 @@ void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* length
                        hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// noise mixing (mix.hip): add_noise_and_scale and its with_HQ / with_HQ_with_Aug forms
+// ---------------------------------------------------------------------------------------------
+constexpr int kMixChunk = 4096;     // samples of a clip per workgroup; the float64 level sums are per chunk, combined in index order
+constexpr int kMixMaxClips = 128;   // clips per launch: their lengths, weights and scales are kernel arguments
+constexpr int kMixPeaks = 8;        // peak slots per clip: front, noise, hq, aug, the mixture (+ padding)
+size_t mix_workspace_bytes(int B, int64_t lmax);  // of `ws` below, for B clips of at most lmax samples
+// in (front, noise, hq, aug), out (front, noise, hq, aug, noisy): device (B, ld) or NULL; lengths, noise_weight (or NULL), scale: HOST (B).
+// The caller has checked the form's pointers and 1 <= lengths[b] <= ld.  Rows of every given output are zero from lengths[b] up to ld.
+void launch_mix_noise(int form, int B, int64_t ld, const int64_t* lengths, const float* const in[4], const double* noise_weight,
+                      const double* scale, float* const out[5], char* ws, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {
@@ -772,6 +784,7 @@ struct vfx_handle {
   vfx::GrowBuffer scratch;   // the tensors between the plans of a varlen call (vfx_restore_gsr_varlen)
   vfx::GrowBuffer score_ws;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more)
   vfx::GrowBuffer sos_ws;    // vfx_sosfiltfilt's forward pass over the extended clips (float64)
+  vfx::GrowBuffer mix_ws;    // vfx_mix_noise's per-clip peaks, level ratios and chunk sums
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;

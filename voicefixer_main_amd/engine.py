@@ -436,6 +436,49 @@ class Engine:
                                            _ptr(y), L, _ptr(peaks), self._stream()), "vfx_reverb_rir")
         return (y[0], peaks[0]) if squeeze else (y, peaks)
 
+    # ------------------------------------------------------------------ noise mixing (add_noise_and_scale and its HQ / Aug forms)
+    def mix_noise(self, front, noise, hq=None, aug=None, lengths=None, noise_weight=None, scale=None, want_noisy=False):
+        """add_noise_and_scale (front, noise), add_noise_and_scale_with_HQ (+ hq) or add_noise_and_scale_with_HQ_with_Aug (+ hq, aug)
+        of float32 clips on the device: every signal (B, L) or (L,), clip b = the first lengths[b] samples (default L) of row b of
+        each; what the rows hold past them is not read.  noise_weight: 10 ** (snr / 20) per clip (a number: the same for every clip),
+        None skips the SNR step; scale: the common scale per clip (default 1).  -> dict of device tensors shaped like `front`:
+        "front", "noise", "hq" and "aug" where given, and "noisy" = noise + speech (front, or aug when given) when asked for; rows
+        are zero past their length.  One float32 operation per sample and step, in the host functions' order: the plain form equals
+        simulate.add_noise_and_scale bit for bit, and a clip's result does not depend on the batch."""
+        sig = {"front": front, "noise": noise, "hq": hq, "aug": aug}
+        sig = {k: _dev_f32(v, self.device) for k, v in sig.items() if v is not None}
+        front = sig["front"]
+        squeeze = front.dim() == 1
+        if any(v.shape != front.shape for v in sig.values()) or front.dim() not in (1, 2):
+            raise ValueError("mix_noise: every signal must be (B, L) or (L,) of one shape, got %s"
+                             % ", ".join("%s %s" % (k, tuple(v.shape)) for k, v in sig.items()))
+        if squeeze:
+            sig = {k: v[None] for k, v in sig.items()}
+        B, L = sig["front"].shape
+        if B == 0:
+            raise ValueError("mix_noise: no clips")
+        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+
+        def per_clip(v, default):
+            v = default if v is None else v
+            return [float(v)] * B if np.ndim(v) == 0 else [float(u) for u in v]
+
+        scale = per_clip(scale, 1.0)
+        weight = None if noise_weight is None else per_clip(noise_weight, None)
+        if len(lengths) != B or len(scale) != B or (weight is not None and len(weight) != B):
+            raise ValueError("mix_noise: %d lengths, %d scales and %s weights for %d clips"
+                             % (len(lengths), len(scale), "no" if weight is None else len(weight), B))
+        form = 2 if "aug" in sig else (1 if "hq" in sig else 0)      # (aug without hq: the library says so)
+        out = {k: torch.empty((B, L), device=self.device, dtype=torch.float32) for k in sig}
+        if want_noisy:
+            out["noisy"] = torch.empty((B, L), device=self.device, dtype=torch.float32)
+        dbl = ctypes.c_double * B
+        _lib.check(self.lib.vfx_mix_noise(self.h, form, B, L, (ctypes.c_int64 * B)(*lengths), _ptr(sig["front"]), _ptr(sig["noise"]),
+                                          _ptr(sig.get("hq")), _ptr(sig.get("aug")), dbl(*weight) if weight is not None else None,
+                                          dbl(*scale), _ptr(out["front"]), _ptr(out["noise"]), _ptr(out.get("hq")),
+                                          _ptr(out.get("aug")), _ptr(out.get("noisy")), self._stream()), "vfx_mix_noise")
+        return {k: v[0] for k, v in out.items()} if squeeze else out
+
     def resunet_mel(self, mel_linear):
         """Generator.forward: linear mel (B,T,128) -> log10 mel (B,T,128)."""
         mel = _dev_f32(mel_linear, self.device)

@@ -14,7 +14,8 @@ same names, argument meaning and error behaviour:
 * ``bandpass_filter`` / ``align_length`` / ``limit``                       tools/dsp/lowpass.py:35-94,148-150
 * ``add_noise_and_scale`` / ``add_noise_and_scale_with_HQ`` / ``add_noise_and_scale_with_HQ_with_Aug``
                                                                            dataloaders/augmentation/base.py:33-118
-  with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56);
+  with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56); their ``..._list``
+  forms mix whole lists of float32 clips on the device (Engine.mix_noise, csrc/mix.hip), ``hard_clip_list`` clips a list;
 * ``reverb_rir(frames, rir)``                              dataloaders/augmentation/magical_effects.py:158-167
   (the `vctk_reverb` test set: convolution with a room impulse response; ``reverb_rir_list`` is its batch form on the device).
 
@@ -424,3 +425,125 @@ def add_noise_and_scale_with_HQ_with_Aug(HQ, front, augfront, noise, snr_l=-5, s
 def hard_clip(x, threshold):
     """The declipping test sets' degradation: samples limited to +-threshold (config/vctk_base_voicefixer_unet.json:80-100)."""
     return np.clip(x, -threshold, threshold)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# batch forms of the noise mixers (Engine.mix_noise, csrc/mix.hip) and of hard_clip
+# ------------------------------------------------------------------------------------------------------------------
+_MIX_FORMS = (     # the host function and its signals in argument order (= the order it returns them in)
+    (add_noise_and_scale, ("front", "noise")),
+    (add_noise_and_scale_with_HQ, ("hq", "front", "noise")),
+    (add_noise_and_scale_with_HQ_with_Aug, ("hq", "front", "aug", "noise")),
+)
+
+
+def _mix_list(form, signals, snr_l, snr_h, scale_lower, scale_upper, rng, engine, to_host, want_noisy):
+    """signals: one list of 1-D clips per argument of the host function.  -> the host function's tuple per item (+ noisy)"""
+    import torch
+    host_fn, names = _MIX_FORMS[form]
+    signals = [list(s) for s in signals]
+    n = len(signals[0])
+    if any(len(s) != n for s in signals):
+        raise ValueError("%s_list: lists of %s clips" % (host_fn.__name__, ", ".join(str(len(s)) for s in signals)))
+    for i in range(n):
+        item = [s[i] for s in signals]
+        if any(len(list(c.shape)) != 1 for c in item):
+            raise ValueError("%s_list: item %d: clips must be 1-d time arrays, (samples,), got %s"
+                             % (host_fn.__name__, i, ", ".join(str(tuple(c.shape)) for c in item)))
+        if any(c.shape[0] != item[0].shape[0] for c in item):
+            raise ValueError("%s_list: item %d: the signals of one item must have one length, got %s"
+                             % (host_fn.__name__, i, ", ".join(str(c.shape[0]) for c in item)))
+    rng = rng if rng is not None else np.random.default_rng()
+    speech = "aug" if form == 2 else "front"
+    eng = engine
+
+    def device():      # the Engine only when something needs the device
+        nonlocal eng
+        if eng is None:
+            eng = _get_engine()
+        return eng
+
+    out = [None] * n
+    draws = {}
+    for i in range(n):      # in list order: the device items' draws, the host items' calls (which draw for themselves)
+        item = [s[i] for s in signals]
+        if all(_is_f32(c) for c in item) and item[0].shape[0] > 0:
+            snr = _uniform(snr_l, snr_h, rng) if snr_l is not None and snr_h is not None else None
+            draws[i] = (snr, _uniform(scale_lower, scale_upper, rng))
+            continue
+        res = host_fn(*[c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c) for c in item], snr_l=snr_l, snr_h=snr_h,
+                      scale_lower=scale_lower, scale_upper=scale_upper, rng=rng)
+        ys = list(res[:len(names)])
+        if want_noisy:
+            ys.append(ys[names.index("noise")] + ys[names.index(speech)])
+        if not to_host:
+            ys = [torch.from_numpy(np.ascontiguousarray(y)).to(device().device) for y in ys]
+        out[i] = tuple(ys[:len(names)]) + tuple(res[len(names):]) + tuple(ys[len(names):])
+    dev = sorted(draws, key=lambda i: signals[0][i].shape[0])
+    for k in range(0, len(dev), MAX_BATCH):
+        idx = dev[k:k + MAX_BATCH]
+        lengths = [signals[0][i].shape[0] for i in idx]
+        ld = (lengths[-1] + 3) // 4 * 4      # rows 16-byte aligned: the kernels' wide loads and stores
+        batch = {}
+        for name, s in zip(names, signals):
+            batch[name] = torch.zeros((len(idx), ld), device=device().device, dtype=torch.float32)
+            for j, i in enumerate(idx):
+                c = s[i]
+                batch[name][j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(
+                    device().device)
+        snrs = [draws[i][0] for i in idx]
+        y = device().mix_noise(batch["front"], batch["noise"], hq=batch.get("hq"), aug=batch.get("aug"), lengths=lengths,
+                               noise_weight=None if snrs[0] is None else [10 ** (float(v) / 20) for v in snrs],
+                               scale=[draws[i][1] for i in idx], want_noisy=want_noisy)
+        if to_host:
+            y = {name: v.cpu().numpy() for name, v in y.items()}
+        for j, i in enumerate(idx):
+            rows = [y[name][j, :lengths[j]] for name in names + (("noisy",) if want_noisy else ())]
+            if to_host:
+                rows = [r.copy() for r in rows]
+            out[i] = tuple(rows[:len(names)]) + draws[i] + tuple(rows[len(names):])
+    return out
+
+
+def add_noise_and_scale_list(front, noise, snr_l=-5, snr_h=35, scale_lower=0.6, scale_upper=1.0, rng=None, engine=None, to_host=True,
+                             want_noisy=False):
+    """`add_noise_and_scale` for lists of 1-D clips (item i = front[i], noise[i], of one length): `snr` then `scale` are drawn per
+    item, in list order, from the one `rng` -- a seeded call consumes the generator as a loop over the single-clip function does.
+    Items whose clips are all float32 (NumPy or device tensors) are sorted by length and go through Engine.mix_noise as padded
+    batches of up to MAX_BATCH, bit for bit the host function; every other dtype takes the host function.
+    -> one tuple per item, (front, noise, snr, scale[, noisy]); snr is None when snr_l or snr_h is; the signals are NumPy arrays
+    (to_host), or device tensors that `restore_list` takes as they are.  noisy = front + noise, the model's input."""
+    return _mix_list(0, (front, noise), snr_l, snr_h, scale_lower, scale_upper, rng, engine, to_host, want_noisy)
+
+
+def add_noise_and_scale_with_HQ_list(HQ, front, noise, snr_l=-5, snr_h=35, scale_lower=0.6, scale_upper=1.0, rng=None, engine=None,
+                                     to_host=True, want_noisy=False):
+    """`add_noise_and_scale_with_HQ` for lists, as `add_noise_and_scale_list` -> (HQ, front, noise, snr, scale[, noisy]) per item.
+    The device's level rule sums in float64 where NumPy sums float32 pairwise: float32 items agree with the host function to
+    rounding (16 * 2^-24 relative, tests/test_gpu_mix_noise.py), not bit for bit."""
+    return _mix_list(1, (HQ, front, noise), snr_l, snr_h, scale_lower, scale_upper, rng, engine, to_host, want_noisy)
+
+
+def add_noise_and_scale_with_HQ_with_Aug_list(HQ, front, augfront, noise, snr_l=-5, snr_h=35, scale_lower=0.6, scale_upper=1.0, rng=None,
+                                              engine=None, to_host=True, want_noisy=False):
+    """`add_noise_and_scale_with_HQ_with_Aug` for lists -> (HQ, front, augfront, noise, snr, scale[, noisy]) per item, noisy =
+    augfront + noise; otherwise as `add_noise_and_scale_with_HQ_list`."""
+    return _mix_list(2, (HQ, front, augfront, noise), snr_l, snr_h, scale_lower, scale_upper, rng, engine, to_host, want_noisy)
+
+
+def hard_clip_list(clips, threshold, engine=None, to_host=True):
+    """`hard_clip` for a list of clips: float32 clips (NumPy or device tensors) through torch.clamp where they are, bit for bit
+    np.clip; every other dtype takes the host function.  -> NumPy arrays (to_host), or tensors on the engine's device."""
+    import torch
+    out = []
+    for c in clips:
+        if _is_f32(c):
+            y = torch.clamp(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c)), -threshold, threshold)
+        else:
+            y = hard_clip(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, threshold)
+        if to_host:
+            out.append(y.cpu().numpy() if isinstance(y, torch.Tensor) else y)
+        else:
+            eng = engine if engine is not None else _get_engine()
+            out.append((y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y))).to(eng.device))
+    return out
