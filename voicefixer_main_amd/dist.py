@@ -13,6 +13,8 @@ import time
 import torch
 import torch.distributed as dist
 
+from . import clips as _clips
+
 
 def world_rank():
     """(world, rank); a process that never initialised torch.distributed is a world of one."""
@@ -241,9 +243,7 @@ def restore_sharded_lengths(engine_fn, clips, device, src=0, max_batch=128, dtyp
                     out = engine_fn(torch.stack([pieces[i] for i in chunk]))
                 else:
                     blen = getattr(engine_fn, "bucket_len", None)
-                    x = torch.zeros((len(chunk), blen(max(lens)) if blen else max(lens)), device=device, dtype=dtype)
-                    for j, i in enumerate(chunk):
-                        x[j, :lengths[i]] = pieces[i]
+                    x = _clips.pad([pieces[i] for i in chunk], device, dtype, width=blen(max(lens)) if blen else None)
                     out = engine_fn(x, lens)
                 for j, i in enumerate(chunk):
                     done[i] = out[j, :lengths[i]]

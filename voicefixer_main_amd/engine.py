@@ -28,6 +28,28 @@ def _dev_f32(t, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _host(a):
+    """A host float32 C-contiguous array (None stays None): what the op_* entry points take their weights as."""
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def _hptr(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _clip_rows(x, lengths, name=None, what="lengths"):
+    """The argument handling every clip-batch method shares: x (B, L) or (L,) and each row's length (default L)
+    -> (x as (B, L), whether x was 1-D, B, L, lengths as a list of ints).  With `name`, a list of another size than B raises."""
+    squeeze = x.dim() == 1
+    if squeeze:
+        x = x[None]
+    B, L = x.shape
+    lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+    if name is not None and len(lengths) != B:
+        raise ValueError("%s: %d %s for %d clips" % (name, len(lengths), what, B))
+    return x, squeeze, B, L, lengths
+
+
 class Engine:
     """One libvfx handle on one GPU (not thread-safe, like the reference's module-level model)."""
 
@@ -229,10 +251,7 @@ class Engine:
             est, target = est[None], target[None]
         if est.shape != target.shape or est.dim() != 2:
             raise ValueError("audio_metrics: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
-        B, L = est.shape
-        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
-        if len(lengths) != B:
-            raise ValueError("audio_metrics: %d lengths for %d clips" % (len(lengths), B))
+        est, _, B, L, lengths = _clip_rows(est, lengths, "audio_metrics")
         out = torch.empty((B, _lib.N_AUDIO_METRICS), device=self.device, dtype=torch.float64)
         _lib.check(self.lib.vfx_audio_metrics(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
                                               self._stream()), "vfx_audio_metrics")
@@ -309,15 +328,9 @@ class Engine:
         length out_lengths[b] = ceil(lengths[b] * up / down).  Window form (streamed input): x holds input indices [x0, x0 + L) of
         every clip, and y (B, n_out) receives outputs [o0, o0 + n_out) (default: up to the longest clip's output length); the window
         must hold what `resample_window` asks for, or the call raises.  1-D x gives a 1-D y and an int out length."""
-        x = _dev_f32(x, self.device)
-        squeeze = x.dim() == 1
-        if squeeze:
-            x = x[None]
-        B, L = x.shape
         x0, o0 = int(x0), int(o0)
-        lengths = [x0 + L] * B if lengths is None else [int(v) for v in lengths]
-        if len(lengths) != B:
-            raise ValueError("resample: %d lengths for %d clips" % (len(lengths), B))
+        x, squeeze, B, L, lens = _clip_rows(_dev_f32(x, self.device), lengths, "resample")
+        lengths = [x0 + L] * B if lengths is None else lens
         up, down = self.resample_ratio(sr_in, sr_out)
         out_lengths = [self.resample_out_len(n, sr_in, sr_out) for n in lengths]
         if any(n < 0 for n in out_lengths):
@@ -377,15 +390,9 @@ class Engine:
         if x.dtype not in (torch.float32, torch.float64):
             x = x.to(torch.float64)
         x = x.to(self.device).contiguous()
-        squeeze = x.dim() == 1
-        if squeeze:
-            x = x[None]
-        if x.dim() != 2:
+        if x.dim() not in (1, 2):
             raise ValueError("sosfiltfilt: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
-        B, L = x.shape
-        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
-        if len(lengths) != B:
-            raise ValueError("sosfiltfilt: %d lengths for %d clips" % (len(lengths), B))
+        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "sosfiltfilt")
         if B == 0 or min(lengths) <= padlen:
             raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
         if max(lengths) > L:
@@ -420,8 +427,8 @@ class Engine:
         if x.dim() != 2 or rirs.dim() != 2:
             raise ValueError("reverb_rir: x must be (B, L) or (L,) and rirs (R, M) or (M,), got %s and %s"
                              % (tuple(x.shape), tuple(rirs.shape)))
-        (B, L), (R, M) = x.shape, rirs.shape
-        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+        x, _, B, L, lengths = _clip_rows(x, lengths)      # (the counts are checked together below)
+        R, M = rirs.shape
         rir_lengths = [M] * R if rir_lengths is None else [int(v) for v in rir_lengths]
         if R == 0 or B == 0:
             raise ValueError("reverb_rir: %d clips and %d RIRs" % (B, R))
@@ -448,16 +455,14 @@ class Engine:
         sig = {"front": front, "noise": noise, "hq": hq, "aug": aug}
         sig = {k: _dev_f32(v, self.device) for k, v in sig.items() if v is not None}
         front = sig["front"]
-        squeeze = front.dim() == 1
         if any(v.shape != front.shape for v in sig.values()) or front.dim() not in (1, 2):
             raise ValueError("mix_noise: every signal must be (B, L) or (L,) of one shape, got %s"
                              % ", ".join("%s %s" % (k, tuple(v.shape)) for k, v in sig.items()))
+        _, squeeze, B, L, lengths = _clip_rows(front, lengths)      # (the counts are checked together below)
         if squeeze:
             sig = {k: v[None] for k, v in sig.items()}
-        B, L = sig["front"].shape
         if B == 0:
             raise ValueError("mix_noise: no clips")
-        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
 
         def per_clip(v, default):
             v = default if v is None else v
@@ -496,9 +501,7 @@ class Engine:
         out = torch.empty_like(mel)
         arr = None
         if frames is not None:
-            frames = [int(v) for v in frames]
-            if len(frames) != B:
-                raise ValueError("analysis_mel: %d frame counts for %d clips" % (len(frames), B))
+            frames = _clip_rows(mel[:, :, 0], frames, "analysis_mel", "frame counts")[4]
             arr = (ctypes.c_int * B)(*frames)
         _lib.check(self.lib.vfx_analysis_mel(self.h, int(model), _ptr(mel), B, T, arr, _ptr(out), self._stream()),
                    "vfx_analysis_mel")
@@ -555,19 +558,17 @@ class Engine:
         slope = float(self.cfg.voc_res_slope)
         return not (int(self.cfg.tuning) & _lib.TUNE_F32_TRUNK) and 0.0 < slope <= 1.0
 
+    def _varlen_args(self, wav, lengths, out, name):
+        """The prologue of the two varlen entries -> (wav on the device, B, Lmax, the lengths as the C int array, out)."""
+        wav, _, B, L, lengths = _clip_rows(_dev_f32(wav, self.device), lengths, name)
+        return wav, B, L, (ctypes.c_int * B)(*lengths), torch.empty_like(wav) if out is None else out
+
     def restore_gsr_varlen(self, wav, lengths, unify_energy=False, want_logmel=False, out=None):
         """The handler() segment body for a batch of clips of UNEQUAL length: wav (B, Lmax), clip b = wav[b, :lengths[b]]
         -> restored (B, Lmax), zero past a clip's end.  Every clip gets what its own restore_gsr(wav[b:b+1, :lengths[b]])
         computes (vfx_restore_gsr_varlen).  Any mix of lengths (round 6): the library runs the mel ResUNet once per padded frame
         count among the clips and the vocoder once over the whole batch."""
-        wav = _dev_f32(wav, self.device)
-        B, L = wav.shape
-        lengths = [int(v) for v in lengths]
-        if len(lengths) != B:
-            raise ValueError("restore_gsr_varlen: %d lengths for %d clips" % (len(lengths), B))
-        arr = (ctypes.c_int * B)(*lengths)
-        if out is None:
-            out = torch.empty_like(wav)
+        wav, B, L, arr, out = self._varlen_args(wav, lengths, out, "restore_gsr_varlen")
         logmel = torch.empty((B, self.frames(L), N_MELS), device=self.device, dtype=torch.float32) if want_logmel else None
         _lib.check(self.lib.vfx_restore_gsr_varlen(self.h, _ptr(wav), B, L, arr, _ptr(out), _ptr(logmel),
                                                    int(bool(unify_energy)), self._stream()), "vfx_restore_gsr_varlen")
@@ -576,14 +577,7 @@ class Engine:
     def restore_ssr_varlen(self, wav, lengths, out=None):
         """ssr_unet / gsr_unet forward (sp = |STFT(wav)|, model(sp, wav)) for a batch of clips of UNEQUAL length: wav (B, Lmax),
         clip b = wav[b, :lengths[b]] -> (B, Lmax), zero past a clip's end; one `padded_frames` bucket per call."""
-        wav = _dev_f32(wav, self.device)
-        B, L = wav.shape
-        lengths = [int(v) for v in lengths]
-        if len(lengths) != B:
-            raise ValueError("restore_ssr_varlen: %d lengths for %d clips" % (len(lengths), B))
-        arr = (ctypes.c_int * B)(*lengths)
-        if out is None:
-            out = torch.empty_like(wav)
+        wav, B, L, arr, out = self._varlen_args(wav, lengths, out, "restore_ssr_varlen")
         _lib.check(self.lib.vfx_restore_ssr_varlen(self.h, _ptr(wav), B, L, arr, _ptr(out), self._stream()), "vfx_restore_ssr_varlen")
         return out
 
@@ -647,41 +641,35 @@ class Engine:
         """x (B,H,W,Cin) channels-last; weight (Cout,Cin,kh,kw) torch layout (host)."""
         x = _dev_f32(x, self.device)
         B, H, W, Cin = x.shape
-        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32))
+        w = _host(weight)
         Cout, _, kh, kw = w.shape
         y = torch.empty((B, H, W, Cout), device=self.device, dtype=torch.float32)
-        hp = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        scale, shift, bias = hp(scale), hp(shift), hp(bias)
-        cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        scale, shift, bias = _host(scale), _host(shift), _host(bias)
         res = None if residual is None else _dev_f32(residual, self.device)
-        _lib.check(_lib.load_test().vfx_op_conv(self.h, _ptr(x), B, H, W, Cin, cp(w), Cout, kh, kw, dil_w, int(reflect_w), cp(scale),
-                                        cp(shift), act, float(slope), cp(bias), _ptr(res), _ptr(y), self._stream()),
-                   "vfx_op_conv")
+        _lib.check(_lib.load_test().vfx_op_conv(self.h, _ptr(x), B, H, W, Cin, _hptr(w), Cout, kh, kw, dil_w, int(reflect_w),
+                                                _hptr(scale), _hptr(shift), act, float(slope), _hptr(bias), _ptr(res), _ptr(y),
+                                                self._stream()), "vfx_op_conv")
         return y
 
     def op_resblock(self, x, w1, b1, w2, b2, dil, slope=0.01, fused=True):
         """One ResStack layer on x (B, T, C) channels-last; w1 / w2 (C, C, 3), b1 / b2 (C) torch layout (host)."""
         x = _dev_f32(x, self.device)
         B, T, C = x.shape
-        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        w1, b1, w2, b2 = hp(w1), hp(b1), hp(w2), hp(b2)
-        cp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        layer = [_host(a) for a in (w1, b1, w2, b2)]
         y = torch.empty_like(x)
-        _lib.check(_lib.load_test().vfx_op_resblock(self.h, _ptr(x), B, T, C, cp(w1), cp(b1), cp(w2), cp(b2), int(dil), float(slope),
-                                            int(bool(fused)), _ptr(y), self._stream()), "vfx_op_resblock")
+        _lib.check(_lib.load_test().vfx_op_resblock(self.h, _ptr(x), B, T, C, *[_hptr(a) for a in layer], int(dil), float(slope),
+                                                    int(bool(fused)), _ptr(y), self._stream()), "vfx_op_resblock")
         return y
 
     def op_resblock_pair(self, x, layer_a, dil_a, layer_b, dil_b, slope=0.01):
         """Two consecutive ResStack layers as one launch (16-bit mode, C = 64); layer_* = (w1, b1, w2, b2) in torch layout."""
         x = _dev_f32(x, self.device)
         B, T, C = x.shape
-        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        la, lb = [hp(a) for a in layer_a], [hp(a) for a in layer_b]
-        cp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        la, lb = [_host(a) for a in layer_a], [_host(a) for a in layer_b]
         y = torch.empty_like(x)
-        _lib.check(_lib.load_test().vfx_op_resblock_pair(self.h, _ptr(x), B, T, C, cp(la[0]), cp(la[1]), cp(la[2]), cp(la[3]), int(dil_a),
-                                                 cp(lb[0]), cp(lb[1]), cp(lb[2]), cp(lb[3]), int(dil_b), float(slope), _ptr(y),
-                                                 self._stream()), "vfx_op_resblock_pair")
+        _lib.check(_lib.load_test().vfx_op_resblock_pair(self.h, _ptr(x), B, T, C, *[_hptr(a) for a in la[:4]], int(dil_a),
+                                                         *[_hptr(a) for a in lb[:4]], int(dil_b), float(slope), _ptr(y),
+                                                         self._stream()), "vfx_op_resblock_pair")
         return y
 
     def op_block2d(self, x, w1, sc1, sh1, w2, sc2, sh2, slope=0.01):
@@ -689,30 +677,26 @@ class Engine:
         BatchNorm affines (C) in torch layout on the host."""
         x = _dev_f32(x, self.device)
         B, H, W, C = x.shape
-        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        w1, sc1, sh1, w2, sc2, sh2 = hp(w1), hp(sc1), hp(sh1), hp(w2), hp(sc2), hp(sh2)
-        cp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        block = [_host(a) for a in (w1, sc1, sh1, w2, sc2, sh2)]
         y = torch.empty_like(x)
-        _lib.check(_lib.load_test().vfx_op_block2d(self.h, _ptr(x), B, H, W, C, cp(w1), cp(sc1), cp(sh1), cp(w2), cp(sc2), cp(sh2),
-                                           float(slope), _ptr(y), self._stream()), "vfx_op_block2d")
+        _lib.check(_lib.load_test().vfx_op_block2d(self.h, _ptr(x), B, H, W, C, *[_hptr(a) for a in block], float(slope), _ptr(y),
+                                                   self._stream()), "vfx_op_block2d")
         return y
 
     def op_conv_transpose(self, x, weight, stride, prune_w=False, scale=None, shift=None, act=0, slope=0.0, bias=None):
         x = _dev_f32(x, self.device)
         B, H, W, Cin = x.shape
-        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32))
+        w = _host(weight)
         _, Cout, kh, kw = w.shape
         if kh == 3:
             shape = (B, 2 * H, 2 * W if prune_w else 2 * W + 1, Cout)
         else:
             shape = (B, 1, W * stride, Cout)
         y = torch.empty(shape, device=self.device, dtype=torch.float32)
-        hp = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        scale, shift, bias = hp(scale), hp(shift), hp(bias)
-        cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(_lib.load_test().vfx_op_conv_transpose(self.h, _ptr(x), B, H, W, Cin, cp(w), Cout, kh, kw, stride, int(prune_w),
-                                                  cp(scale), cp(shift), act, float(slope), cp(bias), _ptr(y), self._stream()),
-                   "vfx_op_conv_transpose")
+        scale, shift, bias = _host(scale), _host(shift), _host(bias)
+        _lib.check(_lib.load_test().vfx_op_conv_transpose(self.h, _ptr(x), B, H, W, Cin, _hptr(w), Cout, kh, kw, stride, int(prune_w),
+                                                          _hptr(scale), _hptr(shift), act, float(slope), _hptr(bias), _ptr(y),
+                                                          self._stream()), "vfx_op_conv_transpose")
         return y
 
     # the vocoder's launches as its plan builds them (include/vfx_test.h: vfx_op_voc_*)
@@ -721,8 +705,7 @@ class Engine:
         output; 1.0: the fp16 trunk of the 16-bit mode.  y starts as NaN, so do unwritten elements of ya."""
         x = _dev_f32(x, self.device)
         B, T, Cin = x.shape
-        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        w, b = hp(weight), hp(bias)
+        w, b = _host(weight), _host(bias)
         Cout = w.shape[1]
         shape = (B, T * stride, Cout)
         y = torch.full(shape, float("nan"), device=self.device) if want_raw else None
@@ -730,10 +713,9 @@ class Engine:
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
         up16 = ctypes.c_int(-1)
         _lib.check(_lib.load_test().vfx_op_voc_upsample(
-            self.h, _ptr(x), B, T, Cin, w.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), int(stride), float(up_slope),
-            int(bool(src_act)), int(bool(want_raw)), int(act_slope is not None), float(act_slope if act_slope is not None else 1.0),
-            None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(y), _ptr(ya), ctypes.byref(up16), self._stream()),
-            "vfx_op_voc_upsample")
+            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), int(stride), float(up_slope), int(bool(src_act)), int(bool(want_raw)),
+            int(act_slope is not None), float(act_slope if act_slope is not None else 1.0), _hptr(ln), _ptr(y), _ptr(ya),
+            ctypes.byref(up16), self._stream()), "vfx_op_voc_upsample")
         return y, ya, bool(up16.value)
 
     def op_voc_conv1d(self, x, weight, bias, dil=1, reflect=False, src_act=False, act=0, slope=1.0, residual=None, residual_act=False,
@@ -741,37 +723,35 @@ class Engine:
         """Conv1d of the vocoder plan on x (B, T, Cin): -> (y raw or None, ya activated or None); both start as NaN."""
         x = _dev_f32(x, self.device)
         B, T, Cin = x.shape
-        hp = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-        w, b = hp(weight), hp(bias)
+        w, b = _host(weight), _host(bias)
         Cout, _, K = w.shape
         y = torch.full((B, T, Cout), float("nan"), device=self.device) if want_raw else None
         ya = torch.empty((B, T, Cout), device=self.device) if next_act else None
         res = None if residual is None else _dev_f32(residual, self.device)
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
         _lib.check(_lib.load_test().vfx_op_voc_conv1d(
-            self.h, _ptr(x), B, T, Cin, w.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), Cout, K, int(dil),
-            int(bool(reflect)), int(bool(src_act)), int(act), float(slope), _ptr(res), int(bool(residual_act)), int(bool(want_raw)),
-            int(next_act), float(next_slope), None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(y), _ptr(ya),
-            self._stream()), "vfx_op_voc_conv1d")
+            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), Cout, K, int(dil), int(bool(reflect)), int(bool(src_act)), int(act),
+            float(slope), _ptr(res), int(bool(residual_act)), int(bool(want_raw)), int(next_act), float(next_slope), _hptr(ln),
+            _ptr(y), _ptr(ya), self._stream()), "vfx_op_voc_conv1d")
         return y, ya
 
     def op_voc_final(self, x, weight, bias, slope=0.2, x_f16=False, lens=None):
         """The vocoder tail on x (B, T, C): -> wav (B, T), NaN where nothing was written."""
         x = _dev_f32(x, self.device)
         B, T, C = x.shape
-        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32))
+        w = _host(weight)
         wav = torch.full((B, T), float("nan"), device=self.device)
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
         _lib.check(_lib.load_test().vfx_op_voc_final(
-            self.h, _ptr(x), B, T, C, w.ctypes.data_as(ctypes.c_void_p), float(bias), float(slope), int(bool(x_f16)),
-            None if ln is None else ln.ctypes.data_as(ctypes.c_void_p), _ptr(wav), self._stream()), "vfx_op_voc_final")
+            self.h, _ptr(x), B, T, C, _hptr(w), float(bias), float(slope), int(bool(x_f16)), _hptr(ln), _ptr(wav), self._stream()),
+            "vfx_op_voc_final")
         return wav
 
     def op_ssim(self, est, target, rows=None):
         """The SSIM kernels of audio_metrics alone: (B, T, F) images, image b = its first rows[b] rows -> (B,) float64."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
         B, T, F = est.shape
-        rows = [T] * B if rows is None else [int(v) for v in rows]
+        rows = _clip_rows(est[:, :, 0], rows, "op_ssim")[4]
         out = torch.empty(B, device=self.device, dtype=torch.float64)
         _lib.check(_lib.load_test().vfx_op_ssim(self.h, _ptr(est), _ptr(target), B, T, F, (ctypes.c_int * B)(*rows), _ptr(out),
                                                 self._stream()), "vfx_op_ssim")
@@ -780,8 +760,7 @@ class Engine:
     def op_sisdr(self, est, target, lengths=None):
         """The SI-SDR kernels of audio_metrics alone: (B, L), clip b = its first lengths[b] samples -> (B,) float64 dB."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
-        B, L = est.shape
-        lengths = [L] * B if lengths is None else [int(v) for v in lengths]
+        est, _, B, L, lengths = _clip_rows(est, lengths, "op_sisdr")
         out = torch.empty(B, device=self.device, dtype=torch.float64)
         _lib.check(_lib.load_test().vfx_op_sisdr(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
                                                  self._stream()), "vfx_op_sisdr")

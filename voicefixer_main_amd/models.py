@@ -24,6 +24,7 @@ import pickle
 import numpy as np
 import torch
 
+from . import clips
 from .engine import Engine, MODEL_DNN_MEL, MODEL_GRU_MEL, MODEL_UNET_MEL, MODEL_UNET_SPEC, MODEL_VOCODER
 
 EPS = 1e-8
@@ -309,11 +310,9 @@ def _resample_list(engine, wavs, sample_rate):
     if int(sample_rate) == sr_out or not wavs:
         return wavs
     lengths = [int(w.shape[-1]) for w in wavs]
-    batch = torch.zeros((len(wavs), max(max(lengths), 1)), device=engine.device, dtype=torch.float32)
-    for i, w in enumerate(wavs):
-        batch[i, :lengths[i]] = w.reshape(-1).to(device=engine.device, dtype=torch.float32)
+    batch = clips.pad([w.reshape(-1) for w in wavs], engine.device, torch.float32, width=max(max(lengths), 1))
     y, out_lengths = engine.resample(batch, sample_rate, sr_out, lengths=lengths)
-    return [y[i, :n] for i, n in enumerate(out_lengths)]
+    return clips.unpad(y, out_lengths, to_host=False)
 
 
 class _Base:

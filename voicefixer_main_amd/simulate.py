@@ -24,6 +24,9 @@ front-end and back-end (``vfx_stft_mel`` in its phase-emitting form and ``vfx_is
 ``Engine`` -- the reference keeps a module-level ``FDomainHelper`` for it (lowpass.py:14,111-113).
 """
 import numpy as np
+import torch
+
+from . import clips as _clips
 
 _engine = None     # the reference's module-level `f_helper` (lowpass.py:14): created on first use of `stft_hard`
 
@@ -40,6 +43,10 @@ def _get_engine():
         from .engine import Engine
         _engine = Engine("cuda:0")
     return _engine
+
+
+def _engine_or_default(engine):
+    return engine if engine is not None else _get_engine()
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -112,8 +119,7 @@ def stft_hard_lowpass_v0(data, lowpass_ratio, engine=None):
     magnitude bins from int(1025 * ratio) up set to zero, ISTFT to the original length.  Runs on the GPU: the front-end kernel
     in its phase-emitting form (`vfx_stft_mel`), the mask, `vfx_istft`.  Returns float32 (samples,) on the host like the
     reference's `.numpy()`."""
-    import torch
-    eng = engine if engine is not None else _get_engine()
+    eng = _engine_or_default(engine)
     length = data.shape[0]
     x = torch.as_tensor(np.ascontiguousarray(data), dtype=torch.float32)[None]
     o = eng.stft(x, want_mel=False, want_sp=True, want_phase=True)
@@ -123,15 +129,27 @@ def stft_hard_lowpass_v0(data, lowpass_ratio, engine=None):
     return eng.istft(sp * o["cos"], sp * o["sin"], length)[0].cpu().numpy()
 
 
-def lowpass(data, highcut, fs, order=5, _type="butter", engine=None):
-    """lowpass.py:152-187.  data: 1-D float array (samples,) -- (samples, 1) is an error, as in the reference."""
-    if len(list(data.shape)) != 1:
-        raise ValueError("Error (chebyshev_lowpass_filter): Data " + str(data.shape) +
-                         " should be type 1d time array, (samples,) , can not be (samples, 1)")
-    # substring tests, in the reference's order
+def _check_1d(clips):
+    for data in clips:
+        if len(list(data.shape)) != 1:
+            raise ValueError("Error (chebyshev_lowpass_filter): Data " + str(data.shape) +
+                             " should be type 1d time array, (samples,) , can not be (samples, 1)")
+
+
+def _iir_type(_type, order):
+    """The reference's substring tests for the IIR types, in its order, and its order clamp -> (name, order), or None."""
     for name in ("butter", "cheby1", "ellip", "bessel"):
         if _type in name:
-            return lowpass_filter(x=data, highcut=int(highcut), fs=fs, order=limit(order, high=10, low=2), ftype=name)
+            return name, limit(order, high=10, low=2)
+    return None
+
+
+def lowpass(data, highcut, fs, order=5, _type="butter", engine=None):
+    """lowpass.py:152-187.  data: 1-D float array (samples,) -- (samples, 1) is an error, as in the reference."""
+    _check_1d([data])
+    iir = _iir_type(_type, order)
+    if iir:
+        return lowpass_filter(x=data, highcut=int(highcut), fs=fs, order=iir[1], ftype=iir[0])
     if _type in "stft":
         return stft_hard_lowpass(data, lowpass_ratio=highcut / int(fs / 2))
     if _type in "stft_hard":
@@ -142,95 +160,62 @@ def lowpass(data, highcut, fs, order=5, _type="butter", engine=None):
 def bandpass(data, lowcut, highcut, fs, order=5, _type="butter"):
     """lowpass.py:189-215: the band-pass twin of `lowpass` -- same 1-D check, same substring dispatch and order clamp, IIR
     types only (butter / cheby1 / ellip / bessel; cheby2 is commented out in the reference and raises here as well)."""
-    if len(list(data.shape)) != 1:
-        raise ValueError("Error (chebyshev_lowpass_filter): Data " + str(data.shape) +
-                         " should be type 1d time array, (samples,) , can not be (samples, 1)")
-    for name in ("butter", "cheby1", "ellip", "bessel"):
-        if _type in name:
-            return bandpass_filter(x=data, lowcut=int(lowcut), highcut=int(highcut), fs=fs,
-                                   order=limit(order, high=10, low=2), ftype=name)
+    _check_1d([data])
+    iir = _iir_type(_type, order)
+    if iir:
+        return bandpass_filter(x=data, lowcut=int(lowcut), highcut=int(highcut), fs=fs, order=iir[1], ftype=iir[0])
     raise ValueError("Error: Unexpected filter type " + _type)
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# batch forms: a whole test set of clips per call, the IIR types on the device (Engine.sosfiltfilt, csrc/sosfilt.hip)
+# batch forms: a whole test set of clips per call, the IIR types on the device (Engine.sosfiltfilt, csrc/sosfilt.hip).
+# Ordering by length, batching, padding and handing the rows back are clips.py's; a function here decides which items go to
+# the device, what a batch is made of and which Engine method takes it.
 # ------------------------------------------------------------------------------------------------------------------
 MAX_BATCH = 128     # clips per device call, as in restore_list / evaluation_list
 
 
-def _check_1d(clips):
-    for data in clips:
-        if len(list(data.shape)) != 1:
-            raise ValueError("Error (chebyshev_lowpass_filter): Data " + str(data.shape) +
-                             " should be type 1d time array, (samples,) , can not be (samples, 1)")
-
-
-def _is_f32(clip):
-    return str(clip.dtype).endswith("float32")
-
-
-def _results(ys, to_host):
-    """device tensors -> what the caller asked for"""
-    return [y.cpu().numpy() for y in ys] if to_host else ys
-
-
 def _sosfiltfilt_list(clips, sos, engine, to_host):
-    """scipy.signal.sosfiltfilt(sos, clip) of every clip: sorted by length, padded batches of up to MAX_BATCH clips of one dtype
-    (float32 clips are extended in float32, as SciPy does; every other dtype goes as float64), results in the caller's order."""
-    import torch
-    eng = engine if engine is not None else _get_engine()
+    """scipy.signal.sosfiltfilt(sos, clip) of every clip, in padded batches of one dtype (float32 clips are extended in float32, as
+    SciPy does; every other dtype goes as float64), results in the caller's order."""
+    eng = _engine_or_default(engine)
     padlen = eng.sosfiltfilt_padlen(sos)
     if any(c.shape[0] <= padlen for c in clips):
         raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+    lengths = [c.shape[0] for c in clips]
     out = [None] * len(clips)
     for f32 in (True, False):
         dtype = torch.float32 if f32 else torch.float64
-        order = sorted((i for i in range(len(clips)) if _is_f32(clips[i]) == f32), key=lambda i: clips[i].shape[0])
-        for k in range(0, len(order), MAX_BATCH):
-            idx = order[k:k + MAX_BATCH]
-            lengths = [clips[i].shape[0] for i in idx]
-            batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=dtype)
-            for j, i in enumerate(idx):
-                c = clips[i]
-                batch[j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(
-                    device=eng.device, dtype=dtype)
-            y = eng.sosfiltfilt(batch, sos, lengths=lengths)
-            if to_host:
-                y = y.cpu().numpy()
-            for j, i in enumerate(idx):
-                out[i] = y[j, :lengths[j]].copy() if to_host else y[j, :lengths[j]]
+        for idx in _clips.batches([i for i in range(len(clips)) if _clips.is_f32(clips[i]) == f32], lengths, MAX_BATCH):
+            lens = [lengths[i] for i in idx]
+            y = eng.sosfiltfilt(_clips.pad([clips[i] for i in idx], eng.device, dtype), sos, lengths=lens)
+            for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
+                out[i] = row
     return out
 
 
 def _stft_list(clips, ratio, engine, to_host, fs_ori=44100):
     """`_type="stft"` for a list: float32 clips whose two rate pairs the device resampler takes go down and up through
     Engine.resample as padded batches (bit for bit `stft_hard_lowpass`); everything else takes the host function."""
-    import torch
     from .engine import Engine
     fs_down = int(ratio * fs_ori)
     on_device = fs_down > 0 and fs_down != fs_ori and Engine.resample_supported(fs_ori, fs_down) and Engine.resample_supported(fs_down, fs_ori)
-    eng = engine if engine is not None else _get_engine()
+    eng = _engine_or_default(engine)
+    lengths = [c.shape[0] for c in clips]
     out = [None] * len(clips)
-    dev = [i for i in range(len(clips)) if on_device and _is_f32(clips[i]) and clips[i].shape[0] > 0]
-    dev.sort(key=lambda i: clips[i].shape[0])
-    for k in range(0, len(dev), MAX_BATCH):
-        idx = dev[k:k + MAX_BATCH]
-        lengths = [clips[i].shape[0] for i in idx]
-        batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=torch.float32)
-        for j, i in enumerate(idx):
-            c = clips[i]
-            batch[j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(eng.device)
-        low, low_lengths = eng.resample(batch, fs_ori, fs_down, lengths=lengths)
-        y, y_lengths = eng.resample(low, fs_down, fs_ori, lengths=low_lengths)
-        for j, i in enumerate(idx):      # align_length: cut, or zero-padded at the end (rows are zero past their length)
-            n = lengths[j]
-            row = y[j, :n] if y.shape[1] >= n else torch.nn.functional.pad(y[j], (0, n - y.shape[1]))
-            out[i] = row.cpu().numpy() if to_host else row
+    dev = [i for i in range(len(clips)) if on_device and _clips.is_f32(clips[i]) and lengths[i] > 0]
+    for idx in _clips.batches(dev, lengths, MAX_BATCH):
+        lens = [lengths[i] for i in idx]
+        low, low_lengths = eng.resample(_clips.pad([clips[i] for i in idx], eng.device, torch.float32), fs_ori, fs_down, lengths=lens)
+        y, _ = eng.resample(low, fs_down, fs_ori, lengths=low_lengths)
+        if y.shape[1] < lens[-1]:      # align_length: cut, or zero-padded at the end (rows are zero past their length)
+            y = torch.nn.functional.pad(y, (0, lens[-1] - y.shape[1]))
+        for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
+            out[i] = row
     for i in range(len(clips)):
         if out[i] is None:
-            c = clips[i]
-            y = stft_hard_lowpass(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, lowpass_ratio=ratio, fs_ori=fs_ori)
-            out[i] = y if to_host else torch.from_numpy(np.ascontiguousarray(y)).to(eng.device)
+            y = stft_hard_lowpass(_clips.as_numpy(clips[i]), lowpass_ratio=ratio, fs_ori=fs_ori)
+            out[i] = y if to_host else _clips.to_device(y, eng.device)
     return out
 
 
@@ -241,18 +226,15 @@ def lowpass_list(clips, highcut, fs, order=5, _type="butter", engine=None, to_ho
     that `restore_list` takes as they are."""
     clips = list(clips)
     _check_1d(clips)
-    for name in ("butter", "cheby1", "ellip", "bessel"):
-        if _type in name:
-            sos = _design(limit(order, high=10, low=2), int(highcut) / (0.5 * fs), "low", name, "lowpass")
-            return _sosfiltfilt_list(clips, sos, engine, to_host)
+    iir = _iir_type(_type, order)
+    if iir:
+        return _sosfiltfilt_list(clips, _design(iir[1], int(highcut) / (0.5 * fs), "low", iir[0], "lowpass"), engine, to_host)
     if _type in "stft":
         return _stft_list(clips, highcut / int(fs / 2), engine, to_host)
     if _type in "stft_hard":
-        import torch
-        eng = engine if engine is not None else _get_engine()
-        ys = [stft_hard_lowpass_v0(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, lowpass_ratio=highcut / int(fs / 2),
-                                   engine=eng) for c in clips]
-        return ys if to_host else [torch.from_numpy(y).to(eng.device) for y in ys]
+        eng = _engine_or_default(engine)
+        ys = [stft_hard_lowpass_v0(_clips.as_numpy(c), lowpass_ratio=highcut / int(fs / 2), engine=eng) for c in clips]
+        return ys if to_host else [_clips.to_device(y, eng.device) for y in ys]
     raise ValueError("Error: Unexpected filter type " + _type)
 
 
@@ -260,11 +242,11 @@ def bandpass_list(clips, lowcut, highcut, fs, order=5, _type="butter", engine=No
     """`bandpass` for a list of 1-D clips, as `lowpass_list` (IIR types only)."""
     clips = list(clips)
     _check_1d(clips)
-    for name in ("butter", "cheby1", "ellip", "bessel"):
-        if _type in name:
-            nyq = 0.5 * fs
-            sos = _design(limit(order, high=10, low=2), [int(lowcut) / nyq, int(highcut) / nyq], "band", name, "bandpass")
-            return _sosfiltfilt_list(clips, sos, engine, to_host)
+    iir = _iir_type(_type, order)
+    if iir:
+        nyq = 0.5 * fs
+        sos = _design(iir[1], [int(lowcut) / nyq, int(highcut) / nyq], "band", iir[0], "bandpass")
+        return _sosfiltfilt_list(clips, sos, engine, to_host)
     raise ValueError("Error: Unexpected filter type " + _type)
 
 
@@ -289,7 +271,6 @@ def reverb_rir_list(clips, rirs, rir_index=None, engine=None, to_host=True):
     float32 clips with float32 RIRs are sorted by length and go through Engine.reverb_rir as padded batches of up to MAX_BATCH --
     direct-form convolution, each clip bit for bit what its own device call gives; every other dtype takes the host function.
     -> list in the caller's order: NumPy arrays (to_host), or device tensors that `restore_list` takes as they are."""
-    import torch
     clips = list(clips)
     rirs = [rirs] if isinstance(rirs, (np.ndarray, torch.Tensor)) else list(rirs)
     if not rirs:
@@ -297,45 +278,33 @@ def reverb_rir_list(clips, rirs, rir_index=None, engine=None, to_host=True):
     rir_index = [i % len(rirs) for i in range(len(clips))] if rir_index is None else [int(v) for v in rir_index]
     if len(rir_index) != len(clips) or any(not 0 <= r < len(rirs) for r in rir_index):
         raise ValueError("reverb_rir_list: %d indices for %d clips, each must be in [0, %d)" % (len(rir_index), len(clips), len(rirs)))
-    eng = engine if engine is not None else _get_engine()
+    eng = _engine_or_default(engine)
 
-    def host(a):
-        return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-    def flat(a):     # the 1-D device form of a clip or RIR that np.squeeze makes 1-D and non-empty, or None
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        t = t.squeeze()
+    def flat(a):     # the 1-D tensor form of a clip or RIR that np.squeeze makes 1-D and non-empty, or None
+        t = _clips.as_tensor(a).squeeze()
         return t if t.dim() == 1 and t.numel() > 0 else None
 
-    out = [None] * len(clips)
     def on_device(clip, rir):      # (a clip that squeezes to another length than shape[0] is cut differently: host)
         c, r = flat(clip), flat(rir)
-        return (_is_f32(clip) and _is_f32(rir) and c is not None and r is not None and c.numel() == clip.shape[0]
+        return (_clips.is_f32(clip) and _clips.is_f32(rir) and c is not None and r is not None and c.numel() == clip.shape[0]
                 and r.numel() <= eng.MAX_RIR_TAPS)
 
+    lengths = [c.shape[0] for c in clips]
+    out = [None] * len(clips)
     dev = [i for i in range(len(clips)) if on_device(clips[i], rirs[rir_index[i]])]
-    dev.sort(key=lambda i: clips[i].shape[0])
-    for k in range(0, len(dev), MAX_BATCH):
-        idx = dev[k:k + MAX_BATCH]
-        lengths = [clips[i].shape[0] for i in idx]
-        used = sorted({rir_index[i] for i in idx})
+    for idx in _clips.batches(dev, lengths, MAX_BATCH):
+        lens = [lengths[i] for i in idx]
+        used = sorted({rir_index[i] for i in idx})      # the batch's bank: the RIRs it uses, padded like the clips
         taps = [flat(rirs[r]) for r in used]
-        bank = torch.zeros((len(used), max(t.numel() for t in taps)), device=eng.device, dtype=torch.float32)
-        for j, t in enumerate(taps):
-            bank[j, :t.numel()] = t.to(eng.device)
-        batch = torch.zeros((len(idx), lengths[-1]), device=eng.device, dtype=torch.float32)
-        for j, i in enumerate(idx):
-            batch[j, :lengths[j]] = flat(clips[i]).to(eng.device)
-        y, _ = eng.reverb_rir(batch, bank, rir_index=[used.index(rir_index[i]) for i in idx], lengths=lengths,
-                              rir_lengths=[t.numel() for t in taps])
-        if to_host:
-            y = y.cpu().numpy()
-        for j, i in enumerate(idx):
-            out[i] = y[j, :lengths[j]].copy() if to_host else y[j, :lengths[j]]
+        y, _ = eng.reverb_rir(_clips.pad([flat(clips[i]) for i in idx], eng.device, torch.float32),
+                              _clips.pad(taps, eng.device, torch.float32), rir_index=[used.index(rir_index[i]) for i in idx],
+                              lengths=lens, rir_lengths=[t.numel() for t in taps])
+        for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
+            out[i] = row
     for i in range(len(clips)):
         if out[i] is None:
-            y = reverb_rir(host(clips[i]), host(rirs[rir_index[i]]))
-            out[i] = y if to_host else torch.from_numpy(np.ascontiguousarray(y)).to(eng.device)
+            y = reverb_rir(_clips.as_numpy(clips[i]), _clips.as_numpy(rirs[rir_index[i]]))
+            out[i] = y if to_host else _clips.to_device(y, eng.device)
     return out
 
 
@@ -439,7 +408,6 @@ _MIX_FORMS = (     # the host function and its signals in argument order (= the 
 
 def _mix_list(form, signals, snr_l, snr_h, scale_lower, scale_upper, rng, engine, to_host, want_noisy):
     """signals: one list of 1-D clips per argument of the host function.  -> the host function's tuple per item (+ noisy)"""
-    import torch
     host_fn, names = _MIX_FORMS[form]
     signals = [list(s) for s in signals]
     n = len(signals[0])
@@ -455,53 +423,38 @@ def _mix_list(form, signals, snr_l, snr_h, scale_lower, scale_upper, rng, engine
                              % (host_fn.__name__, i, ", ".join(str(c.shape[0]) for c in item)))
     rng = rng if rng is not None else np.random.default_rng()
     speech = "aug" if form == 2 else "front"
-    eng = engine
-
-    def device():      # the Engine only when something needs the device
-        nonlocal eng
-        if eng is None:
-            eng = _get_engine()
-        return eng
-
+    eng = engine      # the default Engine is created only when something needs the device
     out = [None] * n
     draws = {}
     for i in range(n):      # in list order: the device items' draws, the host items' calls (which draw for themselves)
         item = [s[i] for s in signals]
-        if all(_is_f32(c) for c in item) and item[0].shape[0] > 0:
+        if all(_clips.is_f32(c) for c in item) and item[0].shape[0] > 0:
             snr = _uniform(snr_l, snr_h, rng) if snr_l is not None and snr_h is not None else None
             draws[i] = (snr, _uniform(scale_lower, scale_upper, rng))
             continue
-        res = host_fn(*[c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c) for c in item], snr_l=snr_l, snr_h=snr_h,
-                      scale_lower=scale_lower, scale_upper=scale_upper, rng=rng)
+        res = host_fn(*[_clips.as_numpy(c) for c in item], snr_l=snr_l, snr_h=snr_h, scale_lower=scale_lower, scale_upper=scale_upper,
+                      rng=rng)
         ys = list(res[:len(names)])
         if want_noisy:
             ys.append(ys[names.index("noise")] + ys[names.index(speech)])
         if not to_host:
-            ys = [torch.from_numpy(np.ascontiguousarray(y)).to(device().device) for y in ys]
+            eng = _engine_or_default(eng)
+            ys = [_clips.to_device(y, eng.device) for y in ys]
         out[i] = tuple(ys[:len(names)]) + tuple(res[len(names):]) + tuple(ys[len(names):])
-    dev = sorted(draws, key=lambda i: signals[0][i].shape[0])
-    for k in range(0, len(dev), MAX_BATCH):
-        idx = dev[k:k + MAX_BATCH]
-        lengths = [signals[0][i].shape[0] for i in idx]
-        ld = (lengths[-1] + 3) // 4 * 4      # rows 16-byte aligned: the kernels' wide loads and stores
-        batch = {}
-        for name, s in zip(names, signals):
-            batch[name] = torch.zeros((len(idx), ld), device=device().device, dtype=torch.float32)
-            for j, i in enumerate(idx):
-                c = s[i]
-                batch[name][j, :lengths[j]] = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))).to(
-                    device().device)
+    lengths = [c.shape[0] for c in signals[0]]
+    for idx in _clips.batches(draws, lengths, MAX_BATCH):
+        eng = _engine_or_default(eng)
+        lens = [lengths[i] for i in idx]
+        ld = (lens[-1] + 3) // 4 * 4      # rows 16-byte aligned: the kernels' wide loads and stores
+        batch = {name: _clips.pad([s[i] for i in idx], eng.device, torch.float32, width=ld) for name, s in zip(names, signals)}
         snrs = [draws[i][0] for i in idx]
-        y = device().mix_noise(batch["front"], batch["noise"], hq=batch.get("hq"), aug=batch.get("aug"), lengths=lengths,
-                               noise_weight=None if snrs[0] is None else [10 ** (float(v) / 20) for v in snrs],
-                               scale=[draws[i][1] for i in idx], want_noisy=want_noisy)
-        if to_host:
-            y = {name: v.cpu().numpy() for name, v in y.items()}
+        y = eng.mix_noise(batch["front"], batch["noise"], hq=batch.get("hq"), aug=batch.get("aug"), lengths=lens,
+                          noise_weight=None if snrs[0] is None else [10 ** (float(v) / 20) for v in snrs],
+                          scale=[draws[i][1] for i in idx], want_noisy=want_noisy)
+        cols = [_clips.unpad(y[name], lens, to_host) for name in names + (("noisy",) if want_noisy else ())]
         for j, i in enumerate(idx):
-            rows = [y[name][j, :lengths[j]] for name in names + (("noisy",) if want_noisy else ())]
-            if to_host:
-                rows = [r.copy() for r in rows]
-            out[i] = tuple(rows[:len(names)]) + draws[i] + tuple(rows[len(names):])
+            rows = tuple(col[j] for col in cols)
+            out[i] = rows[:len(names)] + draws[i] + rows[len(names):]
     return out
 
 
@@ -534,16 +487,8 @@ def add_noise_and_scale_with_HQ_with_Aug_list(HQ, front, augfront, noise, snr_l=
 def hard_clip_list(clips, threshold, engine=None, to_host=True):
     """`hard_clip` for a list of clips: float32 clips (NumPy or device tensors) through torch.clamp where they are, bit for bit
     np.clip; every other dtype takes the host function.  -> NumPy arrays (to_host), or tensors on the engine's device."""
-    import torch
     out = []
     for c in clips:
-        if _is_f32(c):
-            y = torch.clamp(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c)), -threshold, threshold)
-        else:
-            y = hard_clip(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, threshold)
-        if to_host:
-            out.append(y.cpu().numpy() if isinstance(y, torch.Tensor) else y)
-        else:
-            eng = engine if engine is not None else _get_engine()
-            out.append((y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y))).to(eng.device))
+        y = torch.clamp(_clips.as_tensor(c), -threshold, threshold) if _clips.is_f32(c) else hard_clip(_clips.as_numpy(c), threshold)
+        out.append(_clips.as_numpy(y) if to_host else _clips.to_device(y, _engine_or_default(engine).device))
     return out
