@@ -277,6 +277,23 @@ int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx,
                     const double* zi, int padlen, double* y, int64_t ldy, void* stream);
 
 /*
+ * vfx_sosfiltfilt with a design per clip (the training collator's low-pass, dataloaders/data_module.py:28-70, draws a cut-off, an
+ * order and a type for every item): row b is scipy.signal.sosfiltfilt(sos[filter_index[b]], clip b), bit for bit.
+ *   x, lengths, y as in vfx_sosfiltfilt;  filter_index HOST int[B], 0 <= filter_index[b] < F;
+ *   sos (F, Smax, 6) and zi (F, Smax, 2) HOST doubles, 1 <= F <= 128, 1 <= Smax <= 16: design f is the first sections[f] rows of its
+ *   slice (HOST int[F], 1 <= sections[f] <= Smax; the rows past them are not read), zi[f] = scipy.signal.sosfilt_zi of those rows;
+ *   padlens HOST int[F]: sosfiltfilt's default padlen of each design; a clip must be longer than the padlen of ITS design.
+ * The clips of a call may mix section counts freely: one launch pair (forward, backward) takes up to 128 clips, the blocks of
+ * different section counts running side by side.  The bank is uploaded on `stream` into a buffer of the handle, grown on demand,
+ * so a call is no subject for hipGraph capture.  Fails, launching nothing and leaving y as it is, for F, Smax, a section count or
+ * a padlen out of range, sos[f][s][3] != 1, an index outside [0, F), or a clip that is not longer than its design's padlen (the
+ * message names the clip, its length and that padlen).
+ */
+int vfx_sosfiltfilt_bank(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* filter_index,
+                         const double* sos, const double* zi, const int* sections, const int* padlens, int F, int Smax, double* y,
+                         int64_t ldy, void* stream);
+
+/*
  * Reverberation of a padded batch of clips: MagicalEffects.reverb_rir (dataloaders/augmentation/magical_effects.py:158-167) per clip,
  * the degradation of the `vctk_reverb` test set -- the full convolution of the clip with a room impulse response, the whole result
  * scaled to a peak of 0.98 when its peak exceeds 0.99, cut back to the clip's length.

@@ -57,6 +57,9 @@ SIGNATURES = {
                              c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "vfx_sosfiltfilt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(ctypes.c_double), c_int,
                                 POINTER(ctypes.c_double), c_int, c_void_p, c_int64, c_void_p]),
+    "vfx_sosfiltfilt_bank": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int),
+                                     POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int), POINTER(c_int), c_int, c_int,
+                                     c_void_p, c_int64, c_void_p]),
     "vfx_reverb_rir": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_void_p, c_int, c_int64, POINTER(c_int64),
                                POINTER(c_int), c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "vfx_mix_noise": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p,

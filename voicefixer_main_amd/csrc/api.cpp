@@ -448,6 +448,45 @@ int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx,
   VFX_API_END
 }
 
+int vfx_sosfiltfilt_bank(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* filter_index,
+                         const double* sos, const double* zi, const int* sections, const int* padlens, int F, int Smax, double* y,
+                         int64_t ldy, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && filter_index && sos && zi && sections && padlens && y && B > 0 && (x_f64 == 0 || x_f64 == 1),
+            "vfx_sosfiltfilt_bank: bad argument");
+  VFX_CHECK(F >= 1 && F <= kSosMaxDesigns, "vfx_sosfiltfilt_bank: %d designs (need 1 <= F <= %d)", F, kSosMaxDesigns);
+  VFX_CHECK(Smax >= 1 && Smax <= kSosMaxSections, "vfx_sosfiltfilt_bank: rows of %d sections (need 1 <= Smax <= %d)", Smax, kSosMaxSections);
+  for (int f = 0; f < F; ++f) {
+    VFX_CHECK(sections[f] >= 1 && sections[f] <= Smax, "vfx_sosfiltfilt_bank: design %d has %d sections (need 1 <= S <= %d)", f, sections[f],
+              Smax);
+    VFX_CHECK(padlens[f] >= 0 && padlens[f] <= 3 * (2 * sections[f] + 1), "vfx_sosfiltfilt_bank: design %d: padlen %d (need 0 <= padlen <= %d)",
+              f, padlens[f], 3 * (2 * sections[f] + 1));
+    for (int i = 0; i < sections[f]; ++i)
+      VFX_CHECK(sos[((size_t)f * Smax + i) * 6 + 3] == 1.0, "vfx_sosfiltfilt_bank: design %d: sos[%d][3] = %g, should be 1", f, i,
+                sos[((size_t)f * Smax + i) * 6 + 3]);
+  }
+  int64_t lext = 0;
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(filter_index[b] >= 0 && filter_index[b] < F, "vfx_sosfiltfilt_bank: clip %d asks for design %d of %d", b, filter_index[b], F);
+    const int padlen = padlens[filter_index[b]];
+    VFX_CHECK(lengths[b] > padlen,
+              "vfx_sosfiltfilt_bank: clip %d has %lld samples: the length must be greater than padlen, which is %d for its design %d", b,
+              (long long)lengths[b], padlen, filter_index[b]);
+    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 1024,
+              "vfx_sosfiltfilt_bank: clip %d has %lld samples, the rows hold %lld and %lld", b, (long long)lengths[b], (long long)ldx,
+              (long long)ldy);
+    lext = std::max(lext, lengths[b] + 2 * padlen);
+  }
+  const int64_t ldf = (lext + 63) / 64 * 64;
+  double* const f = reinterpret_cast<double*>(h->sos_ws.ensure(h, (size_t)std::min(B, kSosMaxClips) * ldf * sizeof(double), 0));
+  const size_t bank_bytes = (size_t)F * Smax * kSosBankRow * sizeof(double);
+  sosfilt_pack_bank(sos, zi, F, Smax, reinterpret_cast<double*>(h->sos_bank.stage(h, bank_bytes)));
+  const double* const bank = reinterpret_cast<const double*>(h->sos_bank.upload(bank_bytes, static_cast<hipStream_t>(stream)));
+  launch_sosfiltfilt_bank(x, x_f64, B, ldx, lengths, filter_index, bank, Smax, sections, padlens, f, ldf, y, ldy,
+                          static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 // ---------------------------------------------------------------------------------------------
 // room-impulse-response convolution (MagicalEffects.reverb_rir on the device: reverb.hip)
 // ---------------------------------------------------------------------------------------------

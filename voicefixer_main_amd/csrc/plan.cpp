@@ -520,6 +520,30 @@ char* GrowBuffer::ensure(vfx_handle* h, size_t need, size_t slack_div, const cha
   return p;
 }
 
+char* StagedUpload::stage(vfx_handle* h, size_t bytes) {
+  if (pending) VFX_HIP(hipEventSynchronize(copied));
+  pending = false;
+  dev.ensure(h, bytes, 0);
+  if (bytes > host_bytes) {
+    if (host) VFX_HIP(hipHostFree(host));
+    host = nullptr;
+    host_bytes = 0;
+    void* q = nullptr;
+    VFX_HIP(hipHostMalloc(&q, bytes, hipHostMallocDefault));
+    host = static_cast<char*>(q);
+    host_bytes = bytes;
+  }
+  return host;
+}
+
+char* StagedUpload::upload(size_t bytes, hipStream_t s) {
+  if (!copied) VFX_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+  VFX_HIP(hipMemcpyAsync(dev.p, host, bytes, hipMemcpyHostToDevice, s));
+  VFX_HIP(hipEventRecord(copied, s));
+  pending = true;
+  return dev.p;
+}
+
 // Rebase the plan's arena-relative pointers on the (possibly re-allocated) arena and upload
 // the parameter blocks.
 void bind_plan(vfx_handle* h, Plan& plan) {

@@ -223,4 +223,182 @@ void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int6
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The bank form: every clip has its own design.  k_sosfilt's lane mapping needs one section count per block, so the launcher orders
+// the clips of a launch by section count and a block owns up to kSosBankBlockClips clips of ONE count -- its descriptor says which.
+// Blocks of different counts run side by side in one grid: the pass is latency-bound, a launch per count would multiply its time.
+// A clip has a 16-lane row of the recurrence wave to itself, whatever S: wave 1 moves a block's clips one after the other, and
+// with more than about six of them it, not the recurrence, sets the block's time (DESIGN.md has the measurement), while a launch
+// of kSosMaxClips clips is 48 blocks at most either way.  x and y keep the caller's row order (SosClip::row); the forward scratch
+// is indexed by the clip's place in the launch.  Coefficients and zi come from the bank in device memory, read once per lane.  The
+// arithmetic is sos_tile's and ext_at's, as in k_sosfilt.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSosBankBlockClips = 4;  // one per 16-lane row of the recurrence wave
+static_assert(kSosMaxBlocks >= kSosMaxClips / kSosBankBlockClips + kSosMaxSections, "full blocks + one partial block per section count");
+struct SosBlock {
+  uint8_t S, first, count;  // section count, the block's clips [first, first + count) of the launch
+};
+struct SosClip {
+  int row, len;             // row of x and y; samples
+  uint16_t padlen, design;  // of its design; index into the bank
+};
+struct SosBankArgs {
+  const void* x;
+  double* f;
+  double* y;
+  const double* bank;  // (F, Smax, kSosBankRow)
+  int64_t ldx, ldf, ldy;
+  int x_f64, bwd, Smax;
+  SosBlock blk[kSosMaxBlocks];
+  SosClip clip[kSosMaxClips];
+};
+static_assert(sizeof(SosBankArgs) <= 2048, "the kernel-argument block");
+static_assert(kSosMaxClips <= 256 && kSosMaxDesigns <= 65536, "SosBlock::first, SosClip::design");
+
+__global__ __launch_bounds__(128) void k_sosfilt_bank(const SosBankArgs a) {
+  constexpr int C = kSosBankBlockClips;
+  __shared__ __attribute__((aligned(16))) double sos_smem[2 * C * kSosRow];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SosBlock d = a.blk[blockIdx.x];
+  const int S = d.S, c0 = d.first, nc = d.count;
+  const bool bwd = a.bwd != 0;
+  int64_t steps = 0;  // of the skewed cascade over the clip that needs most; the backward pass stops where its last kept output is done
+  for (int c = 0; c < nc; ++c) steps = max(steps, (int64_t)a.clip[c0 + c].len + (bwd ? 1 : 2) * (int)a.clip[c0 + c].padlen);
+  steps += S - 1;
+  const int ntiles = (int)((steps + kSosTile - 1) / kSosTile);
+
+  // wave 1: one row of kSosTile samples per clip, lane i <-> sample i of the tile
+  auto load_tile = [&](int t, int which) {
+    double* const buf = sos_smem + which * C * kSosRow;
+    const int64_t n = (int64_t)t * kSosTile + lane;
+#pragma unroll 4
+    for (int c = 0; c < nc; ++c) {
+      const SosClip k = a.clip[c0 + c];
+      const int64_t len = k.len, lext = len + 2 * (int)k.padlen;
+      double v = 0.0;
+      if (n < lext) {
+        if (bwd)
+          v = a.f[(int64_t)(c0 + c) * a.ldf + (lext - 1 - n)];
+        else if (a.x_f64)
+          v = ext_at(static_cast<const double*>(a.x) + (int64_t)k.row * a.ldx, len, (int)k.padlen, n);
+        else
+          v = ext_at(static_cast<const float*>(a.x) + (int64_t)k.row * a.ldx, len, (int)k.padlen, n);
+      }
+      buf[c * kSosRow + lane] = v;
+    }
+  };
+  // slot i of tile t holds the cascade's output for position t kSosTile + i - (S - 1) of the pass
+  auto flush_tile = [&](int t, int which) {
+    const double* const buf = sos_smem + which * C * kSosRow;
+    const int64_t p = (int64_t)t * kSosTile + lane - (S - 1);
+#pragma unroll 4
+    for (int c = 0; c < nc; ++c) {
+      const SosClip k = a.clip[c0 + c];
+      const int64_t len = k.len, lext = len + 2 * (int)k.padlen;
+      const double v = buf[c * kSosRow + lane];
+      if (bwd) {
+        const int64_t q = lext - 1 - p - (int)k.padlen;  // index in the clip
+        if (p >= 0 && q >= 0 && q < len) a.y[(int64_t)k.row * a.ldy + q] = v;
+      } else if (p >= 0 && p < lext) {
+        a.f[(int64_t)(c0 + c) * a.ldf + p] = v;
+      }
+    }
+  };
+
+  // wave 0: lane -> (clip, section) = (its 16-lane row, its place in the row); the lanes past S and the rows past nc idle along
+  const int lc = lane >> 4;
+  const bool active = (lane & 15) < S && lc < nc;
+  const int lcc = active ? lc : 0, s = active ? lane & 15 : 0;
+  SosLane L;
+  L.s = s;
+  L.first = s == 0;
+  L.last = active && s == S - 1;
+  L.b0 = L.b1 = L.b2 = L.a1 = L.a2 = 0.0;
+  L.z0 = L.z1 = L.xc = 0.0;
+  if (wave == 0) {
+    const SosClip k = a.clip[c0 + lcc];
+    const double* const sec = a.bank + ((int64_t)k.design * a.Smax + s) * kSosBankRow;
+    L.b0 = sec[0], L.b1 = sec[1], L.b2 = sec[2], L.a1 = sec[3], L.a2 = sec[4];
+    const int64_t len = k.len, lext = len + 2 * (int)k.padlen;
+    double x0;
+    if (bwd)
+      x0 = a.f[(int64_t)(c0 + lcc) * a.ldf + lext - 1];
+    else if (a.x_f64)
+      x0 = ext_at(static_cast<const double*>(a.x) + (int64_t)k.row * a.ldx, len, (int)k.padlen, 0);
+    else
+      x0 = ext_at(static_cast<const float*>(a.x) + (int64_t)k.row * a.ldx, len, (int)k.padlen, 0);
+    L.z0 = sec[5] * x0;
+    L.z1 = sec[6] * x0;
+  } else {
+    load_tile(0, 0);
+  }
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    if (wave == 0) {
+      double* const row = sos_smem + ((t & 1) * C + lcc) * kSosRow;
+      if (t == 0)
+        sos_tile<true>(row, L);
+      else
+        sos_tile<false>(row, L);
+    } else {
+      if (t >= 1) flush_tile(t - 1, (t + 1) & 1);
+      if (t + 1 < ntiles) load_tile(t + 1, (t + 1) & 1);
+    }
+    __syncthreads();
+  }
+  if (wave == 1) flush_tile(ntiles - 1, (ntiles - 1) & 1);
+  if (bwd) {  // zeros past each clip's end
+    for (int c = 0; c < nc; ++c) {
+      double* const yr = a.y + (int64_t)a.clip[c0 + c].row * a.ldy;
+      for (int64_t j = (int64_t)a.clip[c0 + c].len + tid; j < a.ldy; j += 128) yr[j] = 0.0;
+    }
+  }
+}
+
+void sosfilt_pack_bank(const double* sos, const double* zi, int F, int Smax, double* bank) {
+  for (int i = 0; i < F * Smax; ++i) {
+    const double row[kSosBankRow] = {sos[i * 6 + 0], sos[i * 6 + 1], sos[i * 6 + 2], sos[i * 6 + 4], sos[i * 6 + 5], zi[i * 2 + 0], zi[i * 2 + 1]};
+    std::copy(row, row + kSosBankRow, bank + (size_t)i * kSosBankRow);
+  }
+}
+
+void launch_sosfiltfilt_bank(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* filter_index,
+                             const double* bank, int Smax, const int* sections, const int* padlens, double* f, int64_t ldf, double* y,
+                             int64_t ldy, hipStream_t s) {
+  SosBankArgs a{};
+  a.x = x;
+  a.f = f;  // the scratch is reused: the launches are ordered on the stream
+  a.y = y;
+  a.bank = bank;
+  a.ldx = ldx;
+  a.ldf = ldf;
+  a.ldy = ldy;
+  a.x_f64 = x_f64;
+  a.Smax = Smax;
+  for (int b0 = 0; b0 < B; b0 += kSosMaxClips) {
+    const int n = std::min(B - b0, kSosMaxClips);
+    int order[kSosMaxClips];
+    for (int i = 0; i < n; ++i) order[i] = b0 + i;
+    std::stable_sort(order, order + n, [&](int p, int q) { return sections[filter_index[p]] < sections[filter_index[q]]; });
+    int nblk = 0;
+    for (int j = 0; j < n; ++j) {
+      const int b = order[j], fi = filter_index[b], S = sections[fi];
+      VFX_CHECK(S >= 1 && S <= kSosMaxSections && S <= Smax, "sosfiltfilt bank: design %d has %d sections (1 .. %d)", fi, S,
+                std::min(Smax, kSosMaxSections));
+      a.clip[j] = SosClip{b, (int)lengths[b], (uint16_t)padlens[fi], (uint16_t)fi};
+      if (nblk == 0 || a.blk[nblk - 1].S != S || a.blk[nblk - 1].count == kSosBankBlockClips) {
+        VFX_CHECK(nblk < kSosMaxBlocks, "sosfiltfilt bank: more than %d blocks", kSosMaxBlocks);
+        a.blk[nblk++] = SosBlock{(uint8_t)S, (uint8_t)j, 0};
+      }
+      ++a.blk[nblk - 1].count;
+    }
+    for (int bwd = 0; bwd < 2; ++bwd) {
+      a.bwd = bwd;
+      hipLaunchKernelGGL(k_sosfilt_bank, dim3((unsigned)nblk), dim3(128), 0, s, a);
+      VFX_HIP(hipGetLastError());
+    }
+  }
+}
+
 }  // namespace vfx

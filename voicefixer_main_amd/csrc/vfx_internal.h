@@ -516,6 +516,18 @@ int sosfilt_clips_per_wave(int S);    // 4 rows of min(16 / S, 8) clips
 // Both passes of every clip; y[b, lengths[b] .. ldy) = 0.
 void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S, const double* zi,
                         int padlen, double* f, int64_t ldf, double* y, int64_t ldy, hipStream_t s);
+// The bank form: clip b takes design filter_index[b] of F designs, each with its own section count and padlen.
+constexpr int kSosMaxDesigns = 128;
+constexpr int kSosBankRow = 7;        // doubles per section of the device bank: b0 b1 b2 a1 a2 zi0 zi1
+constexpr int kSosMaxBlocks = kSosMaxClips / 4 + kSosMaxSections;  // a block takes 4 clips of ONE section count: <= 48 per launch
+// sos (F, Smax, 6), zi (F, Smax, 2) HOST -> bank (F, Smax, kSosBankRow) HOST, what the kernel reads from device memory
+void sosfilt_pack_bank(const double* sos, const double* zi, int F, int Smax, double* bank);
+// x, f, y, bank (sosfilt_pack_bank's, uploaded): device; lengths, filter_index (B), sections, padlens (F): HOST.  f as above with
+// ldf >= max(length + 2 padlen of the clip's design).  The caller has checked the indices, 1 <= sections[.] <= Smax <= 16 and
+// padlens[filter_index[b]] < lengths[b] <= min(ldx, ldy).  One launch pair per kSosMaxClips clips, whatever their section counts.
+void launch_sosfiltfilt_bank(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* filter_index,
+                             const double* bank, int Smax, const int* sections, const int* padlens, double* f, int64_t ldf, double* y,
+                             int64_t ldy, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // room-impulse-response convolution (reverb.hip): direct form on the f32-input MFMA
@@ -587,6 +599,27 @@ struct GrowBuffer {
   }
   GrowBuffer(const GrowBuffer&) = delete;
   GrowBuffer& operator=(const GrowBuffer&) = delete;
+};
+
+// A table of a call that is too large for a kernel-argument block: a device buffer of the handle that only grows, filled on the
+// call's stream from pinned host memory of the handle.  stage() hands out the pinned memory -- after waiting, on the host, for the
+// previous upload's copy to have read it --, upload() enqueues the copy and returns the device table for the launches that follow
+// on that stream.  (Calls on other streams take turns behind it: StreamTurn.)
+struct StagedUpload {
+  GrowBuffer dev;
+  char* host = nullptr;
+  size_t host_bytes = 0;
+  hipEvent_t copied = nullptr;
+  bool pending = false;
+  char* stage(vfx_handle* h, size_t bytes);
+  char* upload(size_t bytes, hipStream_t s);
+  StagedUpload() = default;
+  ~StagedUpload() {
+    if (host) (void)hipHostFree(host);
+    if (copied) (void)hipEventDestroy(copied);
+  }
+  StagedUpload(const StagedUpload&) = delete;
+  StagedUpload& operator=(const StagedUpload&) = delete;
 };
 
 // One launch of a profiled call (vfx_profile_*): HIP events around it, its work, and its row of the VFX_PROFILE_DUMP table.
@@ -784,7 +817,8 @@ struct vfx_handle {
   vfx::GrowBuffer scratch;   // the tensors between the plans of a varlen call (vfx_restore_gsr_varlen)
   vfx::GrowBuffer score_ws;  // vfx_audio_metrics' spectra and partial sums (<= kScoreWorkspaceBytes unless one clip needs more)
   vfx::GrowBuffer sos_ws;    // vfx_sosfiltfilt's forward pass over the extended clips (float64)
-  vfx::GrowBuffer mix_ws;    // vfx_mix_noise's per-clip peaks, level ratios and chunk sums
+  vfx::StagedUpload sos_bank;  // vfx_sosfiltfilt_bank's designs: coefficients and zi of every section (sosfilt_pack_bank)
+  vfx::GrowBuffer mix_ws;   // vfx_mix_noise's per-clip peaks, level ratios and chunk sums
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;

@@ -407,6 +407,55 @@ class Engine:
                    "vfx_sosfiltfilt")
         return y[0] if squeeze else y
 
+    MAX_SOS_DESIGNS = 128
+
+    def sosfiltfilt_bank(self, x, bank, filter_index=None, lengths=None):
+        """`sosfiltfilt` with a design per clip: row b is scipy.signal.sosfiltfilt(bank[filter_index[b]], clip b), bit for bit.
+        bank: a list of (S_f, 6) arrays, of any mixture of section counts (1 .. 16; at most 128 designs); filter_index: one index
+        per clip (default clip b takes design b, which needs len(bank) == B).  x, lengths and the result as in `sosfiltfilt`.  One
+        pair of launches takes the whole batch whatever its section counts.  ValueError, with SciPy's wording, for a malformed
+        design and for a clip that is not longer than ITS design's padlen (the message carries that padlen)."""
+        bank = [self._check_sos(sos) for sos in bank]
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        x = x.to(self.device).contiguous()
+        if x.dim() not in (1, 2):
+            raise ValueError("sosfiltfilt_bank: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
+        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "sosfiltfilt_bank")
+        F = len(bank)
+        if B == 0 or not 1 <= F <= self.MAX_SOS_DESIGNS:
+            raise ValueError("sosfiltfilt_bank: %d clips and %d designs (at most %d)" % (B, F, self.MAX_SOS_DESIGNS))
+        if filter_index is None:
+            if F != B:
+                raise ValueError("sosfiltfilt_bank: %d designs for %d clips and no filter_index" % (F, B))
+            filter_index = range(B)
+        filter_index = [int(v) for v in filter_index]
+        if len(filter_index) != B or any(not 0 <= f < F for f in filter_index):
+            raise ValueError("sosfiltfilt_bank: %d indices for %d clips, each must be in [0, %d)" % (len(filter_index), B, F))
+        padlens = [self.sosfiltfilt_padlen(sos) for sos in bank]
+        for n, f in zip(lengths, filter_index):
+            if n <= padlens[f]:
+                raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlens[f])
+        if max(lengths) > L:
+            raise ValueError("sosfiltfilt_bank: a clip of %d samples in rows of %d" % (max(lengths), L))
+        from scipy.signal import sosfilt_zi
+        sections = [sos.shape[0] for sos in bank]
+        Smax = max(sections)
+        sos_all = np.zeros((F, Smax, 6), dtype=np.float64)
+        zi_all = np.zeros((F, Smax, 2), dtype=np.float64)
+        for f, sos in enumerate(bank):
+            sos_all[f, :sections[f]] = sos
+            zi_all[f, :sections[f]] = sosfilt_zi(sos)
+        y = torch.empty((B, L), device=self.device, dtype=torch.float64)
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _lib.check(self.lib.vfx_sosfiltfilt_bank(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, (ctypes.c_int64 * B)(*lengths),
+                                                 (ctypes.c_int * B)(*filter_index), sos_all.ctypes.data_as(dbl),
+                                                 zi_all.ctypes.data_as(dbl), (ctypes.c_int * F)(*sections), (ctypes.c_int * F)(*padlens),
+                                                 F, Smax, _ptr(y), L, self._stream()), "vfx_sosfiltfilt_bank")
+        return y[0] if squeeze else y
+
     # ------------------------------------------------------------------ room-impulse-response convolution (MagicalEffects.reverb_rir)
     MAX_RIR_TAPS = 1 << 20
 

@@ -251,6 +251,166 @@ def bandpass_list(clips, lowcut, highcut, fs, order=5, _type="butter", engine=No
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# a filter per clip: what the training collator draws (dataloaders/data_module.py:14-70).  The IIR items of a call share
+# Engine.sosfiltfilt_bank launches whatever their designs (csrc/sosfilt.hip, k_sosfilt_bank).
+# ------------------------------------------------------------------------------------------------------------------
+def _per_clip(value, n, name):
+    """A scalar, or a sequence with one entry per clip -> list of n."""
+    if isinstance(value, str) or np.ndim(value) == 0:
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError("%s: %d entries for %d clips" % (name, len(value), n))
+    return value
+
+
+def _sosfiltfilt_each(clips, design_of, designs, engine, to_host):
+    """scipy.signal.sosfiltfilt(designs[design_of[i]], clips[i]) for every i of the dict `design_of`, batched by dtype and length
+    as `_sosfiltfilt_list` does; a batch's bank is the designs it uses.  -> {i: result}"""
+    eng = _engine_or_default(engine)
+    padlens = [eng.sosfiltfilt_padlen(sos) for sos in designs]
+    for i, d in design_of.items():
+        if clips[i].shape[0] <= padlens[d]:
+            raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlens[d])
+    lengths = [c.shape[0] for c in clips]
+    out = {}
+    for f32 in (True, False):
+        dtype = torch.float32 if f32 else torch.float64
+        for idx in _clips.batches([i for i in design_of if _clips.is_f32(clips[i]) == f32], lengths, MAX_BATCH):
+            lens = [lengths[i] for i in idx]
+            used = sorted({design_of[i] for i in idx})
+            y = eng.sosfiltfilt_bank(_clips.pad([clips[i] for i in idx], eng.device, dtype), [designs[d] for d in used],
+                                     filter_index=[used.index(design_of[i]) for i in idx], lengths=lens)
+            out.update(zip(idx, _clips.unpad(y, lens, to_host)))
+    return out
+
+
+def _filter_each(clips, cuts, fs, orders, types, engine, to_host):
+    """cuts[i]: (highcut,) -- `lowpass` -- or (lowcut, highcut) -- `bandpass` -- of clip i.  Every item is sorted to its path first,
+    so an error is raised before anything runs."""
+    _check_1d(clips)
+    band = len(cuts[0]) == 2 if cuts else False
+    nyq = 0.5 * fs
+    designs, keys, design_of, stft, hard = [], {}, {}, {}, []
+    for i, (cut, order, _type) in enumerate(zip(cuts, orders, types)):
+        iir = _iir_type(_type, order)
+        if iir:
+            key = (iir[0], iir[1]) + tuple(int(v) for v in cut)
+            if key not in keys:      # one design per distinct (name, order, cut-offs)
+                wn = [v / nyq for v in key[2:]]
+                keys[key] = len(designs)
+                designs.append(_design(iir[1], wn if band else wn[0], "band" if band else "low", iir[0], "bandpass" if band else "lowpass"))
+            design_of[i] = keys[key]
+        elif not band and _type in "stft":
+            stft.setdefault(cut[0], []).append(i)
+        elif not band and _type in "stft_hard":
+            hard.append(i)
+        else:
+            raise ValueError("Error: Unexpected filter type " + _type)
+    out = [None] * len(clips)
+    if design_of:
+        for i, y in _sosfiltfilt_each(clips, design_of, designs, engine, to_host).items():
+            out[i] = y
+    for highcut, idx in stft.items():
+        for i, y in zip(idx, _stft_list([clips[i] for i in idx], highcut / int(fs / 2), engine, to_host)):
+            out[i] = y
+    if hard:
+        eng = _engine_or_default(engine)
+        for i in hard:
+            y = stft_hard_lowpass_v0(_clips.as_numpy(clips[i]), lowpass_ratio=cuts[i][0] / int(fs / 2), engine=eng)
+            out[i] = y if to_host else _clips.to_device(y, eng.device)
+    return out
+
+
+def lowpass_each(clips, highcuts, fs, orders=5, types="butter", engine=None, to_host=True):
+    """`lowpass(clips[i], highcuts[i], fs, orders[i], types[i])` for every clip of a list -- exactly that function's result,
+    item by item, in the caller's order.  `highcuts`, `orders` and `types` are each a scalar or a sequence with one entry per clip;
+    per clip the 1-D check, the substring dispatch, int() of the cut-off and the order clamp are `lowpass`'s.  The IIR items are
+    designed once per distinct (name, order, cut-off) and go through Engine.sosfiltfilt_bank as padded batches of one dtype, ONE
+    launch pair per batch whatever its designs; "stft" items go through the device resampler grouped by cut-off (`lowpass_list`'s
+    rule for which), "stft_hard" items through `stft_hard_lowpass_v0`.  -> list: NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    n = len(clips)
+    highcuts = _per_clip(highcuts, n, "lowpass_each: highcuts")
+    return _filter_each(clips, [(h,) for h in highcuts], fs, _per_clip(orders, n, "lowpass_each: orders"),
+                        _per_clip(types, n, "lowpass_each: types"), engine, to_host)
+
+
+def bandpass_each(clips, lowcuts, highcuts, fs, orders=5, types="butter", engine=None, to_host=True):
+    """`bandpass(clips[i], lowcuts[i], highcuts[i], fs, orders[i], types[i])` for every clip of a list, as `lowpass_each` (IIR
+    types only)."""
+    clips = list(clips)
+    n = len(clips)
+    cuts = list(zip(_per_clip(lowcuts, n, "bandpass_each: lowcuts"), _per_clip(highcuts, n, "bandpass_each: highcuts")))
+    return _filter_each(clips, cuts, fs, _per_clip(orders, n, "bandpass_each: orders"), _per_clip(types, n, "bandpass_each: types"),
+                        engine, to_host)
+
+
+def draw_lowpass_params(n, low_pass_range, filter_order_range, filter_type, rng):
+    """The training collator's three draws per item, in its order (data_module.py:28-33): the cut-off int(U(lo // 2, hi // 2)), the
+    order int(U(o_lo, o_hi)), the type filter_type[int(U(0, len))].  -> (cutoffs, orders, filters), n entries each."""
+    cutoffs, orders, filters = [], [], []
+    for _ in range(n):
+        cutoffs.append(int(_uniform(int(low_pass_range[0] // 2), int(low_pass_range[1] // 2), rng)))
+        orders.append(int(_uniform(filter_order_range[0], filter_order_range[1], rng)))
+        filters.append(filter_type[int(_uniform(0, len(filter_type), rng))])
+    return cutoffs, orders, filters
+
+
+def lowpass_collate(batch, low_pass_range, filter_order_range, filter_type, fs, rng=None, engine=None, to_host=False):
+    """LowpassTrainCollator.__call__ (data_module.py:28-70) for a batch of dicts of (L, C) arrays: per item a cut-off, an order and
+    a type from `draw_lowpass_params`; `fname` keys pass through as lists; every other key is stacked as (B, L, 1) float32 from
+    channel 0.  For a key containing "vocals", then for one containing "noise", one chance = U(0, 1000) is drawn per item in item
+    order: vocals are always low-passed with the item's type, and again with "stft" when int(chance) is even; noise stays as it is
+    when int(chance) is even, otherwise it is low-passed with the item's type, and again with "stft" when int(chance) % 3 == 0.
+    All items of a key share ONE `lowpass_each` call, the "stft" follow-ups a second one; key + "_LR" is the (B, L, 1) float32
+    stack, every item exactly what the single-clip `lowpass` chain gives, rounded to float32.  -> dict of tensors on the engine's
+    device, or on the host (to_host).  Items of unequal length raise ValueError (the reference's torch.stack raises).  An
+    untouched noise item contributes its channel 0 (the reference stacks the whole (L, C) array, which only stacks with filtered
+    items when C = 1).  NOT mirrored: the reference's early return for an empty low_pass_range (lines 23-26) reads `ret[key]`
+    from an empty dict and can only raise; here such a range draws its one cut-off, as `_uniform` gives it."""
+    rng = rng if rng is not None else np.random.default_rng()
+    batch = list(batch)
+    cutoffs, orders, filters = draw_lowpass_params(len(batch), low_pass_range, filter_order_range, filter_type, rng)
+    eng = _engine_or_default(engine)
+    where = torch.device("cpu") if to_host else eng.device
+
+    def stack(key, rows):
+        if len({r.shape[0] for r in rows}) > 1:
+            raise ValueError("lowpass_collate: %s: items of %s samples do not stack" % (key, sorted({r.shape[0] for r in rows})))
+        return torch.stack([_clips.as_tensor(r).to(device=where, dtype=torch.float32) for r in rows])[..., None]
+
+    def each(rows, idx, types):      # rows[i] <- lowpass of rows[i], i in idx
+        pick = lambda v: [v[i] for i in idx]      # noqa: E731
+        ys = lowpass_each(pick(rows), pick(cutoffs), fs, pick(orders), types, engine=eng, to_host=to_host)
+        for i, y in zip(idx, ys):
+            rows[i] = y
+
+    ret = {}
+    for key in (batch[0].keys() if batch else ()):
+        if "fname" in key:
+            ret[key] = [x[key] for x in batch]
+            continue
+        clips = [x[key][..., 0] for x in batch]
+        ret[key] = stack(key, clips)
+        for word in ("vocals", "noise"):
+            if word not in key:
+                continue
+            chances = [int(_uniform(0, 1000, rng)) for _ in batch]
+            if word == "vocals":
+                first = list(range(len(batch)))
+                again = [i for i in first if chances[i] % 2 == 0]
+            else:
+                first = [i for i in range(len(batch)) if chances[i] % 2 != 0]
+                again = [i for i in first if chances[i] % 3 == 0]
+            rows = list(clips)
+            each(rows, first, [filters[i] for i in first])
+            each(rows, again, "stft")
+            ret[key + "_LR"] = stack(key + "_LR", rows)
+    return ret
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # dataloaders/augmentation/magical_effects.py:158-167
 # ------------------------------------------------------------------------------------------------------------------
 def reverb_rir(frames, rir):
