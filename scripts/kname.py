@@ -4,7 +4,8 @@ k_conv<BN, ELU, SPLIT, ABL, RING, HI>  ->  "k_conv<BN, ELU, SPLIT>" (+ " f16" fo
 k_resblock<C, NW, HI>                  ->  "k_resblock<C, NW>"      (+ " f16")
 k_resblock_w64<C, X16>                 ->  "k_resblock<C, 4> f16"
 k_resblock_r128<PAIR, X16>             ->  "k_resblock<128, 4> f16" / "k_resblock_pair<128, 4> f16"
-k_resblock_rw<NW, PAIR, X16>           ->  "k_resblock<64, NW> f16" / "k_resblock_pair<64, NW> f16"
+k_resblock_rw<PAIR>                    ->  "k_resblock<64, 8> f16" / "k_resblock_pair<64, 8> f16"  (the fp32 trunk of VFX_TUNE_F32_TRUNK)
+k_resblock_rw<NW, PAIR, X16[, HALO]>   ->  "k_resblock<64, NW> f16" / "k_resblock_pair<64, NW> f16"  (rounds 2 to 6: the profiles in profiles/)
 k_resblock_rw16<PAIR, HALO>            ->  "k_resblock<64, 8> f16" / "k_resblock_pair<64, 8> f16"
 (X16 = the fp16 trunk of round 4: same rows of the tables, the bench line's `dtype` names the trunk format)
 """
@@ -24,7 +25,9 @@ def short(n, width=40):
     if name == "k_resblock_r128":                        # C = 128, 16-bit mode: 4-wave blocks, x read once; <true>: a layer pair
         return "k_resblock_pair<128, 4> f16" if args and args[0] == "true" else "k_resblock<128, 4> f16"
     if name == "k_resblock_rw" and args:                 # C = 64, 16-bit mode: persistent, weights in registers
-        if len(args) >= 2 and args[1] == "true":         # two layers per launch
+        if len(args) == 1:                               # <PAIR>: 8 waves; true = two layers per launch
+            return "k_resblock_pair<64, 8> f16" if args[0] == "true" else "k_resblock<64, 8> f16"
+        if args[1] == "true":                            # <NW, PAIR, X16[, HALO]>, as the earlier profiles recorded it
             return "k_resblock_pair<64, %s> f16" % args[0]
         return "k_resblock<64, %s> f16" % args[0]
     if name == "k_resblock_rw16":                        # round 6: the same kernel with the lean tile loop (fp16 trunk); <PAIR, HALO>

@@ -885,6 +885,8 @@ def test_profile_kernel_names():
     assert short(ns + "k_resblock_rw<8, false, true>(vfx::ResBlockParams const*, int, int)") == "k_resblock<64, 8> f16"
     assert short(ns + "k_resblock_rw<8, true, true>(vfx::ResBlockParams const*, int, int)") == "k_resblock_pair<64, 8> f16"
     assert short(ns + "k_resblock_rw<8, false, false>(vfx::ResBlockParams const*, int, int)") == "k_resblock<64, 8> f16"
+    assert short(ns + "k_resblock_rw<false>(vfx::ResBlockParams const*, int, int)") == "k_resblock<64, 8> f16"
+    assert short(ns + "k_resblock_rw<true>(vfx::ResBlockParams const*, int, int)") == "k_resblock_pair<64, 8> f16"
     assert short(ns + "k_resblock_w64<256, true>(vfx::ResBlockParams const*)") == "k_resblock<256, 4> f16"
     assert short(ns + "k_resblock_w64<256, false>(vfx::ResBlockParams const*)") == "k_resblock<256, 4> f16"
     assert short(ns + "k_resblock_r128<false, true>(vfx::ResBlockParams const*)") == "k_resblock<128, 4> f16"

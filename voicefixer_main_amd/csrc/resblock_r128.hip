@@ -554,7 +554,6 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
     const bool have_y = p.y != nullptr, have_ya = p.ya != nullptr;
     int l31e = l31, lhe = lh;
     asm volatile("" : "+v"(l31e), "+v"(lhe));  // the epilogue's index math stays behind the last conv2
-#ifndef VFX_R128_DIRECT_STORES
     // Round 6: y leaves in FULL 128-byte lines.  Stored straight from the MFMA layout a 16-byte store instruction touches 32 rows with
     // 32 bytes each (it writes at 0.65-0.73 of the full-line rate, profiles/r06_c50_direct_store_cost.txt, and the epilogue of this
     // kernel is store-issue-bound: 5.7 k of a block's 27 k cycles).  A wave owns 64 couts = one whole line of each of its 64 positions:
@@ -563,7 +562,6 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
     constexpr int SROW = 144;
     const int sbase = wave_u * (64 * SROW);
     if (have_y) __syncthreads();
-#endif
 #pragma unroll
     for (int n = 0; n < WN; ++n) {
       const int ch = 2 * wn + n;
@@ -592,8 +590,6 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
             const u32x4 w = {s0[0], s1[0], s0[1], s1[1]};
 #ifdef VFX_ABL_NOSTORE  // timing-only build (wrong results): what the direct stores cost
             asm volatile("" : : "v"(w));
-#elif defined(VFX_R128_DIRECT_STORES)
-            __builtin_amdgcn_raw_buffer_store_b128(w, ry, (int)(rowoff + (unsigned)(16 * jp)), 0, 0);
 #else
             *reinterpret_cast<u32x4*>(lds + sbase + (a * 32 + l31e) * SROW + n * 64 + 16 * lhe + 16 * jp) = w;
 #endif
@@ -620,7 +616,7 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
         }
       }
     }
-#if !defined(VFX_R128_DIRECT_STORES) && !defined(VFX_ABL_NOSTORE)
+#ifndef VFX_ABL_NOSTORE
     if (have_y) {
       const int srow = lane >> 3, piece = lane & 7;
 #pragma unroll

@@ -306,7 +306,7 @@ struct ResBlockParams {
   // the residual added in fp32 in registers -- only what travels between two launches is rounded (saturation is flagged).
   // y may be NULL when only ya is consumed (the last layer of a stack in front of an upsampler).
   int x16;
-  int tile_m;       // h positions per tile: 0 = 128 (k_resblock, resblock_w64, resblock_r128); resblock_rw: 128 or 256
+  int tile_m;       // h positions per tile: 0 = 128 (k_resblock, resblock_w64, resblock_r128); resblock_rw: 256
   // Layer pair (resblock_rw.hip, PAIR): dil2 > 0 = a second layer (dilation dil2, weights w1b .. b2b, same slope) follows in the
   // same launch; y is ITS output, the first layer's output is never stored.
   int dil2;
