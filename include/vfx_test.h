@@ -4,7 +4,7 @@
  * NOT part of the drop-in boundary (include/vfx.h, libvfx.so): nothing here corresponds to a call the reference makes.  Each
  * entry point runs ONE kernel family of libvfx.so in isolation -- weights handed over in PyTorch layout on the host, packed on
  * the fly, the launch synchronised -- so that tests/test_gpu_kernels.py can compare it with a float64 torch expression of the
- * same operator.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
+ * same operator; vfx_op_voc_* and vfx_op_unet_piece run single launches exactly as the vocoder and ResUNet plans build them.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
  * handlers.py, dist.py, bench.py's timed path) never loads it.
  */
 #ifndef VFX_TEST_H_
@@ -102,6 +102,37 @@ int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const f
  * first and not the last, in precision mode `precision` with vfx_config.tuning = `tuning`): 1 = k_up16, 0 = the phased k_conv,
  * -1 = bad arguments. */
 int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, int precision, int tuning);
+
+/* The ResUNet plans' launches, one PIECE at a time, for tests/test_gpu_resunet_launches.py.  The piece is appended to a plan of its own by
+ * the member functions of the plan builder that vfx_resunet_mel / vfx_resunet_spec run (resunet.cpp: build_unet_piece -> TrunkBuilder::entry,
+ * conv_block, upsample, pool, add_prep_*, add_final), with the handle's own packed weights of `model` (VFX_MODEL_UNET_MEL / _SPEC,
+ * finalized), through PlanBuilder::add_conv / add_conv_phased / add_resblock: precision, tuning, kernel choice, split-K and its workspace
+ * are the product's.  The plan is bound to the handle's arena, filled with NaN patterns, given the caller's inputs, run and synchronised.
+ *   piece          inputs (device, channels-last fp32)            outputs
+ *   "entry"        (B, H, W)                                       (B, H, W, 32)     encoder_block1.conv_block1
+ *   "enc<l>.<j>", "bott", "after", "dec<d>.<j>" j = 2..4
+ *                  (B, H, W, Cin)                                  (B, H, W, Cout)   one ConvBlockRes
+ *   "dec<d>.1"     2 x (B, H, W, Cout): upsampled, skip            (B, H, W, Cout)   the two-source block behind the upsampler
+ *   "dec<d>.up"    (B, H, W, Cin)                                  (B, 2H, 2W + 1, Cout), arg = prune_w != 0: (B, 2H, 2W, Cout)
+ *   "pool"         (B, H, W, C), arg = C                           (B, H / 2, W / 2, C)
+ *   "prep_logmel"  (B, T = H, 128) linear mel                      (B, Tpad, 127), Tpad = T rounded up to 64; W is ignored
+ *   "prep_spec"    (B, T = H, 1025)                                (B, Tpad, 1024)
+ *   "final"        (B, Tpad, W, 32), then arg = 0: the linear mel (B, T = H, W + 1); arg = 1: cos, sin (B, T, W + 1)
+ *                                                                  arg = 0: log-mel (B, T, W + 1); arg = 1: re, im (B, T, W + 1)
+ * in / out: HOST arrays of nin / nout device pointers, in_n / out_n the float count of each tensor -- checked against the plan's buffers,
+ * a mismatch fails the call.  short_clip: PlanBuilder::short_clip (the split-K rule: 1 short clips, 0, < 0 long clips).  lens: NULL or
+ * HOST int[B] frames per clip (the prep pieces).  h_out (device, h_n floats) or NULL: where a block runs as two launches, the tensor
+ * between them -- *h_form = 1: conv1's ACTIVATED output LeakyReLU(bn2(.)) widened to fp32 from its stored operand form; 0: the entry
+ * block's raw fp32 conv1 output (k_conv_c1); -1: one launch, nothing written.  launches / cap / nlaunch: as vfx_plan_unet_piece. */
+int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, int B, int H, int W, int arg, int short_clip, const int* lens,
+                      const float* const* in, const int64_t* in_n, int nin, float* const* out, const int64_t* out_n, int nout, float* h_out,
+                      int64_t h_n, int* h_form, int* launches, int cap, int* nlaunch, void* stream);
+/* Host-only (no GPU, no handle, no weights): what the plan launches for that piece in precision mode `precision` with
+ * vfx_config.tuning = `tuning`.  *nlaunch = the number of launches; launches (NULL, or `cap` ints) receives, for those that fit, 6 ints
+ * each, in launch order: family (0 small kernel, 1 k_conv, 2 phased k_conv, 3 fused block, 4 fused entry block, 5 fused two-source
+ * block, 6 persistent C = 32 block), ksplit (1 = no split-K), activated output, bias, K segments, output channels. */
+int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches, int cap,
+                        int* nlaunch);
 
 /* The SSIM of vfx_audio_metrics alone (k_ssim_tiles + k_score_final): skimage structural_similarity(win_size=7) of the images
  * est[b], target[b] of (B, T, F) device tensors, clip b = its first rows[b] rows; rows HOST int[B], 7 <= rows[b] <= T, F >= 7

@@ -27,79 +27,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from launch_parity_f64 import U32, _act32, _act64, _act_bar, _bar, _check, _operand, _rand   # the shared operand forms and bounds
+
 pytestmark = pytest.mark.gpu
 
-U32 = 2.0 ** -24
 RES_SLOPE, UP_SLOPE = 0.01, 0.2
-
-
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g) * scale
-
-
-def _operand(t, p):
-    """float32 values -> the operand values the kernel multiplies, in float64."""
-    t = t.float()
-    if p == 2:
-        return t.clamp(-65504.0, 65504.0).half().double()
-    if p == 1:
-        hi = t.bfloat16()
-        lo = (t - hi.float()).bfloat16()
-        return hi.double() + lo.double()
-    return t.double()
-
-
-def _act32(t, act, slope):
-    t = t.float()
-    if act == 2:
-        return F.elu(t)
-    if act == 1:
-        return F.leaky_relu(t, slope)
-    return t
-
-
-def _act64(t, act, slope):
-    if act == 2:
-        return F.elu(t)
-    if act == 1:
-        return F.leaky_relu(t, slope)
-    return t
-
-
-def _products_factor(p):
-    return 3 if p == 1 else 1
-
-
-def _bar(ref, S, n, p, tol, extra=0.0):
-    """Per-element bound of a raw fp32 output (see the module docstring); extra = |bias| + |residual|."""
-    b = (n * _products_factor(p) + 2) * U32 * (S + extra)
-    if p == 1:
-        b = b + 2.0 ** -17 * S
-    cap = tol * max(1.0, float(ref.abs().max()))
-    return torch.minimum(b, torch.full_like(b, cap)), cap
-
-
-def _act_bar(ref_act, bar_y, slope_max, p, cap):
-    """Bound of an activated output: the raw bound through the activation (Lipschitz max(1, slope)), its fp32 rounding and the storage
-    rounding of the stored form."""
-    a = ref_act.abs()
-    b = bar_y * max(1.0, slope_max) + 4 * U32 * a
-    if p == 2:
-        e = torch.floor(torch.log2(torch.clamp(a + b, min=2.0 ** -24)))
-        b = b + 0.5 * 2.0 ** (torch.clamp(e, min=-14.0) - 10.0)
-    elif p == 1:
-        b = b + 2.0 ** -17 * (a + b)
-    return torch.minimum(b, torch.full_like(b, cap))
-
-
-def _check(got, ref, bar, what):
-    got = got.double()
-    assert torch.isfinite(got).all(), (what, "non-finite values inside the clips")
-    err = (got - ref).abs()
-    worst = (err / bar).max().item()
-    assert worst <= 1.0, (what, "max |err| / bar = %.3g at %s (err %.3g, bar %.3g)" %
-                          (worst, np.unravel_index(int((err / bar).argmax()), tuple(err.shape)), err.max().item(), bar.max().item()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 // ops_debug.cpp -- libvfx_test.so: kernel-level C entry points used by the parity tests (include/vfx_test.h).
-// They pack PyTorch-layout weights on the fly, run one kernel family of libvfx.so and synchronise.  Not part of the product
-// library: built into its own shared object that resolves the internals it uses from libvfx.so.
+// They pack PyTorch-layout weights on the fly, run one kernel family of libvfx.so and synchronise; vfx_op_voc_* and vfx_op_unet_piece
+// run single launches of the vocoder and ResUNet plans through the plans' own builder functions (vocoder.cpp, resunet.cpp) -- no
+// launch parameters of those plans are restated here.  Not part of the product library: built into its own shared object that
+// resolves the internals it uses from libvfx.so.
 #include <cmath>
 #include <cstring>
 
@@ -719,14 +721,14 @@ float* to_device_act(const vfx_handle* h, DeviceBlob& blob, const float* dx, siz
 }
 // bytes of an activated tensor of n elements in the handle's operand form
 size_t act_bytes(const vfx_handle* h, size_t n) { return h->cfg.precision == 2 ? n * 2 : n * 4; }
-// ... and back: the caller's fp32 tensor receives the stored values (fp16 widened, hi + lo, fp32), NaN patterns included
-void act_to_f32(const vfx_handle* h, const float* dact, size_t n, float* dy) {
+// ... and back: the caller's fp32 tensor receives the stored values (form 2: fp16 widened, 1: hi + lo, 0: fp32), NaN patterns included
+void act_to_f32(int form, const float* dact, size_t n, float* dy) {
   std::vector<float> hy(n);
-  if (h->cfg.precision == 2) {
+  if (form == 2) {
     std::vector<_Float16> hh(n);
     VFX_HIP(hipMemcpy(hh.data(), dact, n * sizeof(_Float16), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) hy[i] = (float)hh[i];
-  } else if (h->cfg.precision == 1) {
+  } else if (form == 1) {
     std::vector<uint16_t> q(2 * n);
     VFX_HIP(hipMemcpy(q.data(), dact, q.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) {
@@ -806,7 +808,7 @@ extern "C" int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, 
     VFX_HIP(hipMemcpy(d, &p, sizeof(p), hipMemcpyHostToDevice));
     launch_conv(p, d, s);
     VFX_HIP(hipStreamSynchronize(s));
-    if (dact) act_to_f32(h, dact, nout, ya);
+    if (dact) act_to_f32(h->cfg.precision, dact, nout, ya);
     if (used_up16) *used_up16 = p.up16;
   } catch (const vfx::Error&) {
     return 1;
@@ -839,7 +841,7 @@ extern "C" int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, in
                                         want_raw ? y : nullptr, dact, next_act, next_slope, upload_lens(sc.blob, lens, B), 1);
     run_voc_conv(h, p, sc.blob, s);
     VFX_HIP(hipStreamSynchronize(s));
-    if (dact) act_to_f32(h, dact, nout, ya);
+    if (dact) act_to_f32(h->cfg.precision, dact, nout, ya);
   } catch (const vfx::Error&) {
     return 1;
   }
@@ -876,6 +878,90 @@ extern "C" int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, in
   } catch (const vfx::Error&) {
     return -1;
   }
+}
+
+// ---- the ResUNet plans' launches, one piece at a time, built by the plan's own builder (resunet.cpp: build_unet_piece) -----------------
+extern "C" int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, int B, int H, int W, int arg, int short_clip, const int* lens,
+                                 const float* const* in, const int64_t* in_n, int nin, float* const* out, const int64_t* out_n, int nout,
+                                 float* h_out, int64_t h_n, int* h_form, int* launches, int cap, int* nlaunch, void* stream) {
+  try {
+    VFX_CHECK(h && piece && in && in_n && out && out_n && (model == VFX_MODEL_UNET_MEL || model == VFX_MODEL_UNET_SPEC),
+              "vfx_op_unet_piece: bad argument");
+    VFX_CHECK(h->unet[model], "vfx_op_unet_piece: the ResUNet weights of model %d are not finalized", model);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    Plan plan;
+    PlanBuilder pb{h, &plan, {}};
+    pb.short_clip = short_clip;
+    pb.lens_t = upload_lens(sc.blob, lens, B);
+    UNetPiece pc{};
+    pc.name = piece;
+    pc.B = B;
+    pc.H = H;
+    pc.W = W;
+    pc.arg = arg;
+    build_unet_piece(pb, *h->unet[model], pc);
+    // the caller's tensors must be the plan's buffers element for element: nothing below copies by any other count
+    VFX_CHECK(nin == pc.nin && nout == pc.nout, "vfx_op_unet_piece: '%s' has %d inputs and %d outputs", piece, pc.nin, pc.nout);
+    for (int i = 0; i < nin; ++i)
+      VFX_CHECK(in[i] && in_n[i] == pc.in_n[i], "vfx_op_unet_piece: input %d of '%s' has %lld floats", i, piece, (long long)pc.in_n[i]);
+    for (int i = 0; i < nout; ++i)
+      VFX_CHECK(out[i] && out_n[i] == pc.out_n[i], "vfx_op_unet_piece: output %d of '%s' has %lld floats", i, piece, (long long)pc.out_n[i]);
+    VFX_CHECK(pc.h_n == 0 || !h_out || h_n == pc.h_n, "vfx_op_unet_piece: the intermediate tensor of '%s' has %lld floats", piece,
+              (long long)pc.h_n);
+    plan.arena_bytes = pb.arena.high;
+    bind_plan(h, plan);
+    char* base = plan.bound_base;
+    // NaN patterns everywhere first (what no launch writes stays NaN, split-K workspace included), then the inputs
+    VFX_HIP(hipMemsetAsync(base, 0xff, plan.arena_bytes, s));
+    for (int i = 0; i < nin; ++i)
+      VFX_HIP(hipMemcpyAsync(base + pc.in_off[i], in[i], (size_t)pc.in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RunCtx ctx{s, {}, h->d_flags, nullptr};
+    plan.run(ctx);
+    for (int i = 0; i < nout; ++i)
+      VFX_HIP(hipMemcpyAsync(out[i], base + pc.out_off[i], (size_t)pc.out_n[i] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VFX_HIP(hipStreamSynchronize(s));
+    if (pc.h_n && h_out)
+      act_to_f32(pc.h_form == 1 && h->cfg.precision != 0 ? 1 : 0, reinterpret_cast<const float*>(base + pc.h_off), (size_t)pc.h_n, h_out);
+    if (h_form) *h_form = pc.h_n ? pc.h_form : -1;
+    const int n = describe_unet_launches(plan, launches, launches ? cap : 0);
+    if (nlaunch) *nlaunch = n;
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches,
+                                   int cap, int* nlaunch) {
+  try {
+    VFX_CHECK(piece && nlaunch && precision >= 0 && precision <= 2, "vfx_plan_unet_piece: bad argument");
+    vfx_handle hh;  // never touches a device: build_unet_piece only plans
+    VFX_CHECK(vfx_default_config(&hh.cfg) == 0, "no default config");
+    hh.cfg.precision = precision;
+    hh.cfg.tuning = tuning;
+    UNetWeights shapes = unet_weight_shapes();
+    static float dummy;  // never dereferenced (host-side planning only): a block with a shortcut has a bias
+    auto mark = [](ConvBlockW& w) { if (w.shortcut) w.bsc = &dummy; };
+    for (auto& lv : shapes.enc) for (auto& w : lv) mark(w);
+    for (auto& D : shapes.dec) for (auto& w : D.blocks) mark(w);
+    shapes.c1_bsc = &dummy;
+    Plan plan;
+    PlanBuilder pb{&hh, &plan, {}};
+    pb.short_clip = short_clip;
+    UNetPiece pc{};
+    pc.name = piece;
+    pc.B = B;
+    pc.H = H;
+    pc.W = W;
+    pc.arg = arg;
+    build_unet_piece(pb, shapes, pc);
+    *nlaunch = describe_unet_launches(plan, launches, launches ? cap : 0);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
 }
 
 // one column of k_score_final's (B, 9) output -> out (B)

@@ -60,12 +60,19 @@ void check_shape(const HostTensor& t, std::initializer_list<int64_t> shp, const 
   VFX_CHECK(t.shape == std::vector<int64_t>(shp), "tensor '%s' has an unexpected shape", name.c_str());
 }
 
-ConvBlockW load_block(const Staged& st, DeviceBlob& blob, const std::string& p, int cin, int cout, int nsrc) {
-  const bool split = st.h->cfg.precision != 0;
+ConvBlockW block_shape(int cin, int cout, int nsrc) {
   ConvBlockW w;
   w.cin = cin;
   w.cout = cout;
   w.nsrc = nsrc;
+  w.shortcut = cin != cout;
+  return w;
+}
+
+// `w` comes with its channel counts (unet_weight_shapes); the tensors of block `p` are checked against them, packed and uploaded
+void load_block(const Staged& st, DeviceBlob& blob, const std::string& p, ConvBlockW& w) {
+  const bool split = st.h->cfg.precision != 0;
+  const int cin = w.cin, cout = w.cout, nsrc = w.nsrc;
   std::vector<float> sc, sh;
   fold_bn(st, p + ".bn1", cin, sc, sh);
   w.bn1_scale = blob.upload(sc);
@@ -81,8 +88,7 @@ ConvBlockW load_block(const Staged& st, DeviceBlob& blob, const std::string& p, 
   if (cin >= kKC)
     for (int s = 0; s < nsrc; ++s) w.w1[s] = blob.upload(pack_conv(c1.data.data(), cout, cin, 3, 3, s * cs, cs, taps3x3(), split));
   w.w2 = blob.upload(pack_conv(c2.data.data(), cout, cout, 3, 3, 0, cout, taps3x3(), split));
-  w.shortcut = st.has(p + ".shortcut.weight");
-  VFX_CHECK(w.shortcut == (cin != cout), "%s: shortcut presence does not match channel counts", p.c_str());
+  VFX_CHECK(w.shortcut == st.has(p + ".shortcut.weight"), "%s: shortcut presence does not match channel counts", p.c_str());
   if (w.shortcut) {
     const HostTensor& ws = st.get(p + ".shortcut.weight");
     check_shape(ws, {cout, cin, 1, 1}, p + ".shortcut.weight");
@@ -91,24 +97,39 @@ ConvBlockW load_block(const Staged& st, DeviceBlob& blob, const std::string& p, 
         w.wsc[s] = blob.upload(pack_conv(ws.data.data(), cout, cin, 1, 1, s * cs, cs, {{0, 0}}, split));
     w.bsc = blob.upload(st.get(p + ".shortcut.bias").data);
   }
-  return w;
 }
 
 }  // namespace
 
-std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model) {
-  Staged st{h, model};
-  auto W = std::make_shared<UNetWeights>();
-  DeviceBlob& blob = h->blob;
+UNetWeights unet_weight_shapes() {
+  UNetWeights W;
   int cin = 1;
   for (int l = 0; l < 6; ++l) {
     const int c = kEncC[l];
+    for (int j = 0; j < 4; ++j) W.enc[l][j] = block_shape(j == 0 ? cin : c, c, 1);
+    cin = c;
+  }
+  W.bott = block_shape(384, 384, 1);
+  for (int d = 0; d < 6; ++d) {
+    DecoderW& D = W.dec[d];
+    D.cin = kDecIn[d];
+    D.cout = kDecOut[d];
+    for (int j = 0; j < 4; ++j) D.blocks[j] = block_shape(j == 0 ? 2 * D.cout : D.cout, D.cout, j == 0 ? 2 : 1);
+  }
+  W.after = block_shape(32, 32, 1);
+  return W;
+}
+
+std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model) {
+  Staged st{h, model};
+  auto W = std::make_shared<UNetWeights>(unet_weight_shapes());
+  DeviceBlob& blob = h->blob;
+  for (int l = 0; l < 6; ++l) {
     char p[64];
     for (int j = 0; j < 4; ++j) {
       snprintf(p, sizeof(p), "encoder_block%d.conv_block%d", l + 1, j + 1);
-      W->enc[l][j] = load_block(st, blob, p, j == 0 ? cin : c, c, 1);
+      load_block(st, blob, p, W->enc[l][j]);
     }
-    cin = c;
   }
   // Cin = 1 entry convs of encoder_block1.conv_block1
   {
@@ -125,11 +146,9 @@ std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model) {
     W->c1_wsc = blob.upload(st.get(p + ".shortcut.weight").data);  // (32,1,1,1)
     W->c1_bsc = blob.upload(st.get(p + ".shortcut.bias").data);
   }
-  W->bott = load_block(st, blob, "conv_block7", 384, 384, 1);
+  load_block(st, blob, "conv_block7", W->bott);
   for (int d = 0; d < 6; ++d) {
     DecoderW& D = W->dec[d];
-    D.cin = kDecIn[d];
-    D.cout = kDecOut[d];
     char p[64];
     snprintf(p, sizeof(p), "decoder_block%d", d + 1);
     std::vector<float> sc, sh;
@@ -149,10 +168,10 @@ std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model) {
     for (int j = 0; j < 4; ++j) {
       char q[96];
       snprintf(q, sizeof(q), "%s.conv_block%d", p, j + 2);
-      D.blocks[j] = load_block(st, blob, q, j == 0 ? 2 * D.cout : D.cout, D.cout, j == 0 ? 2 : 1);
+      load_block(st, blob, q, D.blocks[j]);
     }
   }
-  W->after = load_block(st, blob, "after_conv_block1", 32, 32, 1);
+  load_block(st, blob, "after_conv_block1", W->after);
   const HostTensor& fw = st.get("after_conv2.weight");
   check_shape(fw, {1, 32, 1, 1}, "after_conv2.weight");
   W->final_w = blob.upload(fw.data);
@@ -207,8 +226,9 @@ struct TrunkBuilder {
 
   // y = ConvBlockRes(x) where x = cat(srcs) (1 or 2 sources); frees nothing.
   // `pre_h` / `pre_sc`: first block of the network, conv1 and shortcut already computed (Cin = 1).
+  // `h_out` (build_unet_piece): receives the two-launch form's intermediate tensor (C = 0: one launch, h never leaves LDS).
   Act4 conv_block(const ConvBlockW& w, const Act4* srcs, int nsrc, const Act4* pre_h = nullptr,
-                  const Act4* pre_sc = nullptr) {
+                  const Act4* pre_sc = nullptr, Act4* h_out = nullptr) {
     const Act4& g = srcs ? srcs[0] : *pre_h;
     // Identity-shortcut blocks of the C = 32 / 64 levels run as ONE launch of k_resblock's 2-D mode: h stays in LDS, 402
     // instead of 872 HBM bytes per output pixel (VFX_TUNE_NO_FUSED_UNET: the two-launch form).
@@ -330,6 +350,7 @@ struct TrunkBuilder {
       p.residual = rel_ptr(srcs[0].off);
     }
     pb.add_conv(p);
+    if (h_out) *h_out = hbuf;
     if (!pre_h) pb.free(hbuf.off);
     return y;
   }
@@ -514,16 +535,13 @@ struct TrunkBuilder {
     return y;
   }
 
-  // Whole trunk from the single-channel input plane x1 (B, Tpad, W0) to the 32-channel tensor
-  // in front of after_conv2.
-  Act4 run(size_t x_off, int Tpad, int W0, bool both) {
+  // encoder_block1.conv_block1 (Cin = 1) on the single-channel plane at x_off: one launch of the fused block's entry form
+  // (resblock.hip, IN1), or -- fp32 mode, VFX_TUNE_NO_FUSED_UNET / VFX_TUNE_SMALL_2D_TILES -- k_conv_c1 (conv1 and the shortcut) +
+  // k_conv (conv2).  `h_out` (build_unet_piece): k_conv_c1's raw conv1 output of the two-launch form (C = 0: one launch).
+  Act4 entry(size_t x_off, int H, int W0, Act4* h_out = nullptr) {
     Plan* pl = pb.plan;
     const UNetWeights* wp = &Wt;
     const int Bc = B;
-    Act4 skips[6];
-    // encoder_block1.conv_block1 (Cin = 1): one launch of the fused block's entry form (resblock.hip, IN1), or -- fp32 mode,
-    // VFX_TUNE_NO_FUSED_UNET / VFX_TUNE_SMALL_2D_TILES -- k_conv_c1 (conv1 and the shortcut) + k_conv (conv2)
-    Act4 y;
     const int tun = pb.h->cfg.tuning;
 #ifdef VFX_ABL_NO_IN1  // measurement builds (scripts/build_variant.sh)
     const bool entry_fused = false;
@@ -531,7 +549,7 @@ struct TrunkBuilder {
     const bool entry_fused = !(tun & (VFX_TUNE_NO_FUSED_UNET | VFX_TUNE_SMALL_2D_TILES)) && pb.h->cfg.precision != 0;
 #endif
     if (entry_fused) {
-      y = make(Tpad, W0, 32);
+      Act4 y = make(H, W0, 32);
       const ConvBlockW& w = Wt.enc[0][0];
       ResBlockParams rp{};
       rp.geo2d = 1;
@@ -548,24 +566,32 @@ struct TrunkBuilder {
       rp.sh2 = w.bn2_shift;
       rp.slope = kSlope;
       rp.B = B;
-      rp.H = Tpad;
+      rp.H = H;
       rp.W = W0;
       rp.C = 32;
       pb.add_resblock(rp);
-    } else {
-    Act4 h1 = make(Tpad, W0, 32), sc1 = make(Tpad, W0, 32);
+      return y;
+    }
+    Act4 h1 = make(H, W0, 32), sc1 = make(H, W0, 32);
     {
       const size_t ho = h1.off, so = sc1.off;
       pl->ops.push_back([=](const RunCtx& c) {
-        launch_conv_c1(reinterpret_cast<const float*>(pl->bound_base + x_off), Bc, Tpad, W0, wp->c1_w, wp->c1_scale,
+        launch_conv_c1(reinterpret_cast<const float*>(pl->bound_base + x_off), Bc, H, W0, wp->c1_w, wp->c1_scale,
                        wp->c1_shift, kSlope, wp->c1_wsc, wp->c1_bsc, reinterpret_cast<float*>(pl->bound_base + ho),
                        reinterpret_cast<float*>(pl->bound_base + so), c.stream);
       });
     }
-    y = conv_block(Wt.enc[0][0], nullptr, 0, &h1, &sc1);
+    Act4 y = conv_block(Wt.enc[0][0], nullptr, 0, &h1, &sc1, h_out);
     pb.free(h1.off);
     pb.free(sc1.off);
-    }
+    return y;
+  }
+
+  // Whole trunk from the single-channel input plane x1 (B, Tpad, W0) to the 32-channel tensor
+  // in front of after_conv2.
+  Act4 run(size_t x_off, int Tpad, int W0, bool both) {
+    Act4 skips[6];
+    Act4 y = entry(x_off, Tpad, W0);
     for (int l = 0; l < 6; ++l) {
       for (int j = (l == 0 ? 1 : 0); j < 4; ++j) {
         Act4 y2 = conv_block(Wt.enc[l][j], &y, 1);
@@ -607,6 +633,37 @@ float* resolve(const Plan* pl, const RunCtx& c, const BufRef& b) {
   return b.ext ? c.ext[b.slot] : reinterpret_cast<float*>(pl->bound_base + b.off);
 }
 
+// The launches in front of and behind the trunk, as build_unet_mel / build_unet_spec and build_unet_piece append them.
+// A varlen batch (PlanBuilder::lens_t): every clip has its own frame count inside the SAME padded length -- the rows past it are
+// zeros like the network's own time padding (unet.py:75-77), so the trunk computes for each clip what its batch-of-one call
+// computes; no kernel of the trunk needs to know.
+void add_prep_logmel(PlanBuilder& pb, int B, int T, int Tpad, BufRef mel_linear, size_t x_off) {
+  Plan* pl = pb.plan;
+  const int* lens_t = pb.lens_t;
+  pl->ops.push_back([=](const RunCtx& c) {
+    launch_prep_logmel(resolve(pl, c, mel_linear), B, T, Tpad, reinterpret_cast<float*>(pl->bound_base + x_off), c.flags,
+                       c.stream, lens_t);
+  });
+}
+void add_prep_spec(PlanBuilder& pb, int B, int T, int Tpad, BufRef sp, size_t x_off) {
+  Plan* pl = pb.plan;
+  const int* lens_t = pb.lens_t;
+  pl->ops.push_back([=](const RunCtx& c) {
+    launch_prep_spec(resolve(pl, c, sp), B, T, Tpad, reinterpret_cast<float*>(pl->bound_base + x_off), c.stream, lens_t);
+  });
+}
+// mode 0: aux0 = the linear mel, out0 = the log-mel estimate; mode 1: aux0 / aux1 = cos / sin, out0 / out1 = re / im
+void add_final(PlanBuilder& pb, const UNetWeights& Wt, int B, int Tpad, int W0, int mode, int T, size_t y_off, BufRef aux0, BufRef aux1,
+               BufRef out0, BufRef out1) {
+  Plan* pl = pb.plan;
+  const UNetWeights* wp = &Wt;
+  pl->ops.push_back([=](const RunCtx& c) {
+    launch_final_1x1(reinterpret_cast<const float*>(pl->bound_base + y_off), B, Tpad, W0, wp->final_w, wp->final_b, mode, T,
+                     resolve(pl, c, aux0), mode ? resolve(pl, c, aux1) : nullptr, resolve(pl, c, out0),
+                     mode ? resolve(pl, c, out1) : nullptr, c.stream);
+  });
+}
+
 }  // namespace
 
 void build_unet_mel(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef logmel_out) {
@@ -614,24 +671,12 @@ void build_unet_mel(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef log
   const UNetWeights& Wt = *pb.h->unet[VFX_MODEL_UNET_MEL];
   const int Tpad = (T + 63) / 64 * 64, W0 = 127;
   pb.short_clip = Tpad <= 128 ? 1 : (Tpad >= 2048 ? -(Tpad / 1024) : 0);  // split-K rule of the deep levels (TapConvParams::short_clip)
-  Plan* pl = pb.plan;
-  // a varlen batch (PlanBuilder::lens_t): every clip has its own frame count inside the SAME padded length -- the rows past it
-  // are zeros like the network's own time padding (unet.py:75-77), so the trunk computes for each clip what its batch-of-one
-  // call computes; no kernel of the trunk needs to know
-  const int* lens_t = pb.lens_t;
   const size_t x_off = pb.alloc_f((int64_t)B * Tpad * W0);
-  pl->ops.push_back([=](const RunCtx& c) {
-    launch_prep_logmel(resolve(pl, c, mel_linear), B, T, Tpad, reinterpret_cast<float*>(pl->bound_base + x_off), c.flags,
-                       c.stream, lens_t);
-  });
+  add_prep_logmel(pb, B, T, Tpad, mel_linear, x_off);
   TrunkBuilder tb{pb, Wt, B};
   Act4 y = tb.run(x_off, Tpad, W0, /*both=*/false);
   pb.free(x_off);
-  const UNetWeights* wp = &Wt;
-  pl->ops.push_back([=](const RunCtx& c) {
-    launch_final_1x1(reinterpret_cast<const float*>(pl->bound_base + y.off), B, Tpad, W0, wp->final_w, wp->final_b, 0, T,
-                     resolve(pl, c, mel_linear), nullptr, resolve(pl, c, logmel_out), nullptr, c.stream);
-  });
+  add_final(pb, Wt, B, Tpad, W0, 0, T, y.off, mel_linear, BufRef{}, logmel_out, BufRef{});
   pb.free(y.off);
 }
 
@@ -640,21 +685,114 @@ void build_unet_spec(PlanBuilder& pb, int B, int T, BufRef sp, BufRef cosb, BufR
   const UNetWeights& Wt = *pb.h->unet[VFX_MODEL_UNET_SPEC];
   const int Tpad = (T + 63) / 64 * 64, W0 = 1024;
   pb.short_clip = Tpad <= 128 ? 1 : (Tpad >= 2048 ? -(Tpad / 1024) : 0);  // split-K rule of the deep levels (TapConvParams::short_clip)
-  Plan* pl = pb.plan;
-  const int* lens_t = pb.lens_t;  // a varlen batch: the rows past a clip's own frames are zeros (cf. build_unet_mel)
   const size_t x_off = pb.alloc_f((int64_t)B * Tpad * W0);
-  pl->ops.push_back([=](const RunCtx& c) {
-    launch_prep_spec(resolve(pl, c, sp), B, T, Tpad, reinterpret_cast<float*>(pl->bound_base + x_off), c.stream, lens_t);
-  });
+  add_prep_spec(pb, B, T, Tpad, sp, x_off);
   TrunkBuilder tb{pb, Wt, B};
   Act4 y = tb.run(x_off, Tpad, W0, /*both=*/true);
   pb.free(x_off);
-  const UNetWeights* wp = &Wt;
-  pl->ops.push_back([=](const RunCtx& c) {
-    launch_final_1x1(reinterpret_cast<const float*>(pl->bound_base + y.off), B, Tpad, W0, wp->final_w, wp->final_b, 1, T,
-                     resolve(pl, c, cosb), resolve(pl, c, sinb), resolve(pl, c, re_out), resolve(pl, c, im_out), c.stream);
-  });
+  add_final(pb, Wt, B, Tpad, W0, 1, T, y.off, cosb, sinb, re_out, im_out);
   pb.free(y.off);
+}
+
+// One piece of the plans above on its own (vfx_internal.h, UNetPiece): the SAME member functions TrunkBuilder::run calls and the same
+// add_prep_* / add_final, over buffers of the piece's own in the arena.
+void build_unet_piece(PlanBuilder& pb, const UNetWeights& Wt, UNetPiece& pc) {
+  const std::string name = pc.name ? pc.name : "";
+  const int B = pc.B, H = pc.H, W = pc.W;
+  VFX_CHECK(B > 0 && H > 0 && W > 0, "unet piece: bad shape");
+  TrunkBuilder tb{pb, Wt, B};
+  pc.nin = pc.nout = 0;
+  pc.h_n = 0;
+  pc.h_form = 0;
+  auto input = [&](int h, int w, int c) {
+    Act4 a = tb.make(h, w, c);
+    pc.in_off[pc.nin] = a.off;
+    pc.in_n[pc.nin++] = (int64_t)B * h * w * c;
+    return a;
+  };
+  auto output = [&](const Act4& a) {
+    pc.out_off[pc.nout] = a.off;
+    pc.out_n[pc.nout++] = (int64_t)B * a.H * a.W * a.C;
+  };
+  auto intermediate = [&](const Act4& hb, int form) {
+    if (hb.C == 0) return;
+    pc.h_off = hb.off;
+    pc.h_n = (int64_t)B * hb.H * hb.W * hb.C;
+    pc.h_form = form;
+  };
+  auto block = [&](const ConvBlockW& w) {
+    Act4 srcs[2], hb;
+    for (int s = 0; s < w.nsrc; ++s) srcs[s] = input(H, W, w.cin / w.nsrc);
+    output(tb.conv_block(w, srcs, w.nsrc, nullptr, nullptr, &hb));
+    intermediate(hb, 1);
+  };
+  int l = 0, j = 0;
+  char extra = 0;
+  if (name == "entry") {
+    Act4 x = input(H, W, 1), hb;
+    output(tb.entry(x.off, H, W, &hb));
+    intermediate(hb, 0);
+  } else if (name == "bott") {
+    block(Wt.bott);
+  } else if (name == "after") {
+    block(Wt.after);
+  } else if (sscanf(name.c_str(), "enc%d.%d%c", &l, &j, &extra) == 2 && l >= 1 && l <= 6 && j >= 1 && j <= 4 && !(l == 1 && j == 1)) {
+    block(Wt.enc[l - 1][j - 1]);
+  } else if (sscanf(name.c_str(), "dec%d.%d%c", &l, &j, &extra) == 2 && l >= 1 && l <= 6 && j >= 1 && j <= 4) {
+    block(Wt.dec[l - 1].blocks[j - 1]);
+  } else if (sscanf(name.c_str(), "dec%d.u%c", &l, &extra) == 2 && extra == 'p' && name.size() == 7 && l >= 1 && l <= 6) {
+    const DecoderW& D = Wt.dec[l - 1];
+    output(tb.upsample(D, input(H, W, D.cin), pc.arg != 0));
+  } else if (name == "pool") {
+    VFX_CHECK(pc.arg > 0 && pc.arg % 4 == 0 && H >= 2 && W >= 2, "unet piece: pool needs C %% 4 == 0 and an image of 2 x 2 or more");
+    output(tb.pool(input(H, W, pc.arg)));
+  } else if (name == "prep_logmel" || name == "prep_spec") {  // H = T frames; W is the model's own
+    const bool mel = name == "prep_logmel";
+    const int T = H, Tpad = (T + 63) / 64 * 64, W0 = mel ? 127 : 1024;
+    Act4 in = input(T, W0 + 1, 1);
+    Act4 x = tb.make(Tpad, W0, 1);
+    BufRef src;
+    src.off = in.off;
+    if (mel) add_prep_logmel(pb, B, T, Tpad, src, x.off);
+    else add_prep_spec(pb, B, T, Tpad, src, x.off);
+    output(x);
+  } else if (name == "final") {  // H = T frames, W = the trunk's width; arg = mode
+    const int T = H, Tpad = (T + 63) / 64 * 64, mode = pc.arg;
+    VFX_CHECK(mode == 0 || mode == 1, "unet piece: final has modes 0 and 1");
+    Act4 y = input(Tpad, W, 32);
+    BufRef aux[2], out[2];
+    for (int k = 0; k <= mode; ++k) aux[k].off = input(T, W + 1, 1).off;
+    for (int k = 0; k <= mode; ++k) {
+      Act4 o = tb.make(T, W + 1, 1);
+      out[k].off = o.off;
+      output(o);
+    }
+    add_final(pb, Wt, B, Tpad, W, mode, T, y.off, aux[0], aux[1], out[0], out[1]);
+  } else {
+    VFX_CHECK(false, "unet piece: unknown piece '%s'", name.c_str());
+  }
+}
+
+// family, ksplit, activated output, bias, segments, output channels of every launch of `plan` (kUNetLaunchInts each); the plans of
+// build_unet_piece run their small kernels first, then their fused blocks or convolutions
+int describe_unet_launches(const Plan& plan, int* out, int cap) {
+  int n = 0;
+  auto put = [&](int fam, int ks, int act, int bias, int nseg, int cout) {
+    if (out && (n + 1) * kUNetLaunchInts <= cap) {
+      const int v[kUNetLaunchInts] = {fam, ks, act, bias, nseg, cout};
+      std::copy(v, v + kUNetLaunchInts, out + n * kUNetLaunchInts);
+    }
+    ++n;
+  };
+  const size_t small = plan.ops.size() - plan.host_rb.size() - plan.host_params.size();
+  for (size_t i = 0; i < small; ++i) put(UNET_LAUNCH_SMALL, 1, 0, 0, 0, 0);
+  for (const ResBlockParams& q : plan.host_rb)
+    put(q.in1 ? UNET_LAUNCH_BLOCK_IN1 : (q.two_src ? UNET_LAUNCH_BLOCK_TWO_SRC : (block2d32_ok(q) ? UNET_LAUNCH_BLOCK2D32 : UNET_LAUNCH_BLOCK)),
+        1, 0, q.bsc != nullptr, q.two_src ? 2 : 1, q.C);
+  for (const TapConvParams& q : plan.host_params)
+    put(q.nphase > 1 ? UNET_LAUNCH_CONV_PHASED : UNET_LAUNCH_CONV, std::max(q.ksplit, 1), q.out_act != nullptr, q.bias != nullptr,
+        q.nseg, q.Cout);
+  return n;
 }
 
 }  // namespace vfx

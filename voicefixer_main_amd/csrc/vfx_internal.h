@@ -848,6 +848,36 @@ struct BufRef {
 };
 void build_unet_mel(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef logmel_out);
 void build_unet_spec(PlanBuilder& pb, int B, int T, BufRef sp, BufRef cosb, BufRef sinb, BufRef re_out, BufRef im_out);
+// One piece of a ResUNet plan on its own, for libvfx_test.so (vfx_op_unet_piece, vfx_plan_unet_piece): appended by the member
+// functions of the plan builder that build_unet_mel / build_unet_spec run (resunet.cpp), over input and output buffers of the
+// piece's own in the arena, with pb's short_clip and lens_t.  name: "entry" (encoder_block1.conv_block1 on a (B, H, W) plane);
+// "enc<l>.<j>", "bott", "after", "dec<d>.<j>" (j = 1: the two-source block behind the upsampler) = one ConvBlockRes on (B, H, W, Cin)
+// sources; "dec<d>.up" = the upsampler (arg = prune_w) -> (B, 2H, 2W [+ 1], Cout); "pool" (arg = C); "prep_logmel" / "prep_spec"
+// (H = T frames: (B, T, 128 / 1025) -> (B, Tpad, 127 / 1024)); "final" (H = T, W = the trunk's width, arg = mode: inputs the trunk's
+// (B, Tpad, W, 32) output and the one (mode 0) or two (B, T, W + 1) planes of the epilogue -> one or two (B, T, W + 1) planes).
+struct UNetPiece {
+  const char* name;
+  int B, H, W, arg;
+  // filled by build_unet_piece: arena byte offsets and float counts of the buffers
+  int nin, nout;
+  size_t in_off[3], out_off[2];
+  int64_t in_n[3], out_n[2];
+  // the tensor between the two launches of a block's two-launch form (h_n = 0: there is none).  h_form 1: the ACTIVATED operand form
+  // conv1 stores for conv2 (TapConvParams::out_act); 0: raw fp32 (the entry block's k_conv_c1)
+  size_t h_off;
+  int64_t h_n;
+  int h_form;
+};
+void build_unet_piece(PlanBuilder& pb, const UNetWeights& Wt, UNetPiece& piece);
+UNetWeights unet_weight_shapes();  // the channel counts of every block, no tensors: what build_unet_weights fills (host-only planning)
+// What a piece's plan launches, in order: kUNetLaunchInts ints per launch = family (UNetLaunchFamily), ksplit (1 = none), activated
+// output, bias, K segments, output channels.  Returns the number of launches; writes those that fit `cap` ints.
+enum UNetLaunchFamily {
+  UNET_LAUNCH_SMALL = 0, UNET_LAUNCH_CONV = 1, UNET_LAUNCH_CONV_PHASED = 2, UNET_LAUNCH_BLOCK = 3, UNET_LAUNCH_BLOCK_IN1 = 4,
+  UNET_LAUNCH_BLOCK_TWO_SRC = 5, UNET_LAUNCH_BLOCK2D32 = 6
+};
+constexpr int kUNetLaunchInts = 6;
+int describe_unet_launches(const Plan& plan, int* out, int cap);
 void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_out, const BufRef* peak = nullptr);
 // bi_gru / dnn Generator.forward: linear mel (B,T,128) -> log-mel (B,T,128); pb.lens_t (frames per clip) or all T
 void build_analysis_mel(PlanBuilder& pb, int model, int B, int T, BufRef mel_linear, BufRef logmel_out);

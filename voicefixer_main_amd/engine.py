@@ -796,6 +796,70 @@ class Engine:
             "vfx_op_voc_final")
         return wav
 
+    # the ResUNet plans' launches, one piece at a time, built by the plan's own builder (include/vfx_test.h: vfx_op_unet_piece)
+    UNET_LAUNCH_FAMILIES = ("small", "k_conv", "k_conv_phased", "k_resblock", "k_resblock_in1", "k_resblock_two_src", "k_block2d32")
+
+    @staticmethod
+    def _unet_launches(buf, n):
+        keys = ("family", "ksplit", "out_act", "bias", "nseg", "cout")
+        rows = [dict(zip(keys, buf[6 * i:6 * i + 6])) for i in range(n)]
+        for r in rows:
+            r["family"] = Engine.UNET_LAUNCH_FAMILIES[r["family"]]
+        return rows
+
+    @staticmethod
+    def _unet_piece_out_shapes(piece, in_shapes, arg):
+        B, H, W = in_shapes[0][:3]
+        if piece == "entry":
+            return [(B, H, W, 32)]
+        if piece.endswith(".up"):
+            cout = {1: 384, 2: 384, 3: 256, 4: 128, 5: 64, 6: 32}[int(piece[3])]
+            return [(B, 2 * H, 2 * W if arg else 2 * W + 1, cout)]
+        if piece == "pool":
+            return [(B, H // 2, W // 2, in_shapes[0][3])]
+        if piece in ("prep_logmel", "prep_spec"):
+            return [(B, (H + 63) // 64 * 64, W - 1)]
+        if piece == "final":
+            return [tuple(in_shapes[1])] * (2 if arg else 1)
+        if piece.startswith("dec") and piece.endswith(".1"):
+            return [tuple(in_shapes[0])]
+        cout = {"enc2.1": 64, "enc3.1": 128, "enc4.1": 256, "enc5.1": 384}.get(piece, in_shapes[0][3])
+        return [(B, H, W, cout)]
+
+    def op_unet_piece(self, piece, inputs, arg=0, short_clip=0, lens=None, model=MODEL_UNET_MEL):
+        """One piece of the ResUNet plan of `model` on device tensors -> (outputs, h, launches).  inputs: the piece's channels-last
+        tensors (include/vfx_test.h); outputs start as NaN.  h: the tensor between the two launches of a block's two-launch form,
+        widened to fp32, as ("act" | "raw", tensor), or None for a single launch.  launches: as plan_unet_piece.  For "final",
+        inputs[0] is the trunk's (B, Tpad, W, 32) output and the frame count is inputs[1]'s."""
+        xs = [_dev_f32(x, self.device) for x in inputs]
+        shapes = [tuple(x.shape) for x in xs]
+        outs = [torch.full(sh, float("nan"), device=self.device) for sh in self._unet_piece_out_shapes(piece, shapes, arg)]
+        if piece == "final":
+            B, H, W = shapes[1][0], shapes[1][1], shapes[0][2]
+        else:
+            B, H, W = shapes[0][:3]
+        hbuf = torch.full(outs[0].shape, float("nan"), device=self.device)
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        pin = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+        pout = (ctypes.c_void_p * len(outs))(*[y.data_ptr() for y in outs])
+        nin = (ctypes.c_int64 * len(xs))(*[x.numel() for x in xs])
+        nout = (ctypes.c_int64 * len(outs))(*[y.numel() for y in outs])
+        form, n, buf = ctypes.c_int(-1), ctypes.c_int(0), (ctypes.c_int * 48)()
+        _lib.check(_lib.load_test().vfx_op_unet_piece(
+            self.h, int(model), piece.encode(), B, H, W, int(arg), int(short_clip), _hptr(ln), pin, nin, len(xs), pout, nout, len(outs),
+            _ptr(hbuf), hbuf.numel(), ctypes.byref(form), buf, 48, ctypes.byref(n), self._stream()), "vfx_op_unet_piece")
+        h = None if form.value < 0 else (("raw", "act")[form.value], hbuf)
+        return outs, h, self._unet_launches(buf, min(n.value, 8))
+
+    @staticmethod
+    def plan_unet_piece(piece, B, H, W, arg=0, short_clip=0, precision=1, tuning=0):
+        """Host-only: the launches the ResUNet plan builds for `piece` over (B, H, W): a list of dicts with family (one of
+        UNET_LAUNCH_FAMILIES), ksplit (1 = no split-K), out_act, bias, nseg, cout.  Needs no GPU."""
+        n, buf = ctypes.c_int(0), (ctypes.c_int * 48)()
+        _lib.check(_lib.load_test().vfx_plan_unet_piece(piece.encode(), B, H, W, int(arg), int(short_clip), int(precision), int(tuning),
+                                                        buf, 48, ctypes.byref(n)), "vfx_plan_unet_piece")
+        return Engine._unet_launches(buf, min(n.value, 8))
+
     def op_ssim(self, est, target, rows=None):
         """The SSIM kernels of audio_metrics alone: (B, T, F) images, image b = its first rows[b] rows -> (B,) float64."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
