@@ -167,6 +167,15 @@ int vfx_mel_project(vfx_handle* h, const float* sp, int64_t rows, float* mel, vo
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav,
               void* stream);
 
+/* stft_hard_lowpass_v0 (tools/dsp/lowpass.py:21-33) of a padded batch of clips in ONE launch: STFT (eps = 1e-8) -> the bins from
+ * cut_bins[b] up set to zero -> ISTFT to the clip's length, with no spectrum in memory.  wav (B, L) device, clip b = the first
+ * lengths[b] samples of row b; lengths, cut_bins: HOST arrays int[B], n_fft/2 < lengths[b] <= L (reflect padding at the clip's OWN
+ * end), cut_bins[b] >= 0 (0: an all-zero clip; 1025 and above: nothing masked).  out (B, L) device, zeros from lengths[b] on; it must
+ * not overlap wav.  Row b is bit for bit vfx_istft of (sp * cos, sp * sin), sp / cos / sin = vfx_stft_mel of the clip alone with
+ * sp[..., cut_bins[b]:] = 0 and each product rounded to float32; it does not depend on the batch.  Fails, launching nothing, for a
+ * NULL pointer, B <= 0, a length outside (n_fft/2, L], a negative cut or overlapping buffers. */
+int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* lengths, const int* cut_bins, float* out, void* stream);
+
 /* Generator.forward of models/gsr_voicefixer.py:86-91 with the mel ResUNet
  * (models/components/unet.py:60-103): linear mel (B, T, 128) >= 0 -> log10 mel (B, T, 128). */
 int vfx_resunet_mel(vfx_handle* h, const float* mel_linear, int B, int T, float* logmel_out,

@@ -51,6 +51,7 @@ SIGNATURES = {
     "vfx_stft_phase": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "vfx_mel_project": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "vfx_istft": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vfx_stft_lowpass": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "vfx_resample_out_len": (c_int64, [c_int64, c_int, c_int]),
     "vfx_resample_window": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "vfx_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_int,

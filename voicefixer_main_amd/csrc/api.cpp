@@ -254,6 +254,32 @@ int vfx_stft_phase(vfx_handle* h, const float* wav, int B, int L, float* sp, flo
   VFX_API_END
 }
 
+int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* lengths, const int* cut_bins, float* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(wav && lengths && cut_bins && out && B > 0 && L > 0, "vfx_stft_lowpass: bad argument");
+  VFX_CHECK(h->cfg.n_fft == 2048, "vfx_stft_lowpass: needs the 44.1 kHz front end (n_fft 2048)");
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] > h->cfg.n_fft / 2 && lengths[b] <= L,
+              "vfx_stft_lowpass: clip %d has %d samples (need n_fft/2 = %d < length <= L = %d: reflect padding)", b, lengths[b],
+              h->cfg.n_fft / 2, L);
+    VFX_CHECK(cut_bins[b] >= 0, "vfx_stft_lowpass: clip %d has cut-off bin %d (need >= 0)", b, cut_bins[b]);
+  }
+  // (compared as integers: the two ranges of B * L floats)
+  const uintptr_t w0 = reinterpret_cast<uintptr_t>(wav), o0 = reinterpret_cast<uintptr_t>(out);
+  const uintptr_t bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float);
+  VFX_CHECK(o0 + bytes <= w0 || w0 + bytes <= o0, "vfx_stft_lowpass: out overlaps wav (a workgroup reads samples its neighbours write)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_l = h->lens_row(LENS_LOWPASS_SAMPLES);
+  int* const d_c = h->lens_row(LENS_LOWPASS_CUT);
+  for (int b0 = 0; b0 < B; b0 += kMaxVarlenClips) {  // (a clip's samples do not depend on the launch it is in)
+    const int n = std::min(kMaxVarlenClips, B - b0);
+    launch_set_frames(d_l, lengths + b0, n, s);
+    launch_set_frames(d_c, cut_bins + b0, n, s);
+    launch_stft_lowpass(h->fe, wav + (int64_t)b0 * L, n, L, h->cfg.hop, d_l, d_c, out + (int64_t)b0 * L, s);
+  }
+  VFX_API_END
+}
+
 int vfx_mel_project(vfx_handle* h, const float* sp, int64_t rows, float* mel, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(sp && mel && rows > 0, "bad argument");

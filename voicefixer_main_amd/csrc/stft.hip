@@ -29,6 +29,12 @@
 //   torchlibrosa ISTFT semantics (see oracle/dsp.py): `y[:, n_fft//2 : n_fft//2 + length]`.
 #include "vfx_internal.h"
 
+// Floating-point contraction is OFF in this file: every fused multiply-add below is written as fmaf.  Left to itself the compiler
+// fuses a * b + c where it sees fit, and what it sees depends on the kernel around the expression (which operations the
+// vectoriser paired, what a product feeds into): the same source rounds differently in two kernels.  k_stft_lowpass has to give
+// bit for bit what k_stft_mel followed by k_istft give, so the arithmetic they share is pinned down here, once.
+#pragma clang fp contract(off)
+
 namespace vfx {
 
 constexpr int NFFT = 2048;
@@ -37,7 +43,7 @@ constexpr int NBINS = NC + 1;    // 1025
 constexpr int NMEL = 128;
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+  return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
 
 // In-place (register) radix-4 butterfly.  SIGN = -1: forward (e^{-i}), +1: inverse.
@@ -183,6 +189,32 @@ __device__ __forceinline__ float2 rtw_of(float2 lane_w, int m) {
   return cmul(lane_w, make_float2(C[m], -S[m]));
 }
 
+// v[m] = A[lane + 64 m] (natural order) -> pn[m] = A[1024 - (lane + 64 m)], through the wave's LDS buffer: what the real-FFT
+// untangle (A = Z) and the Hermitian pack (A = X) pair a bin with.
+// A[1024 - (lane + 64 m)] = A[(64 - lane) + 64 (15 - m)]; lane 0: A[64 (16 - m)], and its m = 0 reads A[1024] from the spare element
+// behind the buffer (zw[ZP - 1]): whatever the caller put there, or the caller overwrites pn[0].  On return zw is free.
+__device__ __forceinline__ void mirror_bins(const float2 (&v)[16], float2 (&pn)[16], float2* zw, int lane) {
+  float2* const nat = zw + lane + (lane >> 4);  // A[lane + 64 m] -> + 68 m
+#pragma unroll
+  for (int m = 0; m < 16; ++m) nat[68 * m] = v[m];
+  wave_sync();
+  const int jp = 64 - lane;
+  const float2* const par = lane == 0 ? zw + 68 : zw + jp + (jp >> 4);
+#pragma unroll
+  for (int m = 0; m < 16; ++m) pn[m] = par[68 * (15 - m)];
+  wave_sync();
+}
+
+// real-FFT untangle of one bin: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[N-k]) / 2, O = (Z[k] - conj Z[N-k]) / (2i), and its
+// magnitude, clamped on the POWER (fDomainHelper.py:62); v_sqrt_f32 (1 ulp) instead of the IEEE expansion
+__device__ __forceinline__ void untangle_bin(float2 zk, float2 znk, float2 wk, float eps, float& re, float& im, float& mag) {
+  const float2 o = make_float2(0.5f * (zk.y + znk.y), -0.5f * (zk.x - znk.x));
+  const float2 wo = cmul(wk, o);
+  re = fmaf(0.5f, zk.x + znk.x, wo.x);  // E + W^k O
+  im = fmaf(0.5f, zk.y - znk.y, wo.y);
+  mag = __builtin_amdgcn_sqrtf(fmaxf(fmaf(im, im, re * re), eps));
+}
+
 // SPEC: the launch writes sp / cos / sin (any of them); false = the mel-only front-end of the restore path
 template <bool SPEC>
 __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_mel(const float* __restrict__ wav, int L, int T,
@@ -266,36 +298,21 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_mel(const float* __
     }
     if (t + 1 < t_end) load_frame(x, L, t + 1, hop, lane, xin);  // in flight during this frame's FFT
     wfft1024<-1>(v, zw, twl, lane);
-    // natural order to LDS: the untangle pairs Z[k] with Z[1024 - k], which another lane holds
-    float2* const nat = zw + lane + (lane >> 4);  // Z[lane + 64 m] -> + 68 m
-#pragma unroll
-    for (int m = 0; m < 16; ++m) nat[68 * m] = v[m];
-    wave_sync();
-    // Z[1024 - (lane + 64 m)] = Z[(64 - lane) + 64 (15 - m)]; lane 0: Z[64 (16 - m)], and Z[1024] = Z[0] is its own v[0]
-    // (its read of m = 0 lands on the spare element behind the buffer)
-    const int jp = 64 - lane;
-    const float2* const par = lane == 0 ? zw + 68 : zw + jp + (jp >> 4);
+    // the untangle pairs Z[k] with Z[1024 - k], which another lane holds; Z[1024] = Z[0] is lane 0's own v[0]
     float2 zn[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) zn[m] = par[68 * (15 - m)];
+    mirror_bins(v, zn, zw, lane);  // zw is free: the magnitudes go over it
     if (lane == 0) zn[0] = v[0];
-    wave_sync();  // zw is free: the magnitudes go over it
     __builtin_amdgcn_sched_barrier(0);
 
-    // real-FFT untangle: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[N-k]) / 2, O = (Z[k] - conj Z[N-k]) / (2i)
     const int64_t row = ((int64_t)b * T + t) * NBINS;
     auto bin = [&](int k, float2 zk, float2 znk, float2 wk) __attribute__((always_inline)) {
-      const float2 e = make_float2(0.5f * (zk.x + znk.x), 0.5f * (zk.y - znk.y));
-      const float2 o = make_float2(0.5f * (zk.y + znk.y), -0.5f * (zk.x - znk.x));
-      const float2 wo = cmul(wk, o);
-      const float re = e.x + wo.x, im = e.y + wo.y;
-      // clamp on the POWER (fDomainHelper.py:62); v_sqrt_f32 / v_rcp_f32 (1 ulp) instead of the IEEE expansions
-      const float mag = __builtin_amdgcn_sqrtf(fmaxf(re * re + im * im, eps));
+      float re, im, mag;
+      untangle_bin(zk, znk, wk, eps, re, im, mag);
       ms[k] = mag;
       if constexpr (!SPEC) return;
       if (sp) sp[row + k] = mag;
       if (cosp || sinp) {
-        const float inv = __builtin_amdgcn_rcpf(mag);  // mag = 0 (eps = 0, silent bin): inf, 0 * inf = NaN like 0 / 0
+        const float inv = __builtin_amdgcn_rcpf(mag);  // v_rcp_f32 (1 ulp); mag = 0 (eps = 0, silent bin): inf, 0 * inf = NaN like 0 / 0
         if (cosp) cosp[row + k] = re * inv;
         if (sinp) sinp[row + k] = im * inv;
       }
@@ -360,12 +377,66 @@ __global__ __launch_bounds__(128) void k_mel_project(const float* __restrict__ s
 // together is chosen so that they cannot touch the same sample (see the kernel).
 // IH = 16 (20 frames per workgroup) for large launches, 2 (6 frames, three times the inverse FFTs but a fraction of the serial
 // chain) when there are too few frames to fill the chip (streaming chunks).
-__global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __restrict__ re, const float* __restrict__ im,
-                                                              const float* __restrict__ window, const float2* __restrict__ tw,
-                                                              const float2* __restrict__ rtw, int T, int L, int hop, int groups,
-                                                              int IH, float* __restrict__ wav, const int* __restrict__ lens) {
+//
+// Low-pass by STFT masking (vfx_stft_lowpass, k_stft_lowpass): the SAME workgroup, with the spectrum of a frame made on the
+// spot instead of read -- the wave that owns the frame loads its samples (the forward kernel's load_frame, the clip's own
+// reflection), windows and transforms them, untangles the bins exactly as k_stft_mel does, forms mag, cos = re / mag,
+// sin = im / mag and X = (mag cos, mag sin), zero from the clip's cut-off bin up, and hands X[k] / X[1024 - k] to the pack
+// above.  No spectrum in HBM; the 4 halo frames of a group are transformed forward by both neighbours ((IH + 4) / IH forward
+// FFTs per frame).  Every expression is the one the two-launch path (k_stft_mel<true>, sp * cos and sp * sin by torch, k_istft)
+// evaluates, so the samples are bit for bit that path's.
+
+// a * b rounded to float32 ON ITS OWN: never the multiplication of an FMA.  The two-launch path stores mag * cos and mag * sin
+// to memory as float32 before the pack adds them; here the products feed straight into the pack's sums.  (The file's pragma says
+// so already; this one keeps the fence where it is needed whatever happens to that one.)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// One frame of the low-pass, by the wave that owns it.  In: xk = the sixteen sample pairs load_frame left.  Out: xk[r] = X[k],
+// xn[r] = X[1024 - k], k = lane + 64 r -- what k_istft's load_spectrum leaves -- with X = 0 for the bins k >= cut.
+__device__ __forceinline__ void lowpass_spectrum(float2 (&xk)[16], float2 (&xn)[16], float2* zw, const float2* twl,
+                                                 const float2* wl, float2 rtw_lane, int lane, int cut) {
+  asm volatile("" : "+v"(rtw_lane.x), "+v"(rtw_lane.y));  // the sixteen W^k are made per frame, not kept across the frame walk (and spilled)
+  float2 v[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float2 ww = wl[lane + 64 * r];
+    v[r] = make_float2(xk[r].x * ww.x, xk[r].y * ww.y);
+  }
+  wfft1024<-1>(v, zw, twl, lane);
+  mirror_bins(v, xn, zw, lane);
+  if (lane == 0) xn[0] = v[0];  // Z[1024] = Z[0]
+  __builtin_amdgcn_sched_barrier(0);
+  auto bin = [&](int k, float2 zk, float2 znk, float2 wk) __attribute__((always_inline)) {
+    float re, im, mag;
+    untangle_bin(zk, znk, wk, 1e-8f, re, im, mag);  // eps of wav_to_spectrogram_phase
+    const float inv = __builtin_amdgcn_rcpf(mag);
+    const float c = re * inv, s = im * inv;  // what k_stft_mel stores as cos / sin
+    return k >= cut ? make_float2(0.f, 0.f) : make_float2(mul_rounded(mag, c), mul_rounded(mag, s));
+  };
+  float2 top = make_float2(0.f, 0.f);
+  if (lane == 0) top = bin(NC, v[0], xn[0], make_float2(-1.f, 0.f));  // Z[1024] = Z[0], W^1024 = -1
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    xk[m] = bin(lane + 64 * m, v[m], xn[m], rtw_of(rtw_lane, m));
+    if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // four bins at a time, as in the forward kernel
+  }
+  if (lane == 0) zw[ZP - 1] = top;  // X[1024]: the partner of k = 0
+  mirror_bins(xk, xn, zw, lane);
+}
+
+// One workgroup of the inverse.  LOWPASS = false (k_istft): the spectrum is re / im (B, T, 1025).  true (k_stft_lowpass): it is
+// made from the rows of `src` (B, L) as above, masked from bin cuts[b] up; re / im are not read.
+template <bool LOWPASS>
+__device__ __forceinline__ void istft_group(const float* __restrict__ re, const float* __restrict__ im,
+                                            const float* __restrict__ src, const int* __restrict__ cuts,
+                                            const float* __restrict__ window, const float2* __restrict__ tw,
+                                            const float2* __restrict__ rtw, int T, int L, int hop, int groups, int IH,
+                                            float* __restrict__ wav, const int* __restrict__ lens) {
   __shared__ float2 twl[NC];
-  __shared__ float2 wl[NC];  // the synthesis window, as pairs
+  __shared__ float2 wl[NC];  // the synthesis window, as pairs (LOWPASS: the analysis window too)
   __shared__ float2 zbuf[STFT_WAVES][ZP];
   extern __shared__ __attribute__((aligned(16))) float ola[];  // [IH * hop]
   const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
@@ -393,15 +464,20 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __res
   __syncthreads();  // ola zeroed, twl and wl complete
 
   // the spectrum of this wave's frame of a round: (Re, Im) of bins k and 1024 - k, k = lane + 64 r
+  // (LOWPASS: what is requested ahead is the frame's samples, in xk; lowpass_spectrum turns them into the spectrum in place)
   float2 xk[16], xn[16];
   auto load_spectrum = [&](int t) __attribute__((always_inline)) {
-    const float* R = re + ((int64_t)b * Ts + t) * NBINS;
-    const float* I = im + ((int64_t)b * Ts + t) * NBINS;
+    if constexpr (LOWPASS) {
+      load_frame(src + (int64_t)b * Ls, L, t, hop, lane, xk);
+    } else {
+      const float* R = re + ((int64_t)b * Ts + t) * NBINS;
+      const float* I = im + ((int64_t)b * Ts + t) * NBINS;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned k = (unsigned)(lane + 64 * r);
-      xk[r] = make_float2(ldg32(R, k), ldg32(I, k));
-      xn[r] = make_float2(ldg32(R, NC - k), ldg32(I, NC - k));
+      for (int r = 0; r < 16; ++r) {
+        const unsigned k = (unsigned)(lane + 64 * r);
+        xk[r] = make_float2(ldg32(R, k), ldg32(I, k));
+        xn[r] = make_float2(ldg32(R, NC - k), ldg32(I, NC - k));
+      }
     }
   };
   // Frames at least D apart touch disjoint samples.  Round r (D rounds, one block barrier each) takes the frames t = r (mod D)
@@ -420,15 +496,15 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __res
     while (r == round) {
       const int t = t_lo + f;
       asm volatile("" : "+v"(lane));  // as in the forward kernel
+      if constexpr (LOWPASS) lowpass_spectrum(xk, xn, zbuf[wave], twl, wl, rtw_lane, lane, cuts[b]);
       float2 v[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const float2 e = make_float2(0.5f * (xk[q].x + xn[q].x), 0.5f * (xk[q].y - xn[q].y));
         const float2 d = make_float2(0.5f * (xk[q].x - xn[q].x), 0.5f * (xk[q].y + xn[q].y));
         float2 wk = rtw_of(rtw_lane, q);
         wk.y = -wk.y;  // conj(W^k) = e^{+2 pi i k / 2048}
         const float2 o = cmul(wk, d);
-        v[q] = make_float2(e.x - o.y, e.y + o.x);  // Z = E + i O
+        v[q] = make_float2(fmaf(0.5f, xk[q].x + xn[q].x, -o.y), fmaf(0.5f, xk[q].y - xn[q].y, o.x));  // Z = E + i O
       }
       // advance to this wave's next frame and request its spectrum: it travels during this frame's FFT
       f += D * STFT_WAVES;
@@ -440,8 +516,8 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __res
       for (int m = 0; m < 16; ++m) {
         const int i0 = off + 2 * (lane + 64 * m);
         const float2 ww = wl[lane + 64 * m];
-        if (i0 >= 0 && i0 < span) ola[i0] += v[m].x * sc * ww.x;  // one lane per sample, no other frame of the round nearby
-        if (i0 + 1 >= 0 && i0 + 1 < span) ola[i0 + 1] += v[m].y * sc * ww.y;
+        if (i0 >= 0 && i0 < span) ola[i0] = fmaf(v[m].x * sc, ww.x, ola[i0]);  // one lane per sample, no other frame of the round nearby
+        if (i0 + 1 >= 0 && i0 + 1 < span) ola[i0 + 1] = fmaf(v[m].y * sc, ww.y, ola[i0 + 1]);
       }
     }
     __syncthreads();
@@ -470,6 +546,25 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __res
   }
 }
 
+__global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __restrict__ re, const float* __restrict__ im,
+                                                              const float* __restrict__ window, const float2* __restrict__ tw,
+                                                              const float2* __restrict__ rtw, int T, int L, int hop, int groups,
+                                                              int IH, float* __restrict__ wav, const int* __restrict__ lens) {
+  istft_group<false>(re, im, nullptr, nullptr, window, tw, rtw, T, L, hop, groups, IH, wav, lens);
+}
+
+// wav (B, L), clip b = its first lens[b] samples (1024 < lens[b] <= L) -> out (B, L): the clip with the STFT bins from cut[b] up
+// removed, zeros past lens[b].  `window` is both the analysis and the synthesis window.  `out` must not overlap `wav`: a workgroup
+// reads samples its neighbours own.
+__global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_lowpass(const float* __restrict__ wav, const int* __restrict__ lens,
+                                                                     const int* __restrict__ cut,
+                                                                     const float* __restrict__ window,
+                                                                     const float2* __restrict__ tw,
+                                                                     const float2* __restrict__ rtw, int T, int L, int hop,
+                                                                     int groups, int IH, float* __restrict__ out) {
+  istft_group<true>(nullptr, nullptr, wav, cut, window, tw, rtw, T, L, hop, groups, IH, out, lens);
+}
+
 // Frames per wave of the forward kernel: as many as keep the launch at about one round of resident waves
 // (2 workgroups of 4 waves per CU -- 59 KB of LDS -- x 256 CUs), at most 32.
 static int frames_per_group(int64_t frames) {
@@ -496,15 +591,35 @@ void launch_mel_project(const FrontEndTables& t, const float* sp, int64_t rows, 
   VFX_HIP(hipGetLastError());
 }
 
+// The inverse's launch geometry: IH hops per workgroup, and the groups that cover the positions [0, 1024 + L) of the un-trimmed
+// overlap-add buffer
+struct IstftGrid {
+  int IH, span, groups;
+};
+static IstftGrid istft_grid(int B, int T, int L, int hop) {
+  IstftGrid g;
+  g.IH = (int64_t)B * T >= 4096 ? 16 : 2;
+  g.span = g.IH * hop;
+  g.groups = (NFFT / 2 + L + g.span - 1) / g.span;
+  return g;
+}
+
 void launch_istft(const FrontEndTables& t, const float* re, const float* im, int B, int T, int L, int hop, float* wav,
                   hipStream_t stream, const int* lens) {
-  // groups cover the positions [0, 1024 + L) of the un-trimmed overlap-add buffer
-  const int IH = (int64_t)B * T >= 4096 ? 16 : 2;
-  const int span = IH * hop;
-  const int groups = (NFFT / 2 + L + span - 1) / span;
-  hipLaunchKernelGGL(k_istft, dim3(B * groups), dim3(256), (size_t)span * sizeof(float), stream, re, im, t.window,
+  const IstftGrid g = istft_grid(B, T, L, hop);
+  hipLaunchKernelGGL(k_istft, dim3(B * g.groups), dim3(256), (size_t)g.span * sizeof(float), stream, re, im, t.window,
                      reinterpret_cast<const float2*>(t.twiddle), reinterpret_cast<const float2*>(t.rtwiddle), T, L, hop,
-                     groups, IH, wav, lens);
+                     g.groups, g.IH, wav, lens);
+  VFX_HIP(hipGetLastError());
+}
+
+void launch_stft_lowpass(const FrontEndTables& t, const float* wav, int B, int L, int hop, const int* lens, const int* cut,
+                         float* out, hipStream_t stream) {
+  const int T = L / hop + 1;  // frames of a clip that fills its row
+  const IstftGrid g = istft_grid(B, T, L, hop);
+  hipLaunchKernelGGL(k_stft_lowpass, dim3(B * g.groups), dim3(256), (size_t)g.span * sizeof(float), stream, wav, lens, cut,
+                     t.window, reinterpret_cast<const float2*>(t.twiddle), reinterpret_cast<const float2*>(t.rtwiddle), T, L,
+                     hop, g.groups, g.IH, out);
   VFX_HIP(hipGetLastError());
 }
 

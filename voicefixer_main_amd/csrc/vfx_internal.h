@@ -145,7 +145,8 @@ enum LensRow {
   LENS_RUN_SAMPLES = 6, LENS_RUN_FRAMES = 7, LENS_RUN_VOC_FRAMES = 8,  // samples / frames / vocoder frames of its vocoder run in flight
   LENS_ANALYSIS_FRAMES = 9,                                            // frames per clip of a vfx_analysis_mel call
   LENS_SCORE_SAMPLES = 10, LENS_SCORE_FRAMES = 11,                     // samples / frames of the vfx_audio_metrics sub-batch in flight
-  kLensRows = 12
+  LENS_LOWPASS_SAMPLES = 12, LENS_LOWPASS_CUT = 13,                    // samples / cut-off bin of the vfx_stft_lowpass sub-batch in flight
+  kLensRows = 14
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -416,6 +417,11 @@ void launch_stft_mel(const FrontEndTables& t, const float* wav, int B, int L, in
 void launch_mel_project(const FrontEndTables& t, const float* sp, int64_t rows, float* mel, hipStream_t stream);
 void launch_istft(const FrontEndTables& t, const float* re, const float* im, int B, int T, int L, int hop, float* wav,
                   hipStream_t stream, const int* lens = nullptr);  // lens: samples per clip of a varlen batch (device, [B])
+// STFT -> zero the bins k >= cut[b] -> ISTFT in one launch: wav (B, L), clip b = its first lens[b] samples (n_fft/2 < lens[b] <= L),
+// -> out (B, L), zeros past lens[b]; lens, cut: device, [B].  out must not overlap wav.  Bit for bit launch_stft_mel's sp * cos and
+// sp * sin, masked, through launch_istft.
+void launch_stft_lowpass(const FrontEndTables& t, const float* wav, int B, int L, int hop, const int* lens, const int* cut,
+                         float* out, hipStream_t stream);
 
 void launch_prep_logmel(const float* mel_linear, int B, int T, int Tpad, float* x, int* flags, hipStream_t s,
                         const int* lens_t = nullptr);  // lens_t: frames per clip of a varlen batch (device, [B])

@@ -230,6 +230,24 @@ class Engine:
         _lib.check(self.lib.vfx_istft(self.h, _ptr(re), _ptr(im), B, T, length, _ptr(wav), self._stream()), "vfx_istft")
         return wav
 
+    def stft_lowpass(self, x, cut_bins, lengths=None):
+        """The "stft_hard" low-pass of a padded batch in ONE launch (vfx_stft_lowpass): x (B, L) or (L,), clip b = the first
+        lengths[b] samples of row b (default L; 1024 < lengths[b] <= L); cut_bins: the first bin set to zero, one int or one per clip
+        (>= 0; 1025 and above masks nothing).  -> float32 of the same shape on the device, rows zero past their length.  Row b is bit
+        for bit simulate.stft_hard_lowpass_v0 of its first lengths[b] samples with int(1025 * ratio) == cut_bins[b], whatever batch
+        it is in."""
+        x = _dev_f32(x, self.device)
+        if x.dim() not in (1, 2):
+            raise ValueError("stft_lowpass: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
+        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "stft_lowpass")
+        cut_bins = [int(cut_bins)] * B if np.ndim(cut_bins) == 0 else [int(v) for v in cut_bins]
+        if B == 0 or len(cut_bins) != B:
+            raise ValueError("stft_lowpass: %d cut-off bins for %d clips" % (len(cut_bins), B))
+        y = torch.empty((B, L), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.vfx_stft_lowpass(self.h, _ptr(x), B, L, (ctypes.c_int * B)(*lengths), (ctypes.c_int * B)(*cut_bins), _ptr(y),
+                                             self._stream()), "vfx_stft_lowpass")
+        return y[0] if squeeze else y
+
     def spectral_metrics(self, est, target):
         """Per-clip (LSD, SiSpec dB) of est vs target, (B, T, F) or (B, 1, T, F) each -> (B, 2)."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)

@@ -21,7 +21,8 @@ same names, argument meaning and error behaviour:
 
 Everything is NumPy / SciPy on the host EXCEPT ``stft_hard``: its STFT -> mask -> ISTFT round trip is the hot path's own
 front-end and back-end (``vfx_stft_mel`` in its phase-emitting form and ``vfx_istft``), so it runs on the GPU through an
-``Engine`` -- the reference keeps a module-level ``FDomainHelper`` for it (lowpass.py:14,111-113).
+``Engine`` -- the reference keeps a module-level ``FDomainHelper`` for it (lowpass.py:14,111-113).  The list forms run it as
+padded batches in one fused launch (``vfx_stft_lowpass``), bit for bit the single-clip form.
 """
 import numpy as np
 import torch
@@ -219,10 +220,34 @@ def _stft_list(clips, ratio, engine, to_host, fs_ori=44100):
     return out
 
 
+def _stft_hard_list(clips, ratios, engine, to_host):
+    """`_type="stft_hard"` for a list, ratios[i] the ratio of clip i: every clip as float32 (what `stft_hard_lowpass_v0` makes of any
+    dtype), cut = int(1025 * ratio) as there, sorted by length and through Engine.stft_lowpass as padded batches of up to MAX_BATCH --
+    ONE launch per batch, each clip bit for bit its own `stft_hard_lowpass_v0` call.  An item of at most 1024 samples (no reflect
+    padding) or with a negative cut, and every item of an engine without `stft_lowpass`, takes that function, and raises what it
+    raises."""
+    eng = _engine_or_default(engine)
+    lengths = [c.shape[0] for c in clips]
+    cuts = [int(1025 * r) for r in ratios]
+    out = [None] * len(clips)
+    dev = [i for i in range(len(clips)) if hasattr(eng, "stft_lowpass") and lengths[i] > 1024 and cuts[i] >= 0]
+    for idx in _clips.batches(dev, lengths, MAX_BATCH):
+        lens = [lengths[i] for i in idx]
+        y = eng.stft_lowpass(_clips.pad([clips[i] for i in idx], eng.device, torch.float32), [cuts[i] for i in idx], lengths=lens)
+        for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
+            out[i] = row
+    for i in range(len(clips)):
+        if out[i] is None:
+            y = stft_hard_lowpass_v0(_clips.as_numpy(clips[i]), lowpass_ratio=ratios[i], engine=eng)
+            out[i] = y if to_host else _clips.to_device(y, eng.device)
+    return out
+
+
 def lowpass_list(clips, highcut, fs, order=5, _type="butter", engine=None, to_host=True):
     """`lowpass` for a list of 1-D clips of any lengths: the same 1-D check, substring dispatch, int() of the cut-off and order
     clamp, ONE filter design, and the IIR types as padded batches on the device -- every clip bit for bit what
-    scipy.signal.sosfiltfilt gives for it alone.  -> list in the caller's order: float64 NumPy arrays (to_host), or device tensors
+    scipy.signal.sosfiltfilt gives for it alone; "stft_hard" as padded batches through Engine.stft_lowpass, every clip bit for bit
+    `stft_hard_lowpass_v0`.  -> list in the caller's order: float64 NumPy arrays (to_host), or device tensors
     that `restore_list` takes as they are."""
     clips = list(clips)
     _check_1d(clips)
@@ -232,9 +257,7 @@ def lowpass_list(clips, highcut, fs, order=5, _type="butter", engine=None, to_ho
     if _type in "stft":
         return _stft_list(clips, highcut / int(fs / 2), engine, to_host)
     if _type in "stft_hard":
-        eng = _engine_or_default(engine)
-        ys = [stft_hard_lowpass_v0(_clips.as_numpy(c), lowpass_ratio=highcut / int(fs / 2), engine=eng) for c in clips]
-        return ys if to_host else [_clips.to_device(y, eng.device) for y in ys]
+        return _stft_hard_list(clips, [highcut / int(fs / 2)] * len(clips), engine, to_host)
     raise ValueError("Error: Unexpected filter type " + _type)
 
 
@@ -315,10 +338,9 @@ def _filter_each(clips, cuts, fs, orders, types, engine, to_host):
         for i, y in zip(idx, _stft_list([clips[i] for i in idx], highcut / int(fs / 2), engine, to_host)):
             out[i] = y
     if hard:
-        eng = _engine_or_default(engine)
-        for i in hard:
-            y = stft_hard_lowpass_v0(_clips.as_numpy(clips[i]), lowpass_ratio=cuts[i][0] / int(fs / 2), engine=eng)
-            out[i] = y if to_host else _clips.to_device(y, eng.device)
+        ys = _stft_hard_list([clips[i] for i in hard], [cuts[i][0] / int(fs / 2) for i in hard], engine, to_host)
+        for i, y in zip(hard, ys):
+            out[i] = y
     return out
 
 
@@ -328,7 +350,8 @@ def lowpass_each(clips, highcuts, fs, orders=5, types="butter", engine=None, to_
     per clip the 1-D check, the substring dispatch, int() of the cut-off and the order clamp are `lowpass`'s.  The IIR items are
     designed once per distinct (name, order, cut-off) and go through Engine.sosfiltfilt_bank as padded batches of one dtype, ONE
     launch pair per batch whatever its designs; "stft" items go through the device resampler grouped by cut-off (`lowpass_list`'s
-    rule for which), "stft_hard" items through `stft_hard_lowpass_v0`.  -> list: NumPy arrays (to_host), or device tensors."""
+    rule for which), "stft_hard" items through Engine.stft_lowpass as padded batches with a cut-off bin per clip (`_stft_hard_list`).
+    -> list: NumPy arrays (to_host), or device tensors."""
     clips = list(clips)
     n = len(clips)
     highcuts = _per_clip(highcuts, n, "lowpass_each: highcuts")
