@@ -381,6 +381,29 @@ int vfx_spectral_metrics(vfx_handle* h, const float* est, const float* target, i
 int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
                       void* stream);
 
+/*
+ * STOI, the short-time objective intelligibility measure (Taal, Hendriks, Heusdens, Jensen, IEEE TASLP 2011; restated from the paper,
+ * the authors' MATLAB and pystoi's stoi(extended=False) -- not pinned against the pystoi package), for a padded batch of (est, target)
+ * waveform pairs: est, target (B, Lmax) device floats, pair b = the first lengths[b] samples of row b; lengths is a HOST array int[B]
+ * with 1 <= lengths[b] <= Lmax.  target is the clean signal, est the processed one: the score is not symmetric.  out: B device doubles.
+ *   1  both signals go to 10 kHz by scipy.signal.resample_poly(x, up, down, window=taps): up / down = 10000 / fs (reduced by their gcd
+ *      here), taps = ntaps DEVICE doubles, the filter ALREADY multiplied by up, ntaps odd.  up == down: the clips are at 10 kHz, taps is
+ *      not read and may be NULL.  The resampler takes a reduced up <= 1024, down <= 32768 and ntaps <= 2^20; anything beyond is refused
+ *      with an error that names the limit, never truncated.
+ *   2  silent-frame removal: w = hanning(258)[1:-1], frames of 256 at range(0, n - 256, 128) (the authors' 1:hop:(n - N): the last
+ *      aligned frame is NOT taken), e = 20 log10(|w . target frame| + EPS), kept when max(e) - 40 - e < 0, the kept windowed frames of
+ *      both signals overlap-added at hop 128
+ *   3  STFT of both by the same window and frame rule (kept - 1 frames), 512-point; fewer than 30 frames: the score is 1e-5
+ *   4  15 third-octave bands from 150 Hz: the square root of the summed |X|^2 of rFFT bins [7,9) [9,11) [11,14) [14,17) [17,22) [22,27)
+ *      [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138) [138,174) [174,219)
+ *   5  per segment of 30 frames and band: a = |x| / (|y| + EPS), y' = min(a y, x (1 + 10^(15/20))), both minus their means and divided
+ *      by (their norm + EPS), the inner product; out[b] = the mean over segments and bands.  EPS = 2^-52.
+ * Float64 from the first multiply on, every sum in an order fixed by the clip alone: a clip's score does not depend on the batch it is
+ * in nor on Lmax; nothing at or past a clip's length is read.  The workspace is the one of vfx_audio_metrics (sub-batched under 256 MiB).
+ */
+int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,
+             const double* taps, int ntaps, double* out, void* stream);
+
 /* Read-and-clear the sticky device flags (synchronises `stream`). */
 int vfx_take_flags(vfx_handle* h, void* stream, int* flags_out);
 /* ... only the bits in `mask` (VFX_FLAG_*): the others stay raised for a later check. */

@@ -141,6 +141,16 @@ int vfx_op_ssim(vfx_handle* h, const float* est, const float* target, int B, int
 /* The SI-SDR of vfx_audio_metrics alone (k_sisdr_slabs + k_score_final): est[b, :lens[b]] against target[b, :lens[b]] of (B, L)
  * device tensors; lens HOST int[B], 1 <= lens[b] <= L -> out (B) device doubles.  Synchronises. */
 int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, int L, const int* lens, double* out, void* stream);
+/* One intermediate of a vfx_stoi call -- the same arguments up to ntaps, B <= 1024 -- for the whole batch, to localise a failing score.  With
+ * N = ceil(max(lens) up / down) samples at 10 kHz and Fm = max(1, frames of N by range(0, N - 256, 128)); what lies past a clip's own
+ * extent is zero.  out and iout are DEVICE arrays of exactly out_n doubles and iout_n ints:
+ *   stage 0  out (B, 2, N): est and target at 10 kHz;                                       iout (B): each clip's samples at 10 kHz
+ *   stage 1  out (B, Fm): the target's frame energies in dB;                                iout (B) kept counts, then (B, Fm) the keep mask
+ *   stage 2  out (B, 2, Fm, 15): band POWERS of est and target per STFT frame m < kept - 1; iout (B): kept counts
+ *   stage 3  out (B, 2, Fm, 15): their square roots (tob);                                  iout (B): kept counts
+ * Synchronises. */
+int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int up, int down,
+                      const double* taps, int ntaps, int stage, double* out, int64_t out_n, int* iout, int64_t iout_n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,12 +3,13 @@
 varlen workload (scripts/bench_varlen.py: the same lengths), timed four ways:
 
   device_ms        vfx_audio_metrics over the 128 pairs as ONE call (sorted by length), HIP events, median of --reps
+  stoi_device_ms   with --stoi: vfx_stoi over the same 128 pairs as one call, timed the same way (report only)
   restore_list_s   VoiceFixer.restore_list on the same clips (synthetic weights, --precision), wall, median: the bar is
                    device_ms <= 10 % of it
   aggregate_s      aggregate_score end to end: 128 PCM16 est files and 128 targets read, scored, JSON / CSV / result.json written
   numpy_s          the float64 numpy restatement (tests/audio_metrics_f64.py) over the same pairs on --threads threads
 
-    python scripts/bench_scoring.py [--clips=128] [--reps=5] [--precision=2] [--threads=16] [--only-device] > scoring.json
+    python scripts/bench_scoring.py [--clips=128] [--reps=5] [--precision=2] [--threads=16] [--only-device] [--stoi] > scoring.json
 """
 import json
 import os
@@ -57,19 +58,28 @@ def main():
         t[j, :lens[i]] = torch.from_numpy(tgts[i])
     e, t = e.to(dev), t.to(dev)
     ls = [lens[i] for i in order]
-    eng.audio_metrics(e, t, ls)                     # workspace
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        eng.audio_metrics(e, t, ls)
-        b.record()
+
+    def device_ms(call):
+        call()                                      # workspace
         torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return ms
+
+    ms = device_ms(lambda: eng.audio_metrics(e, t, ls))
     res["device_ms"] = round(float(np.median(ms)), 3)
     res["device_ms_all"] = [round(v, 3) for v in ms]
     res["device_audio_s_per_s"] = round(total / (res["device_ms"] / 1e3), 1)
+    if "--stoi" in sys.argv:
+        ms = device_ms(lambda: eng.stoi(e, t, ls, fs=44100))
+        res["stoi_device_ms"] = round(float(np.median(ms)), 3)
+        res["stoi_device_ms_all"] = [round(v, 3) for v in ms]
     if "--only-device" in sys.argv:                 # (a profiler run: nothing but the scoring call in the trace)
         print(json.dumps(res))
         return

@@ -390,6 +390,13 @@ int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int 
   VFX_API_END
 }
 
+int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,
+             const double* taps, int ntaps, double* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  stoi_scores(h, est, target, B, Lmax, lengths, up, down, taps, ntaps, out, nullptr, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_chunk_gather(vfx_handle* h, const float* x, int B, int L, int win, int hop, int lead, int n_chunks,
                      float* chunks, void* stream) {
   VFX_API_BEGIN_HS(h, stream)

@@ -1019,3 +1019,24 @@ extern "C" int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target
   }
   return 0;
 }
+
+extern "C" int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int up, int down,
+                                 const double* taps, int ntaps, int stage, double* out, int64_t out_n, int* iout, int64_t iout_n,
+                                 void* stream) {
+  try {
+    VFX_CHECK(h != nullptr, "vfx_op_stoi_stage: NULL handle");
+    DeviceGuard device_guard_(h->device);
+    StoiStageOut so;
+    so.stage = stage;
+    so.out = out;
+    so.out_n = out_n;
+    so.iout = iout;
+    so.iout_n = iout_n;
+    Scratch sc;
+    double* scores = static_cast<double*>(sc.blob.alloc((size_t)std::max(B, 1) * sizeof(double)));
+    stoi_scores(h, est, target, B, Lmax, lens, up, down, taps, ntaps, scores, &so, static_cast<hipStream_t>(stream));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}

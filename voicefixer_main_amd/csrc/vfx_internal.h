@@ -146,7 +146,8 @@ enum LensRow {
   LENS_ANALYSIS_FRAMES = 9,                                            // frames per clip of a vfx_analysis_mel call
   LENS_SCORE_SAMPLES = 10, LENS_SCORE_FRAMES = 11,                     // samples / frames of the vfx_audio_metrics sub-batch in flight
   LENS_LOWPASS_SAMPLES = 12, LENS_LOWPASS_CUT = 13,                    // samples / cut-off bin of the vfx_stft_lowpass sub-batch in flight
-  kLensRows = 14
+  LENS_STOI_SAMPLES = 14, LENS_STOI_OUT = 15, LENS_STOI_FRAMES = 16,   // input samples / 10 kHz samples / frames of the vfx_stoi sub-batch in flight
+  kLensRows = 17
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -476,6 +477,25 @@ void launch_score_frames(const float* est, const float* tgt, int B, int T, int F
 void launch_ssim_tiles(const float* est, const float* tgt, int B, int T, int F, const int* frames, double* ws, hipStream_t s);
 void launch_score_final(const ScoreFinalArgs& a, int B, hipStream_t s);
 int64_t count_nonfinite(const float* p, int64_t n, hipStream_t s);  // debug aid, synchronises
+
+// stoi.hip: STOI (Taal, Hendriks, Heusdens, Jensen 2011) of the clips of a padded batch, float64 from the first multiply on
+constexpr int kStoiRate = 10000, kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiSegment = 30;
+constexpr int kStoiMaxUp = 1024;        // reduced up factor: k_stoi_resample stages the phases of whole tap steps in LDS
+constexpr int kStoiMaxDown = 1 << 15;   // reduced down factor
+constexpr int kStoiMaxTaps = 1 << 20;   // taps of the resampling filter
+__host__ __device__ inline int64_t stoi_out_len(int64_t n, int up, int down) { return (n * up + down - 1) / down; }   // len(resample_poly(x[:n]))
+inline int stoi_frames(int64_t n) { return n > kStoiFrame ? (int)((n - kStoiFrame + kStoiHop - 1) / kStoiHop) : 0; }  // range(0, n - 256, 128)
+// one intermediate of a vfx_stoi call, copied out for libvfx_test.so (vfx_op_stoi_stage; the stages and layouts: include/vfx_test.h)
+struct StoiStageOut {
+  int stage = 0;
+  double* out = nullptr;
+  int64_t out_n = 0;
+  int* iout = nullptr;
+  int64_t iout_n = 0;
+};
+// vfx_stoi (checks its arguments before the first launch); stage: null, or the intermediate to copy out (one sub-batch only)
+void stoi_scores(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,
+                 const double* taps, int ntaps, double* out, const StoiStageOut* stage, hipStream_t s);
 void launch_chunk_gather(const float* x, int B, int L, int win, int hop, int lead, int n_chunks, float* chunks,
                          hipStream_t s);
 void launch_chunk_ola(const float* frames, const float* window, float scale, int B, int n_chunks, int win, int hop,

@@ -81,6 +81,7 @@ class Engine:
         self._strict = None
         self.analysis_model = MODEL_UNET_MEL   # what restore_gsr(_varlen) runs (select_analysis)
         self._resample_taps = {}   # (up, down) -> the filter of resample_poly on the device
+        self._stoi_taps = {}       # (up, down) -> Octave's resample filter (float64) on the device, for `stoi`
 
     def close(self):
         if getattr(self, "_strict", None) is not None:
@@ -273,6 +274,51 @@ class Engine:
         out = torch.empty((B, _lib.N_AUDIO_METRICS), device=self.device, dtype=torch.float64)
         _lib.check(self.lib.vfx_audio_metrics(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
                                               self._stream()), "vfx_audio_metrics")
+        return out
+
+    STOI_RATE = 10000
+    _STOI_MAX_HOST_TAPS = 1 << 20   # a longer filter is not built on the host: vfx_stoi refuses its tap count by itself
+
+    def stoi_taps(self, fs):
+        """(up, down, taps, ntaps) of `stoi` for clips at `fs` Hz: up / down = 10000 / fs reduced, taps = up * h / sum(h) of Octave's
+        `resample` filter h (fc = 1 / (2 max(up, down)), roll-off fc / 10, 60 dB: a Kaiser-windowed sinc of 2 L + 1 taps), built in
+        float64 on the host and cached on the device per (up, down).  taps is None at 10 kHz, and for a filter too long to build
+        (vfx_stoi then refuses the tap count)."""
+        fs = int(fs)
+        if fs <= 0:
+            raise ValueError("stoi: fs must be positive, got %d" % fs)
+        g = math.gcd(self.STOI_RATE, fs)
+        up, down = self.STOI_RATE // g, fs // g
+        if up == down:
+            return up, down, None, 0
+        fc = 1.0 / (2 * max(up, down))
+        L = int(math.ceil((60.0 - 8.0) / (28.714 * (fc / 10.0))))
+        ntaps = 2 * L + 1
+        if ntaps > self._STOI_MAX_HOST_TAPS:
+            return up, down, None, min(ntaps, 2 ** 31 - 1)
+        taps = self._stoi_taps.get((up, down))
+        if taps is None:
+            t = np.arange(-L, L + 1)
+            h = np.kaiser(ntaps, 0.1102 * (60.0 - 8.7)) * (2 * up * fc * np.sinc(2 * fc * t))
+            taps = torch.from_numpy(up * (h / np.sum(h))).to(self.device)
+            self._stoi_taps[(up, down)] = taps
+        return up, down, taps, ntaps
+
+    def stoi(self, est, target, lengths=None, fs=44100):
+        """STOI (Taal et al. 2011, as pystoi's stoi(target, est, fs, extended=False)) of waveform pairs at `fs` Hz: est, target (B, L)
+        or (L,), pair b = the first lengths[b] samples of row b (default: all L) -> (B,) float64 on the device (vfx_stoi).  target is
+        the clean signal; the score is not symmetric.  A pair with fewer than 30 frames left after the silent-frame removal scores
+        1e-5.  A rate the resampling kernel does not take raises RuntimeError with the library's text."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        if est.shape != target.shape or est.dim() != 2:
+            raise ValueError("stoi: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
+        est, _, B, L, lengths = _clip_rows(est, lengths, "stoi")
+        up, down, taps, ntaps = self.stoi_taps(fs)
+        out = torch.empty(B, device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_stoi(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * max(B, 1))(*lengths), up, down,
+                                     _ptr(taps) if taps is not None else None, ntaps, _ptr(out), self._stream()), "vfx_stoi")
         return out
 
     def chunk_gather(self, x, win, hop, lead, n_chunks):
@@ -896,3 +942,30 @@ class Engine:
         _lib.check(_lib.load_test().vfx_op_sisdr(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
                                                  self._stream()), "vfx_op_sisdr")
         return out
+
+    STOI_STAGES = ("resampled", "mask", "powers", "tob")
+
+    def op_stoi_stage(self, stage, est, target, lengths=None, fs=44100):
+        """One intermediate of `stoi` for the whole batch (vfx_op_stoi_stage), as float64 / int32 tensors on the device; N = the
+        longest clip's samples at 10 kHz, Fm = max(1, its frames); entries past a clip's own extent are zero:
+          "resampled" -> (est and target at 10 kHz (B, 2, N), each clip's samples at 10 kHz (B,))
+          "mask"      -> (the target's frame energies in dB (B, Fm), kept counts (B,), the keep mask (B, Fm))
+          "powers"    -> (band powers of est and target per STFT frame (B, 2, Fm, 15), kept counts (B,)): frames m < kept - 1
+          "tob"       -> (their square roots, kept counts)"""
+        k = self.STOI_STAGES.index(stage)
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        est, _, B, L, lengths = _clip_rows(est, lengths, "op_stoi_stage")
+        up, down, taps, ntaps = self.stoi_taps(fs)
+        N = max(1, -(-max(lengths) * up // down))
+        Fm = max(1, -(-(N - 256) // 128))
+        shape = ((B, 2, N), (B, Fm), (B, 2, Fm, 15), (B, 2, Fm, 15))[k]
+        out = torch.zeros(shape, device=self.device, dtype=torch.float64)
+        iout = torch.zeros(B * (1 + Fm) if k == 1 else B, device=self.device, dtype=torch.int32)
+        _lib.check(_lib.load_test().vfx_op_stoi_stage(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), up, down,
+                                                      _ptr(taps) if taps is not None else None, ntaps, k, _ptr(out), out.numel(),
+                                                      _ptr(iout), iout.numel(), self._stream()), "vfx_op_stoi_stage")
+        if k == 1:
+            return out, iout[:B], iout[B:].view(B, Fm)
+        return out, iout

@@ -5,8 +5,15 @@
 
     sisdr, lsd, non_log_sispec, sispec, ssim, final_mel_lsd, final_non_log_mel_sispec, final_mel_sispec, final_mel_ssim
 
+and, with `stoi=True`, the key `stoi` right after `sisdr` (the reference's order), computed on the GPU by vfx_stoi (Engine.stoi) from
+the same padded batches.  STOI is restated from the published algorithm (Taal, Hendriks, Heusdens, Jensen 2011; the authors' MATLAB;
+pystoi's stoi(extended=False): 10 kHz by Octave's resample filter, frames at range(0, n - 256, 128) -- the last aligned frame is not
+taken --, 1e-5 for fewer than 30 frames) and, like SI-SDR, held against a float64 restatement (tests/stoi_f64.py: within 1e-9), not
+pinned against the pystoi package.
+
 What differs from the reference, on purpose:
-  * STOI, PESQ and the bsseval scores are not computed, and their keys are absent (no implementation to pin them against).
+  * STOI is opt-in (`stoi=True`); PESQ and the bsseval scores are not computed, and their keys are absent (no implementation to pin
+    them against).
   * Only 44.1 kHz targets: any other rate raises ValueError, like the reference's "Bad Samplerate" for rates it has no STFT for
     (its 16 kHz branch is not implemented).  An est file at another rate than its target, or of another length, makes that pair
     an error: speechmetrics would zero-pad the shorter signal and librosa.load would resample est.
@@ -53,9 +60,10 @@ def _wav_info(path):
 
 class AudioMetrics:
     """evaluation_proc/metrics.py:20-106 at 44.1 kHz.  `engine`: an Engine (or anything with `device` and
-    `audio_metrics(est, target, lengths)`); default: a new Engine on cuda:0."""
+    `audio_metrics(est, target, lengths)` -- and, for `stoi=True`, `stoi(est, target, lengths, fs)`); default: a new Engine on cuda:0.
+    stoi=True adds the key "stoi" after "sisdr"."""
 
-    def __init__(self, rate, engine=None):
+    def __init__(self, rate, engine=None, stoi=False):
         if int(rate) != SAMPLE_RATE:
             raise ValueError("Bad Samplerate: %s (only %d Hz test sets are scored)" % (rate, SAMPLE_RATE))
         self.rate = int(rate)
@@ -63,10 +71,13 @@ class AudioMetrics:
             from .engine import Engine
             engine = Engine("cuda:0")
         self.engine = engine
+        self.stoi = bool(stoi)
+        self.keys = METRIC_KEYS[:1] + ("stoi",) + METRIC_KEYS[1:] if self.stoi else METRIC_KEYS
 
     # ------------------------------------------------------------------ files
     def evaluation(self, est, target):
-        """est, target: .wav paths -> {key: float} (METRIC_KEYS); {} when target is None."""
+        """est, target: .wav paths -> {key: float} (self.keys: METRIC_KEYS, with "stoi" second when asked for); {} when target is
+        None."""
         if target is None:
             return {}
         r = self.evaluation_list([(est, target)])[0]
@@ -88,7 +99,8 @@ class AudioMetrics:
 
     def evaluation_list(self, pairs, max_batch=128):
         """[(est_path, target_path), ...] -> one entry per pair, in order: the {key: float} dict, or the exception that pair
-        raised.  The pairs are read and scored sorted by length, up to `max_batch` per padded batch (one vfx_audio_metrics call)."""
+        raised.  The pairs are read and scored sorted by length, up to `max_batch` per padded batch (one vfx_audio_metrics call and,
+        with stoi, one vfx_stoi call on the same device tensors)."""
         results = [None] * len(pairs)
         ok = []
         for i, (est, target) in enumerate(pairs):
@@ -117,10 +129,13 @@ class AudioMetrics:
             if not idx:
                 continue
             k = len(idx)
-            scores = self.engine.audio_metrics(torch.from_numpy(est[:k]).to(dev), torch.from_numpy(tgt[:k]).to(dev), lengths)
-            scores = scores.cpu().numpy().tolist()
+            e_dev, t_dev = torch.from_numpy(est[:k]).to(dev), torch.from_numpy(tgt[:k]).to(dev)
+            scores = self.engine.audio_metrics(e_dev, t_dev, lengths).cpu().numpy().tolist()
+            if self.stoi:
+                st = self.engine.stoi(e_dev, t_dev, lengths, fs=SAMPLE_RATE).cpu().numpy().tolist()
+                scores = [row[:1] + [st[j]] + row[1:] for j, row in enumerate(scores)]
             for j, i in enumerate(idx):
-                results[i] = {key: float(v) for key, v in zip(METRIC_KEYS, scores[j])}
+                results[i] = {key: float(v) for key, v in zip(self.keys, scores[j])}
         return results
 
     # ------------------------------------------------------------------ tensors (metrics.py:83-106)
@@ -168,12 +183,13 @@ def _write_table(path, rows, cols, mean_row=None):
             w.writerow(["mean"] + [repr(mean_row[c]) for c in cols])
 
 
-def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=None):
+def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=None, stoi=False):
     """evaluation_proc/eval.py:25-86.  metas[testset] = {"rate": ..., "list": path of the `source [target]` list}; the restored
     file of a line is save_dir/testset/basename(source).  Per pair with a target: the scores, updated with the handler's JSON
     beside the restored file (save_dir/testset/<name>.json, when it exists), are written back to that JSON.  Per test set:
     <testset>.csv (one row per target basename and a `mean` row) and result.json (the means).  A pair that fails is logged and
-    left out.  Returns {testset: {target basename: scores}}."""
+    left out.  stoi=True: the scores carry "stoi" (AudioMetrics(stoi=True)), and so do the tables and means.  Returns
+    {testset: {target basename: scores}}."""
     if metas is None:
         raise ValueError("aggregate_score: metas ({testset: {'rate', 'list'}}) is required (the reference's Config is not part of "
                          "this package)")
@@ -186,7 +202,7 @@ def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=No
         lst = read_list(meta["list"])
         if limit_number is not None:
             lst = lst[:limit_number]
-        judger = AudioMetrics(rate=meta["rate"], engine=engine)
+        judger = AudioMetrics(rate=meta["rate"], engine=engine, stoi=stoi)
         pairs, names = [], []
         for line in lst:
             source, target = _parse(line)
