@@ -95,9 +95,10 @@ int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, int Cin, cons
                       float next_slope, const int* lens, float* y, float* ya, void* stream);
 /* vfx_op_voc_final: the vocoder tail tanh(conv1d(ReflectionPad1d(3)(LeakyReLU(x, slope)), weight (1, C, 7)) + bias) of x (B, T, C)
  *   -> wav (B, T); x_f16: the tail reads x as an fp16 trunk (converted here).  With lens, clip b reflects at its own end and its samples
- *   from lens[b] on are not written. */
+ *   from lens[b] on are not written.  peak: NULL, or B device floats that receive max |wav[b, :len_b]| of each clip -- what the restore
+ *   path's peak normalisation reads. */
 int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const float* weight, float bias, float slope, int x_f16,
-                     const int* lens, float* wav, void* stream);
+                     const int* lens, float* wav, float* peak, void* stream);
 /* Host-only: the kernel the vocoder plan runs a Cin -> Cout = Cin / 2 upsampler of stride s over T input positions on (a stage behind the
  * first and not the last, in precision mode `precision` with vfx_config.tuning = `tuning`): 1 = k_up16, 0 = the phased k_conv,
  * -1 = bad arguments. */
@@ -133,6 +134,37 @@ int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, int B, int H,
  * block, 6 persistent C = 32 block), ksplit (1 = no split-K), activated output, bias, K segments, output channels. */
 int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches, int cap,
                         int* nlaunch);
+
+/* The STFT / ISTFT front end (stft.hip) and the glue launches between the models of a restore call (small_ops.hip), ONE launcher each
+ * with the handle's own tables, for tests/test_gpu_frontend_launches.py.  Tensors on the device, per-clip lengths HOST int[B] or NULL;
+ * every call synchronises.
+ *
+ * vfx_op_stft: launch_stft_mel as the fixed and the varlen callers run it.  wav (B, L); T = the row stride of the outputs in frames:
+ *   L / hop + 1 without lens, any T >= 1 with lens (clip b = its first lens[b] samples, n_fft / 2 < lens[b] <= L, framed and reflected at
+ *   its own end; output rows past its min(T, lens[b] / hop + 1) frames are 0, -8 for the log-mel).  eps: the clamp on the power;
+ *   log10_mel: mel = log10(max(mel, 1e-8)).  mel (B, T, 128), sp / cos / sin (B, T, 1025): any of them NULL, not all. */
+int vfx_op_stft(vfx_handle* h, const float* wav, int B, int L, int T, const int* lens, float eps, int log10_mel, float* mel, float* sp,
+                float* cosp, float* sinp, void* stream);
+/* vfx_op_istft: launch_istft.  re, im (B, T, 1025) -> wav (B, L); with lens (1 <= lens[b] <= L) clip b has min(T, lens[b] / hop + 1)
+ *   frames -- its later rows of re / im are not read -- and lens[b] samples, zeros behind them. */
+int vfx_op_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, const int* lens, float* wav, void* stream);
+/* Host-only: the frames one wave of the forward kernel walks in a launch of `frames` = B * T frames. */
+int vfx_plan_stft_frames_per_group(int64_t frames);
+/* Host-only: the inverse's launch geometry for (B, T, L) at the default hop: out[2] = IH (hops of the overlap-add buffer per workgroup),
+ * workgroups per clip. */
+int vfx_plan_istft_grid(int B, int T, int L, int* out);
+/* vfx_op_from_log: launch_from_log.  mel_out = 10 ** min(logmel, 5) of (B, T, 128) tensors; unify != 0: scaled per clip by the ratio of the
+ *   sums of mel_in and of that estimate over the bins 5..24 (amp_to_original_f) and the clip's frames (lens_t[b] <= T, or all T). */
+int vfx_op_from_log(vfx_handle* h, const float* logmel, const float* mel_in, int B, int T, int unify, const int* lens_t, float* mel_out,
+                    void* stream);
+/* vfx_op_voc_prep: launch_voc_prep with the handle's band weights and voc_amp_floor / voc_min_db / voc_norm_range.  mel (B, T, 128) linear
+ *   -> cond (B, Tp, 128) in [-R, R], Tp >= T; rows at and past a clip's frames (lens_t[b] <= T, or T) are -R. */
+int vfx_op_voc_prep(vfx_handle* h, const float* mel, int B, int T, int Tp, const int* lens_t, float* cond, void* stream);
+/* vfx_op_peak_trim: launch_peak_trim, or launch_peak_trim_varlen when lens_l and lens_tp are given.  wav_long (B, Llong) -> out (B, L):
+ *   the centre L samples of each row (varlen: lens_l[b] samples from (lens_tp[b] * hop - lens_l[b]) / 2 on, zeros behind them), divided by
+ *   peak[b] where that exceeds 1 -- which raises VFX_FLAG_PEAK_NORMALISED in the handle's flag word.  peak: HOST float[B]. */
+int vfx_op_peak_trim(vfx_handle* h, const float* wav_long, int B, int64_t Llong, int L, const float* peak, const int* lens_l,
+                     const int* lens_tp, float* out, void* stream);
 
 /* The SSIM of vfx_audio_metrics alone (k_ssim_tiles + k_score_final): skimage structural_similarity(win_size=7) of the images
  * est[b], target[b] of (B, T, F) device tensors, clip b = its first rows[b] rows; rows HOST int[B], 7 <= rows[b] <= T, F >= 7

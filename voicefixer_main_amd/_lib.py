@@ -111,12 +111,20 @@ TEST_SIGNATURES = {
     "vfx_op_voc_conv1d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_float, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfx_op_voc_final": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p,
-                                 c_void_p]),
+                                 c_void_p, c_void_p]),
     "vfx_plan_voc_upsampler_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vfx_op_unet_piece": (c_int, [c_void_p, c_int, c_char_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int64), c_int,
                                   c_void_p, POINTER(c_int64), c_int, c_void_p, c_int64, POINTER(c_int), POINTER(c_int), c_int,
                                   POINTER(c_int), c_void_p]),
     "vfx_plan_unet_piece": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
+    "vfx_op_stft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p]),
+    "vfx_op_istft": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_plan_stft_frames_per_group": (c_int, [c_int64]),
+    "vfx_plan_istft_grid": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
+    "vfx_op_from_log": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_voc_prep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_peak_trim": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_ssim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_stoi_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_int,

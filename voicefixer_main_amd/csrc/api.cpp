@@ -806,7 +806,7 @@ static int vfx_restore_gsr_1(vfx_handle* h, const float* wav, int B, int L, floa
     build_vocoder(pb, B, T, arena_buf(o_den), arena_buf(o_long), &peak_buf);
     pl->ops.push_back([=](const RunCtx& c) {
       launch_peak_trim(reinterpret_cast<float*>(pl->bound_base + o_long), B, Llong, L,
-                       reinterpret_cast<float*>(pl->bound_base + o_pk), /*have_peak=*/true, c.ext[1], c.stream, c.flags);
+                       reinterpret_cast<float*>(pl->bound_base + o_pk), c.ext[1], c.stream, c.flags);
     });
   });
   VFX_API_END

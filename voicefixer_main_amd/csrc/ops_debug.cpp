@@ -849,7 +849,7 @@ extern "C" int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, in
 }
 
 extern "C" int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const float* weight, float bias, float slope, int x_f16,
-                                const int* lens, float* wav, void* stream) {
+                                const int* lens, float* wav, float* peak, void* stream) {
   try {
     VFX_CHECK(h && x && weight && wav && B > 0 && T > 0, "vfx_op_voc_final: bad argument");
     DeviceGuard device_guard_(h->device);
@@ -859,7 +859,8 @@ extern "C" int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int
     for (int k = 0; k < 7; ++k)
       for (int ch = 0; ch < C; ++ch) wt[k * C + ch] = weight[ch * 7 + k];
     const float* src = x_f16 ? to_device_f16(sc.blob, x, (size_t)B * T * C, 1.f) : x;
-    launch_voc_final(src, x_f16 ? 1 : 0, B, T, C, sc.blob.upload(wt), bias, slope, wav, nullptr, s, upload_lens(sc.blob, lens, B), 1);
+    launch_voc_final(src, x_f16 ? 1 : 0, B, T, C, sc.blob.upload(wt), bias, slope, wav,
+                     reinterpret_cast<unsigned*>(peak), s, upload_lens(sc.blob, lens, B), 1);
     VFX_HIP(hipStreamSynchronize(s));
   } catch (const vfx::Error&) {
     return 1;
@@ -958,6 +959,121 @@ extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int a
     pc.arg = arg;
     build_unet_piece(pb, shapes, pc);
     *nlaunch = describe_unet_launches(plan, launches, launches ? cap : 0);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+// ---- the STFT / ISTFT front end and the glue launches of a restore call, one launcher each with the handle's tables -------------------
+extern "C" int vfx_op_stft(vfx_handle* h, const float* wav, int B, int L, int T, const int* lens, float eps, int log10_mel, float* mel,
+                           float* sp, float* cosp, float* sinp, void* stream) {
+  try {
+    VFX_CHECK(h && wav && B > 0 && T > 0 && (mel || sp || cosp || sinp) && eps >= 0.f, "vfx_op_stft: bad argument");
+    const int hop = h->cfg.hop, half = h->cfg.n_fft / 2;
+    VFX_CHECK(L > half, "vfx_op_stft: clips too short for reflect padding (L = %d)", L);
+    VFX_CHECK(lens || T == L / hop + 1, "vfx_op_stft: without lens, T is L / hop + 1 = %d", L / hop + 1);
+    for (int b = 0; lens && b < B; ++b)
+      VFX_CHECK(lens[b] > half && lens[b] <= L, "vfx_op_stft: clip %d has %d samples (need %d .. L = %d)", b, lens[b], half + 1, L);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    launch_stft_mel(h->fe, wav, B, L, T, mel, sp, cosp, sinp, log10_mel, hop, eps, s, upload_lens(sc.blob, lens, B));
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, const int* lens, float* wav,
+                            void* stream) {
+  try {
+    VFX_CHECK(h && re && im && wav && B > 0 && T > 0 && L > 0, "vfx_op_istft: bad argument");
+    for (int b = 0; lens && b < B; ++b)
+      VFX_CHECK(lens[b] >= 1 && lens[b] <= L, "vfx_op_istft: clip %d has %d samples (need 1 .. L = %d)", b, lens[b], L);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    launch_istft(h->fe, re, im, B, T, L, h->cfg.hop, wav, s, upload_lens(sc.blob, lens, B));
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_plan_stft_frames_per_group(int64_t frames) { return frames > 0 ? frames_per_group(frames) : -1; }
+
+extern "C" int vfx_plan_istft_grid(int B, int T, int L, int* out) {
+  try {
+    VFX_CHECK(B > 0 && T > 0 && L > 0 && out, "vfx_plan_istft_grid: bad argument");
+    vfx_config cfg{};
+    VFX_CHECK(vfx_default_config(&cfg) == 0, "no default config");
+    const IstftGrid g = istft_grid(B, T, L, cfg.hop);
+    out[0] = g.IH;
+    out[1] = g.groups;
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_from_log(vfx_handle* h, const float* logmel, const float* mel_in, int B, int T, int unify, const int* lens_t,
+                               float* mel_out, void* stream) {
+  try {
+    VFX_CHECK(h && logmel && mel_out && B > 0 && T > 0 && (!unify || mel_in), "vfx_op_from_log: bad argument");
+    for (int b = 0; lens_t && b < B; ++b)
+      VFX_CHECK(lens_t[b] >= 1 && lens_t[b] <= T, "vfx_op_from_log: clip %d has %d frames (need 1 .. T = %d)", b, lens_t[b], T);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    float* sums = static_cast<float*>(sc.blob.alloc(2 * (size_t)B * sizeof(float)));
+    launch_from_log(logmel, mel_in, B, T, unify ? 1 : 0, sums, mel_out, s, upload_lens(sc.blob, lens_t, B));
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_voc_prep(vfx_handle* h, const float* mel, int B, int T, int Tp, const int* lens_t, float* cond, void* stream) {
+  try {
+    VFX_CHECK(h && mel && cond && B > 0 && T > 0 && Tp >= T, "vfx_op_voc_prep: bad argument");
+    VFX_CHECK(h->cfg.n_mels == 128 && h->fe.voc_inv_weight, "vfx_op_voc_prep: the handle has no band weights");
+    for (int b = 0; lens_t && b < B; ++b)
+      VFX_CHECK(lens_t[b] >= 0 && lens_t[b] <= T, "vfx_op_voc_prep: clip %d has %d frames (need 0 .. T = %d)", b, lens_t[b], T);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    launch_voc_prep(mel, B, T, Tp, h->fe.voc_inv_weight, h->cfg.voc_amp_floor, h->cfg.voc_min_db, h->cfg.voc_norm_range, cond, s,
+                    upload_lens(sc.blob, lens_t, B));
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_peak_trim(vfx_handle* h, const float* wav_long, int B, int64_t Llong, int L, const float* peak, const int* lens_l,
+                                const int* lens_tp, float* out, void* stream) {
+  try {
+    VFX_CHECK(h && wav_long && peak && out && B > 0 && L > 0 && Llong >= L && (!lens_l == !lens_tp), "vfx_op_peak_trim: bad argument");
+    const int hop = h->cfg.hop;
+    for (int b = 0; lens_l && b < B; ++b)  // the clip's vocoder output lies inside its row, and its centre crop inside that
+      VFX_CHECK(lens_l[b] >= 0 && lens_l[b] <= L && (int64_t)lens_tp[b] * hop <= Llong && (int64_t)lens_tp[b] * hop >= lens_l[b],
+                "vfx_op_peak_trim: clip %d: %d samples from %d vocoder frames do not fit (L = %d, Llong = %lld)", b, lens_l[b], lens_tp[b],
+                L, (long long)Llong);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const float* d_peak = sc.blob.upload(peak, B);
+    if (lens_l)
+      launch_peak_trim_varlen(wav_long, B, Llong, L, hop, upload_lens(sc.blob, lens_l, B), upload_lens(sc.blob, lens_tp, B), d_peak, out,
+                              s, h->d_flags);
+    else
+      launch_peak_trim(wav_long, B, Llong, L, d_peak, out, s, h->d_flags);
+    VFX_HIP(hipStreamSynchronize(s));
   } catch (const vfx::Error&) {
     return 1;
   }

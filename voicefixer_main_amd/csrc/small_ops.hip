@@ -399,16 +399,6 @@ void launch_from_log(const float* logmel, const float* mel_in, int B, int T, int
 }
 
 // Peak normalise (eval_gsr_voicefixer.py:68-70) + trim_center (tools/utils.py:57-70), per clip.
-__global__ void k_absmax(const float* __restrict__ x, int64_t n_per, unsigned* __restrict__ peak) {
-  const int b = blockIdx.y;
-  const float* xb = x + (int64_t)b * n_per;
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_per; i += (int64_t)gridDim.x * 256)
-    m = fmaxf(m, fabsf(xb[i]));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) atomicMax(peak + b, __float_as_uint(m));
-}
-
 __global__ void k_trim_scale(const float* __restrict__ x, int64_t Llong, int L, int off, const unsigned* __restrict__ peak,
                              float* __restrict__ out, int* __restrict__ flags) {
   const int b = blockIdx.y;
@@ -526,18 +516,12 @@ void launch_or_flags(int* flags, int bits, hipStream_t s) {
   VFX_HIP(hipGetLastError());
 }
 
-// `have_peak`: ws[b] already holds the peak of clip b (written by the vocoder tail).
-void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, float* ws, bool have_peak, float* out,
-                      hipStream_t s, int* flags) {
-  if (!have_peak) {
-    VFX_HIP(hipMemsetAsync(ws, 0, sizeof(unsigned) * B, s));
-    const int gx = (int)std::min<int64_t>(64, (Llong + 255) / 256);
-    hipLaunchKernelGGL(k_absmax, dim3(gx, B), dim3(256), 0, s, wav_long, Llong, reinterpret_cast<unsigned*>(ws));
-  }
+// peak[b]: the peak of clip b, written by the vocoder tail.
+void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, const float* peak, float* out, hipStream_t s, int* flags) {
   const int64_t diff = Llong - L;
   const int off = (int)(diff / 2);
   hipLaunchKernelGGL(k_trim_scale, dim3((L + 255) / 256, B), dim3(256), 0, s, wav_long, Llong, L, off,
-                     reinterpret_cast<const unsigned*>(ws), out, flags);
+                     reinterpret_cast<const unsigned*>(peak), out, flags);
   VFX_HIP(hipGetLastError());
 }
 

@@ -567,7 +567,7 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_lowpass(const float
 
 // Frames per wave of the forward kernel: as many as keep the launch at about one round of resident waves
 // (2 workgroups of 4 waves per CU -- 59 KB of LDS -- x 256 CUs), at most 32.
-static int frames_per_group(int64_t frames) {
+int frames_per_group(int64_t frames) {
   const int64_t f = (frames + 2047) / 2048;
   return (int)std::max<int64_t>(1, std::min<int64_t>(32, f));
 }
@@ -593,10 +593,7 @@ void launch_mel_project(const FrontEndTables& t, const float* sp, int64_t rows, 
 
 // The inverse's launch geometry: IH hops per workgroup, and the groups that cover the positions [0, 1024 + L) of the un-trimmed
 // overlap-add buffer
-struct IstftGrid {
-  int IH, span, groups;
-};
-static IstftGrid istft_grid(int B, int T, int L, int hop) {
+IstftGrid istft_grid(int B, int T, int L, int hop) {
   IstftGrid g;
   g.IH = (int64_t)B * T >= 4096 ? 16 : 2;
   g.span = g.IH * hop;

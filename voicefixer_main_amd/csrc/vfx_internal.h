@@ -423,6 +423,13 @@ void launch_istft(const FrontEndTables& t, const float* re, const float* im, int
 // sp * sin, masked, through launch_istft.
 void launch_stft_lowpass(const FrontEndTables& t, const float* wav, int B, int L, int hop, const int* lens, const int* cut,
                          float* out, hipStream_t stream);
+// The launch geometry of the two (host-only; the tests assert the geometry they exercise through these): the frames a wave of
+// k_stft_mel walks for a launch of `frames` = B * T frames; the hops a workgroup of k_istft / k_stft_lowpass owns and the groups per clip
+int frames_per_group(int64_t frames);
+struct IstftGrid {
+  int IH, span, groups;
+};
+IstftGrid istft_grid(int B, int T, int L, int hop);
 
 void launch_prep_logmel(const float* mel_linear, int B, int T, int Tpad, float* x, int* flags, hipStream_t s,
                         const int* lens_t = nullptr);  // lens_t: frames per clip of a varlen batch (device, [B])
@@ -447,8 +454,9 @@ void launch_peak_trim_varlen(const float* wav_long, int B, int64_t Llong, int L,
                              const float* peak, float* out, hipStream_t s, int* flags);
 void launch_from_log(const float* logmel, const float* mel_in, int B, int T, int unify, float* sums, float* mel_out,
                      hipStream_t s, const int* lens_t = nullptr);
-void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, float* ws, bool have_peak, float* out,
-                      hipStream_t s, int* flags = nullptr);  // flags: VFX_FLAG_PEAK_NORMALISED when a clip was divided by its peak
+// peak (device, [B]): each clip's peak as the vocoder tail left it; flags: VFX_FLAG_PEAK_NORMALISED when a clip was divided by its peak
+void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, const float* peak, float* out, hipStream_t s,
+                      int* flags = nullptr);
 void launch_spectral_metrics(const float* est, const float* tgt, int B, int T, int F, double* ws, float* out, hipStream_t s);
 
 // score.hip: the scores of vfx_audio_metrics.  Per-clip partial sums (float64) in ws; lens = samples, frames = rows per clip (device)

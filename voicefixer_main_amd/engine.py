@@ -848,17 +848,96 @@ class Engine:
             _ptr(y), _ptr(ya), self._stream()), "vfx_op_voc_conv1d")
         return y, ya
 
-    def op_voc_final(self, x, weight, bias, slope=0.2, x_f16=False, lens=None):
-        """The vocoder tail on x (B, T, C): -> wav (B, T), NaN where nothing was written."""
+    def op_voc_final(self, x, weight, bias, slope=0.2, x_f16=False, lens=None, want_peak=False):
+        """The vocoder tail on x (B, T, C): -> wav (B, T), NaN where nothing was written.  want_peak: -> (wav, peak (B,)), the per-clip
+        max |wav| the tail hands the peak normalisation (starts as NaN)."""
         x = _dev_f32(x, self.device)
         B, T, C = x.shape
         w = _host(weight)
         wav = torch.full((B, T), float("nan"), device=self.device)
+        peak = torch.full((B,), float("nan"), device=self.device) if want_peak else None
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
         _lib.check(_lib.load_test().vfx_op_voc_final(
-            self.h, _ptr(x), B, T, C, _hptr(w), float(bias), float(slope), int(bool(x_f16)), _hptr(ln), _ptr(wav), self._stream()),
-            "vfx_op_voc_final")
+            self.h, _ptr(x), B, T, C, _hptr(w), float(bias), float(slope), int(bool(x_f16)), _hptr(ln), _ptr(wav), _ptr(peak),
+            self._stream()), "vfx_op_voc_final")
+        return (wav, peak) if want_peak else wav
+
+    # the STFT / ISTFT front end and the glue launches of a restore call (include/vfx_test.h); every output starts as NaN
+    @staticmethod
+    def _lens_arg(lens, B, name):
+        if lens is None:
+            return None
+        lens = [int(v) for v in lens]
+        if len(lens) != B:
+            raise ValueError("%s: %d lengths for %d clips" % (name, len(lens), B))
+        return (ctypes.c_int * B)(*lens)
+
+    def op_stft(self, wav, T=None, lens=None, eps=1e-8, log10_mel=False, want=("mel", "sp", "cos", "sin")):
+        """launch_stft_mel on wav (B, L): -> dict of the outputs named in `want`, mel (B, T, 128), sp / cos / sin (B, T, 1025).  T: the row
+        stride of the outputs (default frames(L)); lens: samples per clip, as the varlen callers pass them."""
+        wav = _dev_f32(wav, self.device)
+        B, L = wav.shape
+        T = self.frames(L) if T is None else int(T)
+        out = {k: torch.full((B, T, N_MELS if k == "mel" else N_BINS), float("nan"), device=self.device) for k in want}
+        _lib.check(_lib.load_test().vfx_op_stft(
+            self.h, _ptr(wav), B, L, T, self._lens_arg(lens, B, "op_stft"), float(eps), int(bool(log10_mel)), _ptr(out.get("mel")),
+            _ptr(out.get("sp")), _ptr(out.get("cos")), _ptr(out.get("sin")), self._stream()), "vfx_op_stft")
+        return out
+
+    def op_istft(self, re, im, length, lens=None):
+        """launch_istft on re, im (B, T, 1025): -> wav (B, length); lens: samples per clip."""
+        re, im = _dev_f32(re, self.device), _dev_f32(im, self.device)
+        B, T, _ = re.shape
+        wav = torch.full((B, int(length)), float("nan"), device=self.device)
+        _lib.check(_lib.load_test().vfx_op_istft(self.h, _ptr(re), _ptr(im), B, T, int(length), self._lens_arg(lens, B, "op_istft"),
+                                                 _ptr(wav), self._stream()), "vfx_op_istft")
         return wav
+
+    @staticmethod
+    def plan_stft_frames_per_group(frames):
+        """Host-only: the frames one wave of k_stft_mel walks in a launch of `frames` = B * T frames.  Needs no GPU."""
+        return int(_lib.load_test().vfx_plan_stft_frames_per_group(int(frames)))
+
+    @staticmethod
+    def plan_istft_grid(B, T, L):
+        """Host-only: (IH, workgroups per clip) of the k_istft launch for (B, T, L).  Needs no GPU."""
+        out = (ctypes.c_int * 2)()
+        _lib.check(_lib.load_test().vfx_plan_istft_grid(int(B), int(T), int(L), out), "vfx_plan_istft_grid")
+        return out[0], out[1]
+
+    def op_from_log(self, logmel, mel_in=None, unify=False, lens_t=None):
+        """launch_from_log on logmel (B, T, 128) (and mel_in, the target of unify): -> mel_out (B, T, 128)."""
+        logmel = _dev_f32(logmel, self.device)
+        mel_in = None if mel_in is None else _dev_f32(mel_in, self.device)
+        B, T, _ = logmel.shape
+        out = torch.full_like(logmel, float("nan"))
+        _lib.check(_lib.load_test().vfx_op_from_log(self.h, _ptr(logmel), _ptr(mel_in), B, T, int(bool(unify)),
+                                                    self._lens_arg(lens_t, B, "op_from_log"), _ptr(out), self._stream()),
+                   "vfx_op_from_log")
+        return out
+
+    def op_voc_prep(self, mel, Tp, lens_t=None):
+        """launch_voc_prep on mel (B, T, 128) linear: -> cond (B, Tp, 128)."""
+        mel = _dev_f32(mel, self.device)
+        B, T, _ = mel.shape
+        cond = torch.full((B, int(Tp), N_MELS), float("nan"), device=self.device)
+        _lib.check(_lib.load_test().vfx_op_voc_prep(self.h, _ptr(mel), B, T, int(Tp), self._lens_arg(lens_t, B, "op_voc_prep"),
+                                                    _ptr(cond), self._stream()), "vfx_op_voc_prep")
+        return cond
+
+    def op_peak_trim(self, wav_long, L, peak, lens_l=None, lens_tp=None):
+        """launch_peak_trim (launch_peak_trim_varlen with lens_l, lens_tp) on wav_long (B, Llong) and the per-clip peaks (host): ->
+        out (B, L).  The flag a division raises stays in the handle's flag word for take_flags()."""
+        wav_long = _dev_f32(wav_long, self.device)
+        B, Llong = wav_long.shape
+        pk = _host(peak)
+        if pk.shape != (B,):
+            raise ValueError("op_peak_trim: %s peaks for %d clips" % (pk.shape, B))
+        out = torch.full((B, int(L)), float("nan"), device=self.device)
+        _lib.check(_lib.load_test().vfx_op_peak_trim(
+            self.h, _ptr(wav_long), B, Llong, int(L), _hptr(pk), self._lens_arg(lens_l, B, "op_peak_trim"),
+            self._lens_arg(lens_tp, B, "op_peak_trim"), _ptr(out), self._stream()), "vfx_op_peak_trim")
+        return out
 
     # the ResUNet plans' launches, one piece at a time, built by the plan's own builder (include/vfx_test.h: vfx_op_unet_piece)
     UNET_LAUNCH_FAMILIES = ("small", "k_conv", "k_conv_phased", "k_resblock", "k_resblock_in1", "k_resblock_two_src", "k_block2d32")
