@@ -271,6 +271,32 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
                  const float* taps, int ntaps, float* y, int64_t ldy, int64_t o0, int64_t n_out, void* stream);
 
 /*
+ * vfx_resample with a rate pair per clip, for float32 and float64 clips and any pair with max(up, down) <= 65536 after the gcd (what
+ * the "stft" low-pass of the degradation simulator, tools/dsp/lowpass.py:135-146, needs at 44.1 / 48 kHz: a drawn cut-off c resamples
+ * to int(c / 22050 * 44100) Hz and back).  Row b is scipy.signal.resample_poly(clip b, up, down) of design pair_index[b], bit for bit:
+ * the recurrence above in the clip's dtype T, one rounding per product and per sum, with h = fl_T(g T(up)) -- scipy's `h *= up` -- where
+ * g = firwin(20 M + 1, 1 / M, window=('kaiser', 5.0)).astype(T), M = max(up, down) after the gcd.  Finite input is the contract.
+ *   x (B, ldx) device, float32 (x_f64 = 0) or float64 (1); clip b = the first lens_in[b] samples of row b (HOST int64[B], >= 0);
+ *   pair_index HOST int[B], 0 <= pair_index[b] < F;  up, down HOST int[F], as given (reduced inside);  1 <= B, F <= 128;
+ *   taps DEVICE, x's dtype: the UNSCALED g of every design back to back; taps_at HOST int64[F]: the element design f starts at (the
+ *   down and the up step of one cut-off share M, so they may share one g; not read for a design with up == down after the gcd);
+ *   y (B, ldy) device, x's dtype: row b receives outputs [0, n_out), zeros at or past vfx_resample_each_out_len(lens_in[b]); a clip
+ *   of a design with up == down is copied.
+ * The taps are read from global memory: a call scales each design into a buffer of the handle, phase-major (row phi holds
+ * h[phi + j up], so a lane reads one contiguous run), then one launch takes all clips.  The clip and design tables are uploaded on
+ * `stream` into a buffer of the handle, grown on demand, so a call is no subject for hipGraph capture.  Fails, launching nothing and
+ * leaving y as it is, for a NULL pointer, B or F out of range, an index outside [0, F), a negative length or one past ldx, n_out
+ * past ldy, rates <= 0, or a pair past the cap (the message names the clip and its reduced pair).
+ * vfx_resample_each_out_len: ceil(n_in up / down) after the gcd; -1 for up or down <= 0, max(up, down) > 65536 after the gcd, or
+ *   n_in outside [0, 2^46].
+ * vfx_resample, vfx_resample_out_len and vfx_resample_window keep their own, narrower set of pairs.
+ */
+int64_t vfx_resample_each_out_len(int64_t n_in, int up, int down);
+int vfx_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lens_in, const int* pair_index,
+                      const int* up, const int* down, const void* taps, const int64_t* taps_at, int F, void* y, int64_t ldy, int64_t n_out,
+                      void* stream);
+
+/*
  * Zero-phase IIR filtering of a padded batch of clips: scipy.signal.sosfiltfilt(sos, x) per clip (the degradation simulator's
  * low-pass and band-pass, tools/dsp/lowpass.py:58-133), bit for bit, for float32 and float64 input.
  *   x (B, ldx) device, float32 (x_f64 = 0) or float64 (x_f64 = 1); clip b = the first lengths[b] samples of row b (HOST int64[B]);

@@ -183,6 +183,9 @@ int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, in
  * Synchronises. */
 int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int up, int down,
                       const double* taps, int ntaps, int stage, double* out, int64_t out_n, int* iout, int64_t iout_n, void* stream);
+/* Debug switch of a handle, for measurements: natural != 0 makes vfx_resample_each keep its scaled taps in natural order instead of
+ * phase-major (the same sums in the same order: every result bit stays; only the memory the tap reads touch changes). */
+int vfx_debug_resample_each_layout(vfx_handle* h, int natural);
 
 #ifdef __cplusplus
 }

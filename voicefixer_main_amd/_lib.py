@@ -56,6 +56,9 @@ SIGNATURES = {
     "vfx_resample_window": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "vfx_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_int,
                              c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "vfx_resample_each_out_len": (c_int64, [c_int64, c_int, c_int]),
+    "vfx_resample_each": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                  c_void_p, POINTER(c_int64), c_int, c_void_p, c_int64, c_int64, c_void_p]),
     "vfx_sosfiltfilt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(ctypes.c_double), c_int,
                                 POINTER(ctypes.c_double), c_int, c_void_p, c_int64, c_void_p]),
     "vfx_sosfiltfilt_bank": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int),
@@ -129,6 +132,7 @@ TEST_SIGNATURES = {
     "vfx_op_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_stoi_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "vfx_debug_resample_each_layout": (c_int, [c_void_p, c_int]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // api.cpp -- error text, the stream turns and the extern "C" entry points of libvfx.so.
 #include <cstring>
 #include <cstdlib>
+#include <numeric>
 
 #include "vfx_internal.h"
 
@@ -453,6 +454,49 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
               (long long)o0, (long long)(o0 + n_out), (long long)k0, (long long)k1, (long long)x0, (long long)(x0 + Lx));
   }
   launch_resample(x, B, ldx, x0, Lx, lens_in, p, taps, y, ldy, o0, n_out, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+int64_t vfx_resample_each_out_len(int64_t n_in, int up, int down) {
+  ResamplePair p;
+  if (n_in < 0 || n_in > ((int64_t)1 << 46) || !resample_each_reduce(up, down, &p)) return -1;
+  return resample_out_len(n_in, p);
+}
+
+int vfx_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lens_in, const int* pair_index,
+                      const int* up, const int* down, const void* taps, const int64_t* taps_at, int F, void* y, int64_t ldy, int64_t n_out,
+                      void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lens_in && pair_index && up && down && taps && taps_at && y && (x_f64 == 0 || x_f64 == 1), "vfx_resample_each: bad argument");
+  VFX_CHECK(B >= 1 && B <= kResampleEachMaxClips, "vfx_resample_each: %d clips (need 1 <= B <= %d)", B, kResampleEachMaxClips);
+  VFX_CHECK(F >= 1 && F <= kResampleEachMaxDesigns, "vfx_resample_each: %d designs (need 1 <= F <= %d)", F, kResampleEachMaxDesigns);
+  VFX_CHECK(n_out >= 0 && n_out <= ldy && n_out <= (int64_t)0x7fffffff * kResampleEachBlock && ldx >= 0,
+            "vfx_resample_each: bad n_out (%lld) or row stride (%lld, %lld)", (long long)n_out, (long long)ldx, (long long)ldy);
+  ResamplePair pairs[kResampleEachMaxDesigns];
+  bool taken[kResampleEachMaxDesigns];
+  for (int f = 0; f < F; ++f) {
+    VFX_CHECK(up[f] > 0 && down[f] > 0, "vfx_resample_each: design %d: bad rates %d/%d", f, up[f], down[f]);
+    taken[f] = resample_each_reduce(up[f], down[f], &pairs[f]);
+    VFX_CHECK(!taken[f] || pairs[f].up == pairs[f].down || taps_at[f] >= 0, "vfx_resample_each: design %d: taps_at = %lld", f,
+              (long long)taps_at[f]);
+  }
+  for (int b = 0; b < B; ++b) {
+    const int f = pair_index[b];
+    VFX_CHECK(f >= 0 && f < F, "vfx_resample_each: clip %d asks for design %d of %d", b, f, F);
+    if (!taken[f]) {
+      const int64_t g = std::gcd((int64_t)up[f], (int64_t)down[f]);
+      VFX_CHECK(false, "vfx_resample_each: clip %d: the pair %lld/%lld (reduced) is past the cap max(up, down) <= %d", b,
+                (long long)(up[f] / g), (long long)(down[f] / g), kResampleEachMaxRate);
+    }
+    VFX_CHECK(lens_in[b] >= 0, "vfx_resample_each: clip %d has a negative length", b);
+    VFX_CHECK(lens_in[b] <= ldx && lens_in[b] <= ((int64_t)1 << 46), "vfx_resample_each: clip %d has %lld samples, the rows hold %lld", b,
+              (long long)lens_in[b], (long long)ldx);
+  }
+  for (int f = 0; f < F; ++f)  // (a design past the cap that no clip asks for)
+    VFX_CHECK(taken[f], "vfx_resample_each: design %d: the pair %d/%d is past the cap max(up, down) <= %d after the gcd", f, up[f], down[f],
+              kResampleEachMaxRate);
+  if (n_out > 0)
+    launch_resample_each(h, x, x_f64, B, ldx, lens_in, pair_index, pairs, taps, taps_at, F, y, ldy, n_out, static_cast<hipStream_t>(stream));
   VFX_API_END
 }
 

@@ -1003,6 +1003,12 @@ extern "C" int vfx_op_istft(vfx_handle* h, const float* re, const float* im, int
   return 0;
 }
 
+extern "C" int vfx_debug_resample_each_layout(vfx_handle* h, int natural) {
+  if (!h) return 1;
+  h->rs_natural_taps = natural != 0;
+  return 0;
+}
+
 extern "C" int vfx_plan_stft_frames_per_group(int64_t frames) { return frames > 0 ? frames_per_group(frames) : -1; }
 
 extern "C" int vfx_plan_istft_grid(int B, int T, int L, int* out) {

@@ -164,4 +164,138 @@ void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx,
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The per-clip form: a rate pair per clip, float32 or float64, max(up, down) up to kResampleEachMaxRate (1.3 M taps).  The same
+// recurrence in the clip's dtype T; the taps stay in global memory (L2).  A call first scales the unscaled firwin g of each of its
+// designs, h = fl_T(g T(up)) -- scipy's `h *= up` --, into a buffer of the handle that only grows (k_resample_each_taps), phase-major:
+//
+//   P[phi][j] = h[phi + j up],  0 <= phi < up, rows of J = 2 hl / up + 1
+//
+// With t = n down + hl = q up + phi, the tap of input k is h[t - k up] = P[phi][q - k]: as k rises a lane walks ONE row backwards,
+// where the natural order would touch a cache line per tap.  The order of the sum, and so every bit of it, is the same either way
+// (vfx_handle::rs_natural_taps keeps the natural order selectable for measurements).  One lane per output, kResampleEachBlock
+// outputs of one clip per workgroup; the input is read from global memory as well (a block's span is short and contiguous, and for
+// the down step its size has no bound that LDS could hold).
+// ---------------------------------------------------------------------------------------------------------------------------------
+bool resample_each_reduce(int64_t up, int64_t down, ResamplePair* out) {
+  if (up <= 0 || down <= 0) return false;
+  const int64_t g = gcd64(up, down);
+  up /= g;
+  down /= g;
+  if (std::max(up, down) > kResampleEachMaxRate) return false;
+  out->up = (int)up;
+  out->down = (int)down;
+  out->hl = 10 * (int)std::max(up, down);
+  out->R = 0;
+  return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_resample_each_taps(const T* __restrict__ g, T* __restrict__ P,
+                                                            const ResampleEachDesign* __restrict__ designs, int natural) {
+#pragma clang fp contract(off)
+  const ResampleEachDesign d = designs[blockIdx.y];
+  const T scale = (T)d.up;  // exact: up <= 65536
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < d.ntaps; i += gridDim.x * 256) {
+    const int64_t at = natural ? (int64_t)i : (int64_t)(i % d.up) * d.J + i / d.up;  // i / up <= 2 hl / up = J - 1
+    P[d.dst + at] = g[d.src + i] * scale;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kResampleEachBlock) void k_resample_each(const T* __restrict__ x, const T* __restrict__ P, T* __restrict__ y,
+                                                                      const ResampleEachClip* __restrict__ clips, int64_t n_out,
+                                                                      int natural) {
+#pragma clang fp contract(off)
+  const ResampleEachClip c = clips[blockIdx.y];
+  const int64_t n = (int64_t)blockIdx.x * kResampleEachBlock + threadIdx.x;
+  if (n >= n_out) return;
+  T acc = (T)0;
+  if (n < c.len_out) {
+    const T* xb = x + c.x_at;
+    if (c.up == c.down) {  // the same rate: a copy (len_out = len_in)
+      acc = xb[n];
+    } else {
+      const int64_t t = n * c.down + c.hl;  // < 2^63: n down < (len_in + 1) up
+      const int64_t q = t / c.up;           // the one division of the output
+      const int phi = (int)(t - q * c.up);
+      const int jmax = (2 * c.hl - phi) / c.up;  // t - k up <= 2 hl  <=>  q - k <= jmax  (phi < up <= 2 hl)
+      const int64_t k_lo = max(q - jmax, (int64_t)0);
+      const int64_t k_hi = min(q, c.len_in - 1);  // t - k up >= 0  <=>  k <= q
+      const int cnt = (int)max(k_hi - k_lo + 1, (int64_t)0);  // <= jmax + 1
+      const T* xp = xb + k_lo;                                // k in [0, len_in)
+      // the tap of k_lo + i is row phi's entry j - i, j = q - k_lo in [cnt - 1, jmax]; natural order: h[phi + (j - i) up] <= h[2 hl]
+      const int64_t step = natural ? c.up : 1;
+      const T* tp = P + c.taps_at + (natural ? (int64_t)phi : (int64_t)phi * c.J) + (q - k_lo) * step;
+#pragma unroll 4
+      for (int i = 0; i < cnt; ++i) {
+        const T p = xp[i] * tp[-(int64_t)i * step];  // two roundings, never an FMA (contract off): scipy's order and arithmetic
+        acc = acc + p;
+      }
+    }
+  }
+  y[c.y_at + n] = acc;
+}
+
+void launch_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lens_in, const int* pair_index,
+                          const ResamplePair* pairs, const void* taps, const int64_t* taps_at, int F, void* y, int64_t ldy, int64_t n_out,
+                          hipStream_t s) {
+  const size_t esize = x_f64 ? sizeof(double) : sizeof(float);
+  const int natural = h->rs_natural_taps ? 1 : 0;
+  const size_t designs_bytes = (size_t)F * sizeof(ResampleEachDesign), table_bytes = designs_bytes + (size_t)B * sizeof(ResampleEachClip);
+  char* const host = h->rs_table.stage(h, table_bytes);
+  ResampleEachDesign* const designs = reinterpret_cast<ResampleEachDesign*>(host);
+  ResampleEachClip* const clips = reinterpret_cast<ResampleEachClip*>(host + designs_bytes);
+  size_t elems = 0;
+  int max_ntaps = 0;
+  for (int f = 0; f < F; ++f) {
+    const ResamplePair& p = pairs[f];
+    ResampleEachDesign& d = designs[f];
+    d = ResampleEachDesign{};
+    d.up = p.up;
+    d.J = 2 * p.hl / p.up + 1;
+    d.ntaps = p.up == p.down ? 0 : 2 * p.hl + 1;  // the same rate: no filter, taps_at[f] is not read
+    d.src = d.ntaps ? taps_at[f] : 0;
+    d.dst = (int64_t)elems;
+    if (d.ntaps) elems += ((size_t)p.up * d.J + 63) / 64 * 64;  // >= ntaps in either order: up J >= 2 hl + 1
+    max_ntaps = std::max(max_ntaps, d.ntaps);
+  }
+  for (int b = 0; b < B; ++b) {
+    const int f = pair_index[b];
+    const ResamplePair& p = pairs[f];
+    ResampleEachClip& c = clips[b];
+    c = ResampleEachClip{};
+    c.x_at = (int64_t)b * ldx;
+    c.y_at = (int64_t)b * ldy;
+    c.len_in = lens_in[b];
+    c.len_out = ceil_div(lens_in[b] * p.up, p.down);
+    c.taps_at = designs[f].dst;
+    c.up = p.up;
+    c.down = p.down;
+    c.hl = p.hl;
+    c.J = designs[f].J;
+  }
+  // the scaled taps of the call's designs: at most 21 * 65536 elements each (11 MB in float64), 128 designs
+  char* const P = elems ? h->rs_taps.ensure(h, elems * esize, 0) : nullptr;
+  const char* const dev = h->rs_table.upload(table_bytes, s);
+  const ResampleEachDesign* const d_designs = reinterpret_cast<const ResampleEachDesign*>(dev);
+  const ResampleEachClip* const d_clips = reinterpret_cast<const ResampleEachClip*>(dev + designs_bytes);
+  const dim3 taps_grid((unsigned)std::min((max_ntaps + 255) / 256, 1024), (unsigned)F);
+  const dim3 grid((unsigned)((n_out + kResampleEachBlock - 1) / kResampleEachBlock), (unsigned)B);  // the caller has bounded n_out
+  if (x_f64) {
+    if (max_ntaps)
+      hipLaunchKernelGGL(k_resample_each_taps<double>, taps_grid, dim3(256), 0, s, static_cast<const double*>(taps),
+                         reinterpret_cast<double*>(P), d_designs, natural);
+    hipLaunchKernelGGL(k_resample_each<double>, grid, dim3(kResampleEachBlock), 0, s, static_cast<const double*>(x),
+                       reinterpret_cast<const double*>(P), static_cast<double*>(y), d_clips, n_out, natural);
+  } else {
+    if (max_ntaps)
+      hipLaunchKernelGGL(k_resample_each_taps<float>, taps_grid, dim3(256), 0, s, static_cast<const float*>(taps),
+                         reinterpret_cast<float*>(P), d_designs, natural);
+    hipLaunchKernelGGL(k_resample_each<float>, grid, dim3(kResampleEachBlock), 0, s, static_cast<const float*>(x),
+                       reinterpret_cast<const float*>(P), static_cast<float*>(y), d_clips, n_out, natural);
+  }
+  VFX_HIP(hipGetLastError());
+}
+
 }  // namespace vfx

@@ -538,6 +538,31 @@ struct ResampleArgs {
 void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx, const int64_t* lens_in, const ResamplePair& p,
                      const float* taps, float* y, int64_t ldy, int64_t o0, int64_t n_out, hipStream_t s);
 
+// The per-clip form (k_resample_each): a rate pair per clip, float32 or float64, the taps in global memory.
+constexpr int kResampleEachMaxClips = 128;     // clips per call: their parameters travel in a device table
+constexpr int kResampleEachMaxDesigns = 128;
+constexpr int kResampleEachMaxRate = 65536;    // max(up, down) after the gcd: what 44.1 / 48 kHz "stft" cut-offs need
+constexpr int kResampleEachBlock = 256;        // outputs per workgroup, one per lane
+struct ResampleEachDesign {  // one design of the call, for k_resample_each_taps
+  int64_t src, dst;          // elements: the unscaled firwin in the caller's taps, the scaled copy in the handle's buffer
+  int up, ntaps, J, pad_;    // J = 2 hl / up + 1: the row length of the phase-major copy
+};
+struct ResampleEachClip {    // one clip of the call, for k_resample_each
+  int64_t x_at, y_at;        // elements: the clip's input and output row
+  int64_t len_in, len_out;
+  int64_t taps_at;           // elements: its design's scaled copy
+  int up, down, hl, J;
+  int64_t pad_;
+};
+// up / down reduced by their gcd, hl = 10 max(up, down); false for up or down <= 0 or max(up, down) > kResampleEachMaxRate after it
+bool resample_each_reduce(int64_t up, int64_t down, ResamplePair* out);
+// x, y (x's dtype), taps (x's dtype): device; lens_in, pair_index (B), pairs (F, reduced), taps_at (F): HOST.  The caller has checked
+// 1 <= B <= kResampleEachMaxClips, 1 <= F <= kResampleEachMaxDesigns, the indices, 0 <= lens_in[b] <= ldx and 0 < n_out <= ldy.
+// y[b, n] for n < n_out: resample_poly's output n of clip b, zero at or past the clip's output length.
+void launch_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lens_in, const int* pair_index,
+                          const ResamplePair* pairs, const void* taps, const int64_t* taps_at, int F, void* y, int64_t ldy, int64_t n_out,
+                          hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // zero-phase IIR filter (sosfilt.hip): scipy.signal.sosfiltfilt's arithmetic, bit for bit
 // ---------------------------------------------------------------------------------------------
@@ -853,6 +878,9 @@ struct vfx_handle {
   vfx::GrowBuffer sos_ws;    // vfx_sosfiltfilt's forward pass over the extended clips (float64)
   vfx::StagedUpload sos_bank;  // vfx_sosfiltfilt_bank's designs: coefficients and zi of every section (sosfilt_pack_bank)
   vfx::GrowBuffer mix_ws;   // vfx_mix_noise's per-clip peaks, level ratios and chunk sums
+  vfx::GrowBuffer rs_taps;  // vfx_resample_each's scaled taps of the designs of a call (at most 11 MB per design)
+  vfx::StagedUpload rs_table;  // vfx_resample_each's design and clip tables
+  bool rs_natural_taps = false;  // debug switch (vfx_debug_resample_each_layout): the scaled taps in natural order, not phase-major
   float* d_ones = nullptr;   // identity prologue tables (kIdentityLen floats)
   float* d_zeros = nullptr;
   vfx::ConvProfile prof;

@@ -3,6 +3,7 @@
 All compute happens in the HIP library; this file only allocates outputs with torch,
 passes raw device pointers + the current HIP stream, and raises on any failure.
 """
+import collections
 import ctypes
 import math
 
@@ -82,6 +83,7 @@ class Engine:
         self.analysis_model = MODEL_UNET_MEL   # what restore_gsr(_varlen) runs (select_analysis)
         self._resample_taps = {}   # (up, down) -> the filter of resample_poly on the device
         self._stoi_taps = {}       # (up, down) -> Octave's resample filter (float64) on the device, for `stoi`
+        self._resample_each_cache = collections.OrderedDict()   # (M, dtype) -> resample_poly's unscaled filter on the device, LRU
 
     def close(self):
         if getattr(self, "_strict", None) is not None:
@@ -417,6 +419,112 @@ class Engine:
                 lens = (ctypes.c_int64 * B)(*lengths)
                 _lib.check(self.lib.vfx_resample(self.h, _ptr(x), B, L, x0, L, lens, up, down, _ptr(taps), taps.numel(), _ptr(y),
                                                  int(n_out), o0, int(n_out), self._stream()), "vfx_resample")
+        return (y[0], out_lengths[0]) if squeeze else (y, out_lengths)
+
+    # ------------------------------------------------------------------ resampling with a rate pair per clip (the "stft" low-pass)
+    MAX_RESAMPLE_EACH_CLIPS = 128
+    RESAMPLE_EACH_CACHE_BYTES = 256 << 20
+
+    @staticmethod
+    def resample_each_out_len(n_in, sr_in, sr_out):
+        """len(resample_poly(x[:n_in], up, down)); -1 for a pair past `resample_each`'s cap (vfx_resample_each_out_len)."""
+        up, down = Engine.resample_ratio(sr_in, sr_out)
+        if not (0 < up < 1 << 31 and 0 < down < 1 << 31):
+            return -1
+        return int(_lib.load().vfx_resample_each_out_len(int(n_in), up, down))
+
+    @staticmethod
+    def resample_each_supported(sr_in, sr_out):
+        """True when `resample_each` takes sr_in -> sr_out: both rates positive and max(up, down) <= 65536 after the gcd."""
+        return int(sr_in) > 0 and int(sr_out) > 0 and Engine.resample_each_out_len(1, sr_in, sr_out) >= 0
+
+    def _resample_each_taps(self, ms, dtype):
+        """The unscaled filters of resample_poly for the rates `ms` (M = max(up, down)): firwin(20 M + 1, 1 / M, ("kaiser", 5.0)) from
+        SciPy on the host, in `dtype`, cached on the device per (M, dtype) -- the down and the up step of a cut-off share one.  The
+        cache is bounded: past RESAMPLE_EACH_CACHE_BYTES (256 MiB) the least recently used designs go, never one of `ms`.
+        -> (one device tensor holding the filters of `ms` back to back, {M: its first element})."""
+        cache = self._resample_each_cache
+        np_dtype = np.float32 if dtype == torch.float32 else np.float64
+        for m in ms:
+            key = (m, dtype)
+            if key in cache:
+                cache.move_to_end(key)
+            else:
+                from scipy.signal import firwin
+                cache[key] = torch.from_numpy(firwin(2 * 10 * m + 1, 1.0 / m, window=("kaiser", 5.0)).astype(np_dtype)).to(self.device)
+        needed = {(m, dtype) for m in ms}
+        total = sum(t.numel() * t.element_size() for t in cache.values())
+        for key in [k for k in cache if k not in needed]:      # oldest first
+            if total <= self.RESAMPLE_EACH_CACHE_BYTES:
+                break
+            t = cache.pop(key)
+            total -= t.numel() * t.element_size()
+        parts = [cache[(m, dtype)] for m in ms]
+        at, n = {}, 0
+        for m, t in zip(ms, parts):
+            at[m] = n
+            n += t.numel()
+        if not parts:
+            return torch.zeros(1, device=self.device, dtype=dtype), at
+        return (parts[0] if len(parts) == 1 else torch.cat(parts)), at
+
+    def resample_each(self, x, sr_in, sr_out, lengths=None, n_out=None, _y=None):
+        """scipy.signal.resample_poly(clip b, up_b, down_b) with a rate pair per clip, on the device, bit for bit, in the clips' dtype:
+        x (B, L) or (L,), float32 or float64 (any other dtype raises TypeError: SciPy treats integer input differently, which stays
+        with the caller) -> (y, out_lengths), y of x's dtype.
+
+        sr_in / sr_out: each an int or one int per clip; any pair with max(up, down) <= 65536 after the gcd (`resample_each_supported`;
+        RuntimeError naming the clip and its pair otherwise), the same rate included (a copy).  lengths: each clip's true length
+        (default L).  y (B, n_out) -- n_out defaults to the longest output -- holds row b's first n_out outputs, zeros at or past
+        out_lengths[b] = ceil(lengths[b] up_b / down_b).  The distinct reduced pairs of a call are its designs; B > 128 is cut into
+        calls of 128.  The unscaled filters come from SciPy's firwin on the host and are cached on the device per (M, dtype), least
+        recently used evicted past RESAMPLE_EACH_CACHE_BYTES = 256 MiB (`_resample_each_taps`).  1-D x gives a 1-D y and an int."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError("resample_each: clips must be float32 or float64, got %s" % x.dtype)
+        if x.dim() not in (1, 2):
+            raise ValueError("resample_each: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
+        x, squeeze, B, L, lengths = _clip_rows(x.to(self.device).contiguous(), lengths, "resample_each")
+        if B and (min(lengths) < 0 or max(lengths) > L):
+            raise ValueError("resample_each: clips of %d .. %d samples in rows of %d" % (min(lengths), max(lengths), L))
+
+        def per_clip(v, name):
+            v = [int(v)] * B if np.ndim(v) == 0 else [int(r) for r in v]
+            if len(v) != B:
+                raise ValueError("resample_each: %d %s for %d clips" % (len(v), name, B))
+            if any(r <= 0 for r in v):
+                raise ValueError("resample_each: %s must be positive" % name)
+            return v
+
+        sr_in, sr_out = per_clip(sr_in, "sr_in"), per_clip(sr_out, "sr_out")
+        pairs = [self.resample_ratio(i, o) for i, o in zip(sr_in, sr_out)]
+        for b, (up, down) in enumerate(pairs):
+            if max(up, down) > 65536:
+                raise RuntimeError("resample_each: clip %d: %d Hz -> %d Hz is the pair %d/%d, past the cap max(up, down) <= 65536"
+                                   % (b, sr_in[b], sr_out[b], up, down))
+        out_lengths = [-((-n * up) // down) for n, (up, down) in zip(lengths, pairs)]
+        n_out = max(out_lengths, default=0) if n_out is None else int(n_out)
+        if n_out < 0:
+            raise ValueError("resample_each: n_out = %d" % n_out)
+        if _y is None:      # (the kernel writes every element of y: zeros at or past a clip's output length)
+            _y = torch.empty((B, n_out), device=self.device, dtype=x.dtype)
+        elif _y.shape != (B, n_out) or _y.dtype != x.dtype or not _y.is_contiguous() or _y.device != x.device:
+            raise ValueError("resample_each: _y must be a contiguous (%d, %d) %s tensor on %s" % (B, n_out, x.dtype, x.device))
+        y = _y
+        if L == 0:
+            y.zero_()
+        for b0 in range(0, B if n_out and L else 0, self.MAX_RESAMPLE_EACH_CLIPS):
+            chunk = pairs[b0:b0 + self.MAX_RESAMPLE_EACH_CLIPS]
+            designs = sorted(set(chunk))
+            taps, at = self._resample_each_taps(sorted({max(p) for p in designs if p[0] != p[1]}), x.dtype)
+            nb, F = len(chunk), len(designs)
+            _lib.check(self.lib.vfx_resample_each(
+                self.h, _ptr(x[b0:]), int(x.dtype == torch.float64), nb, L, (ctypes.c_int64 * nb)(*lengths[b0:b0 + nb]),
+                (ctypes.c_int * nb)(*[designs.index(p) for p in chunk]), (ctypes.c_int * F)(*[p[0] for p in designs]),
+                (ctypes.c_int * F)(*[p[1] for p in designs]), _ptr(taps),
+                (ctypes.c_int64 * F)(*[at.get(max(p), 0) if p[0] != p[1] else 0 for p in designs]), F, _ptr(y[b0:]), n_out, n_out,
+                self._stream()), "vfx_resample_each")
         return (y[0], out_lengths[0]) if squeeze else (y, out_lengths)
 
     # ------------------------------------------------------------------ zero-phase IIR filter (scipy.signal.sosfiltfilt)

@@ -195,13 +195,12 @@ def _sosfiltfilt_list(clips, sos, engine, to_host):
     return out
 
 
-def _stft_list(clips, ratio, engine, to_host, fs_ori=44100):
-    """`_type="stft"` for a list: float32 clips whose two rate pairs the device resampler takes go down and up through
-    Engine.resample as padded batches (bit for bit `stft_hard_lowpass`); everything else takes the host function."""
+def _stft_group(clips, ratio, eng, to_host, fs_ori):
+    """`_stft_list` for clips of ONE ratio on an engine without `resample_each`: float32 clips whose two rate pairs `Engine.resample`
+    takes go down and up through it as padded batches; everything else is left to the host (None)."""
     from .engine import Engine
     fs_down = int(ratio * fs_ori)
     on_device = fs_down > 0 and fs_down != fs_ori and Engine.resample_supported(fs_ori, fs_down) and Engine.resample_supported(fs_down, fs_ori)
-    eng = _engine_or_default(engine)
     lengths = [c.shape[0] for c in clips]
     out = [None] * len(clips)
     dev = [i for i in range(len(clips)) if on_device and _clips.is_f32(clips[i]) and lengths[i] > 0]
@@ -213,9 +212,45 @@ def _stft_list(clips, ratio, engine, to_host, fs_ori=44100):
             y = torch.nn.functional.pad(y, (0, lens[-1] - y.shape[1]))
         for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
             out[i] = row
+    return out
+
+
+def _stft_list(clips, ratios, engine, to_host, fs_ori=44100):
+    """`_type="stft"` for a list, ratios[i] the ratio of clip i: bit for bit `stft_hard_lowpass`, item by item.  Non-empty float32 and
+    float64 items (device tensors included, as they are) with 0 < fs_down != fs_ori and a rate pair Engine.resample_each takes are
+    grouped by dtype, sorted by length and cut into batches of MAX_BATCH whatever their cut-offs; a batch costs TWO calls: down with
+    a rate per clip, up with n_out = the batch's longest clip, which is `align_length`'s cut or zero pad (rows are zero past their
+    output length).  Everything else -- other dtypes, empty clips, fs_down <= 0, fs_down == fs_ori, a pair past the cap -- takes the
+    host function.  An engine without `resample_each` keeps the older path: per distinct ratio, float32 clips at the pairs
+    Engine.resample takes go through it, the rest to the host."""
+    eng = _engine_or_default(engine)
+    lengths = [c.shape[0] for c in clips]
+    out = [None] * len(clips)
+    if hasattr(eng, "resample_each"):
+        from .engine import Engine
+        downs = [int(r * fs_ori) for r in ratios]
+        takes = {d: 0 < d != fs_ori and Engine.resample_each_supported(fs_ori, d) and Engine.resample_each_supported(d, fs_ori)
+                 for d in set(downs)}
+        for dtype in (torch.float32, torch.float64):
+            name = str(dtype).split(".")[-1]
+            dev = [i for i in range(len(clips)) if str(clips[i].dtype).endswith(name) and lengths[i] > 0 and takes[downs[i]]]
+            for idx in _clips.batches(dev, lengths, MAX_BATCH):
+                lens = [lengths[i] for i in idx]
+                rates = [downs[i] for i in idx]
+                low, low_lengths = eng.resample_each(_clips.pad([clips[i] for i in idx], eng.device, dtype), fs_ori, rates, lengths=lens)
+                y, _ = eng.resample_each(low, rates, fs_ori, lengths=low_lengths, n_out=lens[-1])
+                for i, row in zip(idx, _clips.unpad(y, lens, to_host)):
+                    out[i] = row
+    else:
+        groups = {}
+        for i, r in enumerate(ratios):
+            groups.setdefault(r, []).append(i)
+        for r, idx in groups.items():
+            for i, y in zip(idx, _stft_group([clips[i] for i in idx], r, eng, to_host, fs_ori)):
+                out[i] = y
     for i in range(len(clips)):
         if out[i] is None:
-            y = stft_hard_lowpass(_clips.as_numpy(clips[i]), lowpass_ratio=ratio, fs_ori=fs_ori)
+            y = stft_hard_lowpass(_clips.as_numpy(clips[i]), lowpass_ratio=ratios[i], fs_ori=fs_ori)
             out[i] = y if to_host else _clips.to_device(y, eng.device)
     return out
 
@@ -255,7 +290,7 @@ def lowpass_list(clips, highcut, fs, order=5, _type="butter", engine=None, to_ho
     if iir:
         return _sosfiltfilt_list(clips, _design(iir[1], int(highcut) / (0.5 * fs), "low", iir[0], "lowpass"), engine, to_host)
     if _type in "stft":
-        return _stft_list(clips, highcut / int(fs / 2), engine, to_host)
+        return _stft_list(clips, [highcut / int(fs / 2)] * len(clips), engine, to_host)
     if _type in "stft_hard":
         return _stft_hard_list(clips, [highcut / int(fs / 2)] * len(clips), engine, to_host)
     raise ValueError("Error: Unexpected filter type " + _type)
@@ -314,7 +349,7 @@ def _filter_each(clips, cuts, fs, orders, types, engine, to_host):
     _check_1d(clips)
     band = len(cuts[0]) == 2 if cuts else False
     nyq = 0.5 * fs
-    designs, keys, design_of, stft, hard = [], {}, {}, {}, []
+    designs, keys, design_of, stft, hard = [], {}, {}, [], []
     for i, (cut, order, _type) in enumerate(zip(cuts, orders, types)):
         iir = _iir_type(_type, order)
         if iir:
@@ -325,7 +360,7 @@ def _filter_each(clips, cuts, fs, orders, types, engine, to_host):
                 designs.append(_design(iir[1], wn if band else wn[0], "band" if band else "low", iir[0], "bandpass" if band else "lowpass"))
             design_of[i] = keys[key]
         elif not band and _type in "stft":
-            stft.setdefault(cut[0], []).append(i)
+            stft.append(i)
         elif not band and _type in "stft_hard":
             hard.append(i)
         else:
@@ -334,8 +369,8 @@ def _filter_each(clips, cuts, fs, orders, types, engine, to_host):
     if design_of:
         for i, y in _sosfiltfilt_each(clips, design_of, designs, engine, to_host).items():
             out[i] = y
-    for highcut, idx in stft.items():
-        for i, y in zip(idx, _stft_list([clips[i] for i in idx], highcut / int(fs / 2), engine, to_host)):
+    if stft:      # one list whatever the cut-offs: a ratio per clip
+        for i, y in zip(stft, _stft_list([clips[i] for i in stft], [cuts[i][0] / int(fs / 2) for i in stft], engine, to_host)):
             out[i] = y
     if hard:
         ys = _stft_hard_list([clips[i] for i in hard], [cuts[i][0] / int(fs / 2) for i in hard], engine, to_host)
@@ -349,8 +384,9 @@ def lowpass_each(clips, highcuts, fs, orders=5, types="butter", engine=None, to_
     item by item, in the caller's order.  `highcuts`, `orders` and `types` are each a scalar or a sequence with one entry per clip;
     per clip the 1-D check, the substring dispatch, int() of the cut-off and the order clamp are `lowpass`'s.  The IIR items are
     designed once per distinct (name, order, cut-off) and go through Engine.sosfiltfilt_bank as padded batches of one dtype, ONE
-    launch pair per batch whatever its designs; "stft" items go through the device resampler grouped by cut-off (`lowpass_list`'s
-    rule for which), "stft_hard" items through Engine.stft_lowpass as padded batches with a cut-off bin per clip (`_stft_hard_list`).
+    launch pair per batch whatever its designs; "stft" items go through Engine.resample_each as padded batches with a rate pair per
+    clip, two calls per batch whatever its cut-offs (`_stft_list`'s rule for which items), "stft_hard" items through
+    Engine.stft_lowpass as padded batches with a cut-off bin per clip (`_stft_hard_list`).
     -> list: NumPy arrays (to_host), or device tensors."""
     clips = list(clips)
     n = len(clips)
@@ -430,6 +466,40 @@ def lowpass_collate(batch, low_pass_range, filter_order_range, filter_type, fs, 
             each(rows, first, [filters[i] for i in first])
             each(rows, again, "stft")
             ret[key + "_LR"] = stack(key + "_LR", rows)
+    return ret
+
+
+VAL_CUTOFFS = (1000, 2000, 4000, 8000, 12000)
+
+
+def lowpass_collate_val(batch, engine=None, to_host=False):
+    """collate_fn_val (data_module.py:130-150) for a batch of dicts of (L, C) arrays: `fname` keys pass through as lists; every other
+    key is stacked as (B, L, 1) float32 from channel 0, and for every c in VAL_CUTOFFS key + "LR_" + str(c) is the (B, L, 1) float32
+    stack of lowpass(lowpass(x, c, 44100, 8, "butter"), c, 44100, 8, "stft") -- one `lowpass_list` call per filter, cut-off and key,
+    the "stft" pass on the float64 device rows of the Butterworth pass; every item exactly what the single-clip chain gives, rounded
+    to float32.  "cutoffs_c" / "orders_c" / "filters_c" are kept as the reference fills them: the list of cut-offs and two empty
+    lists.  -> tensors on the engine's device, or on the host (to_host)."""
+    batch = list(batch)
+    eng = _engine_or_default(engine)
+    where = torch.device("cpu") if to_host else eng.device
+
+    def stack(rows):
+        return torch.stack([_clips.as_tensor(r).to(device=where, dtype=torch.float32) for r in rows])[..., None]
+
+    ret = {}
+    for key in (batch[0].keys() if batch else ()):
+        if "fname" in key:
+            ret[key] = [x[key] for x in batch]
+            continue
+        clips = [x[key][..., 0] for x in batch]
+        ret[key] = stack(clips)
+        for c in VAL_CUTOFFS:
+            rows = lowpass_list(clips, c, 44100, order=8, _type="butter", engine=eng, to_host=to_host)
+            rows = lowpass_list(rows, c, 44100, order=8, _type="stft", engine=eng, to_host=to_host)
+            ret[key + "LR_" + str(c)] = stack(rows)
+            ret["cutoffs_" + str(c)] = list(VAL_CUTOFFS)
+            ret["orders_" + str(c)] = []
+            ret["filters_" + str(c)] = []
     return ret
 
 
