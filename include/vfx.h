@@ -406,6 +406,19 @@ int vfx_spectral_metrics(vfx_handle* h, const float* est, const float* target, i
 #define VFX_N_AUDIO_METRICS 9
 int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
                       void* stream);
+/*
+ * The same nine scores for test sets at `rate` Hz, the two rates the reference has a front end for (evaluation_proc/metrics.py:37-51):
+ *   44100  exactly vfx_audio_metrics (which forwards here), bit for bit
+ *   16000  |STFT| with n_fft 743, hop 160, periodic Hann, centre reflect padding (librosa.stft: an odd n_fft pads 371 samples on each
+ *          side, so T = 1 + (lengths[b] - 1) / 160 frames) -> the (T, 372) image, and MelScale(n_mels=80, sample_rate=16000, n_stft=372)
+ *          of it -> the (T, 80) image; 961 <= lengths[b] <= Lmax (7 frames).  The transform is a DFT-matrix product on the f32-input
+ *          MFMA, one f32 fma chain over the 743 samples of a frame in ascending order (stft_dft.hip); its tables belong to the handle,
+ *          are built on the first call and need no particular vfx_config.  The filterbank is the HTK table evaluated in float64 unless
+ *          a (372, 80) tensor "mel16k.fb" was loaded into VFX_MODEL_FRONTEND.
+ * Any other rate is an error.  Scores, sub-batching, workspace and batch independence are vfx_audio_metrics'.
+ */
+int vfx_audio_metrics_rate(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int rate,
+                           double* out, void* stream);
 
 /*
  * STOI, the short-time objective intelligibility measure (Taal, Hendriks, Heusdens, Jensen, IEEE TASLP 2011; restated from the paper,

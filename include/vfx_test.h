@@ -173,6 +173,12 @@ int vfx_op_ssim(vfx_handle* h, const float* est, const float* target, int B, int
 /* The SI-SDR of vfx_audio_metrics alone (k_sisdr_slabs + k_score_final): est[b, :lens[b]] against target[b, :lens[b]] of (B, L)
  * device tensors; lens HOST int[B], 1 <= lens[b] <= L -> out (B) device doubles.  Synchronises. */
 int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, int L, const int* lens, double* out, void* stream);
+/* The two images vfx_audio_metrics_rate scores, of one signal: wav (B, Lmax) device, clip b = its first lengths[b] samples (lengths HOST
+ * int[B], the bounds of vfx_audio_metrics_rate at that rate) -> sp (B, T, 372) and mel (B, T, 80) at rate 16000 (k_stft_dft), (B, T, 1025)
+ * and (B, T, 128) at rate 44100 (k_stft_mel); T = the frames of the longest clip, rows at or past a clip's own frames are zeros.
+ * Synchronises. */
+int vfx_op_score_spectrogram(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, int rate, float* sp, float* mel,
+                             void* stream);
 /* One intermediate of a vfx_stoi call -- the same arguments up to ntaps, B <= 1024 -- for the whole batch, to localise a failing score.  With
  * N = ceil(max(lens) up / down) samples at 10 kHz and Fm = max(1, frames of N by range(0, N - 256, 128)); what lies past a clip's own
  * extent is zero.  out and iout are DEVICE arrays of exactly out_n doubles and iout_n ints:

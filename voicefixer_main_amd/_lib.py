@@ -71,6 +71,7 @@ SIGNATURES = {
                               c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_audio_metrics_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),
     "vfx_stoi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_chunk_ola": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -130,6 +131,7 @@ TEST_SIGNATURES = {
     "vfx_op_peak_trim": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_ssim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_score_spectrogram": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "vfx_op_stoi_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "vfx_debug_resample_each_layout": (c_int, [c_void_p, c_int]),

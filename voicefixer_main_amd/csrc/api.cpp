@@ -157,7 +157,9 @@ int vfx_load_tensor(vfx_handle* h, int model, const char* name, const float* dat
 
 int vfx_finalize_weights(vfx_handle* h, int model) {
   VFX_API_BEGIN_H(h)
-  h->plans.clear();
+  // (no plan reads the scoring tables at 16 kHz: loading them alone leaves the plans, pinned ones included, as they are)
+  const bool score16k_only = model == VFX_MODEL_FRONTEND && h->staged[model].size() == 1 && h->staged[model].count("mel16k.fb");
+  if (!score16k_only) h->plans.clear();
   if (model == VFX_MODEL_UNET_MEL || model == VFX_MODEL_UNET_SPEC) {
     h->unet[model] = build_unet_weights(h, model);
   } else if (model == VFX_MODEL_VOCODER) {
@@ -173,6 +175,13 @@ int vfx_finalize_weights(vfx_handle* h, int model) {
                 "mel.fb must be (%d, %d)", h->cfg.n_fft / 2 + 1, h->cfg.n_mels);
       VFX_HIP(hipDeviceSynchronize());
       set_mel_filterbank(h, it->second.data.data());
+    }
+    it = h->staged[model].find("mel16k.fb");
+    if (it != h->staged[model].end()) {
+      VFX_CHECK(it->second.shape.size() == 2 && it->second.shape[0] == kDftBins && it->second.shape[1] == kDftMels,
+                "mel16k.fb must be (%d, %d)", kDftBins, kDftMels);
+      VFX_HIP(hipDeviceSynchronize());
+      set_score16k_filterbank(h, it->second.data.data());
     }
   } else {
     VFX_CHECK(false, "vfx_finalize_weights: bad model id %d", model);
@@ -323,16 +332,37 @@ static ScoreLayout score_layout(int n, int T, int nslab, int nbins, int nmels) {
   return l;
 }
 
-int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
-                      void* stream) {
+// the front end of a rate: the images' shapes, the frame rule and the shortest clip (7 frames: the smallest image skimage's 7 x 7
+// SSIM accepts)
+struct ScoreFrontEnd {
+  int rate, hop, nbins, nmels, min_len;
+  int frames(int len) const { return rate == kDftRate ? dft_frames(len) : len / hop + 1; }
+};
+static ScoreFrontEnd score_front_end(const vfx_handle* h, int rate, const char* who) {
+  VFX_CHECK(rate == 44100 || rate == kDftRate, "%s: rate %d is not scored (the supported rates are 44100 and 16000)", who, rate);
+  if (rate == kDftRate) return {rate, kDftHop, kDftBins, kDftMels, kDftMinLen};  // (its tables are its own: any handle has them)
+  VFX_CHECK(h->cfg.n_fft == 2048 && h->cfg.n_mels == 128, "%s: needs the 44.1 kHz front end (n_fft 2048, 128 mel bands)", who);
+  return {rate, h->cfg.hop, h->cfg.n_fft / 2 + 1, h->cfg.n_mels, 6 * h->cfg.hop};
+}
+// librosa.stft magnitudes (eps 0) and their mel projection, every clip framed at its own length; rows past it are zeros
+static void launch_score_images(vfx_handle* h, const ScoreFrontEnd& fe, const float* wav, int n, int Lmax, int T, const int* d_lens,
+                                float* sp, float* mel, hipStream_t s) {
+  if (fe.rate == kDftRate)
+    launch_stft_dft(ensure_score16k_tables(h), wav, n, Lmax, T, d_lens, sp, mel, s);
+  else
+    launch_stft_mel(h->fe, wav, n, Lmax, T, mel, sp, nullptr, nullptr, 0, fe.hop, 0.f, s, d_lens);
+}
+
+int vfx_audio_metrics_rate(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int rate,
+                           double* out, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(est && target && lengths && out && B > 0 && Lmax > 0, "vfx_audio_metrics: bad argument");
-  const int hop = h->cfg.hop, nbins = h->cfg.n_fft / 2 + 1, nmels = h->cfg.n_mels;
-  VFX_CHECK(h->cfg.n_fft == 2048 && nmels == 128, "vfx_audio_metrics: needs the 44.1 kHz front end (n_fft 2048, 128 mel bands)");
-  const int min_len = 6 * hop;  // 7 frames: the smallest image skimage's 7 x 7 SSIM accepts
+  const ScoreFrontEnd fe = score_front_end(h, rate, "vfx_audio_metrics");
+  const int nbins = fe.nbins, nmels = fe.nmels;
+  VFX_CHECK(rate != kDftRate || Lmax < (1 << 30), "vfx_audio_metrics: Lmax = %d is too long at 16 kHz (need < 2^30)", Lmax);
   for (int b = 0; b < B; ++b)
-    VFX_CHECK(lengths[b] >= min_len && lengths[b] <= Lmax, "vfx_audio_metrics: clip %d has %d samples (need %d <= length <= Lmax = %d)", b,
-              lengths[b], min_len, Lmax);
+    VFX_CHECK(lengths[b] >= fe.min_len && lengths[b] <= Lmax, "vfx_audio_metrics: clip %d has %d samples (need %d <= length <= Lmax = %d)",
+              b, lengths[b], fe.min_len, Lmax);
   // sub-batches of consecutive clips: each as many as keep its workspace (spectra of ITS longest clip) under the cap
   struct Sub { int b0, n, T, nslab; };
   std::vector<Sub> subs;
@@ -340,7 +370,7 @@ int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int 
   for (int b0 = 0; b0 < B;) {
     Sub s{b0, 0, 0, 0};
     while (b0 + s.n < B && s.n < kMaxVarlenClips) {
-      const int Tn = std::max(s.T, frames_of(h, lengths[b0 + s.n])), nsn = std::max(s.nslab, sisdr_slabs(lengths[b0 + s.n]));
+      const int Tn = std::max(s.T, fe.frames(lengths[b0 + s.n])), nsn = std::max(s.nslab, sisdr_slabs(lengths[b0 + s.n]));
       if (s.n > 0 && score_layout(s.n + 1, Tn, nsn, nbins, nmels).end > kScoreWorkspaceBytes) break;
       s.T = Tn;
       s.nslab = nsn;
@@ -355,7 +385,7 @@ int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int 
   int* const d_l = h->lens_row(LENS_SCORE_SAMPLES);
   int* const d_t = h->lens_row(LENS_SCORE_FRAMES);
   std::vector<int> frames(B);
-  for (int b = 0; b < B; ++b) frames[b] = frames_of(h, lengths[b]);
+  for (int b = 0; b < B; ++b) frames[b] = fe.frames(lengths[b]);
   for (const Sub& sb : subs) {
     const ScoreLayout l = score_layout(sb.n, sb.T, sb.nslab, nbins, nmels);
     auto f32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
@@ -363,9 +393,7 @@ int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int 
     launch_set_frames(d_l, lengths + sb.b0, sb.n, s);
     launch_set_frames(d_t, frames.data() + sb.b0, sb.n, s);
     const float* src[2] = {est + (int64_t)sb.b0 * Lmax, target + (int64_t)sb.b0 * Lmax};
-    // librosa.stft magnitudes (eps 0) and their mel projection, every clip framed at its own length; rows past it are zeros
-    for (int i = 0; i < 2; ++i)
-      launch_stft_mel(h->fe, src[i], sb.n, Lmax, sb.T, f32(l.mel[i]), f32(l.sp[i]), nullptr, nullptr, 0, hop, 0.f, s, d_l);
+    for (int i = 0; i < 2; ++i) launch_score_images(h, fe, src[i], sb.n, Lmax, sb.T, d_l, f32(l.sp[i]), f32(l.mel[i]), s);
     launch_sisdr_slabs(src[0], src[1], sb.n, Lmax, d_l, sb.nslab, f64(l.sisdr), s);
     launch_score_frames(f32(l.sp[0]), f32(l.sp[1]), sb.n, sb.T, nbins, d_t, f64(l.fr[0]), s);
     launch_score_frames(f32(l.mel[0]), f32(l.mel[1]), sb.n, sb.T, nmels, d_t, f64(l.fr[1]), s);
@@ -389,6 +417,11 @@ int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int 
     launch_score_final(a, sb.n, s);
   }
   VFX_API_END
+}
+
+int vfx_audio_metrics(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out,
+                      void* stream) {
+  return vfx_audio_metrics_rate(h, est, target, B, Lmax, lengths, 44100, out, stream);
 }
 
 int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,

@@ -1142,6 +1142,36 @@ extern "C" int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target
   return 0;
 }
 
+extern "C" int vfx_op_score_spectrogram(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, int rate, float* sp,
+                                        float* mel, void* stream) {
+  try {
+    VFX_CHECK(h && wav && lengths && sp && mel && B > 0 && B <= 65535 && Lmax > 0, "vfx_op_score_spectrogram: bad argument");
+    VFX_CHECK(rate == 44100 || rate == kDftRate, "vfx_op_score_spectrogram: rate %d is not scored (the supported rates are 44100 and 16000)",
+              rate);
+    const int min_len = rate == kDftRate ? kDftMinLen : 6 * h->cfg.hop;
+    VFX_CHECK(rate == kDftRate ? Lmax < (1 << 30) : h->cfg.n_fft == 2048 && h->cfg.n_mels == 128,
+              "vfx_op_score_spectrogram: Lmax too long, or not the 44.1 kHz front end");
+    int T = 0;
+    for (int b = 0; b < B; ++b) {
+      VFX_CHECK(lengths[b] >= min_len && lengths[b] <= Lmax, "vfx_op_score_spectrogram: clip %d has %d samples (need %d <= length <= Lmax = %d)",
+                b, lengths[b], min_len, Lmax);
+      T = std::max(T, rate == kDftRate ? dft_frames(lengths[b]) : lengths[b] / h->cfg.hop + 1);
+    }
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const int* d_lens = upload_lens(sc.blob, lengths, B);
+    if (rate == kDftRate)
+      launch_stft_dft(ensure_score16k_tables(h), wav, B, Lmax, T, d_lens, sp, mel, s);
+    else
+      launch_stft_mel(h->fe, wav, B, Lmax, T, mel, sp, nullptr, nullptr, 0, h->cfg.hop, 0.f, s, d_lens);
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
 extern "C" int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int up, int down,
                                  const double* taps, int ntaps, int stage, double* out, int64_t out_n, int* iout, int64_t iout_n,
                                  void* stream) {

@@ -486,6 +486,35 @@ void launch_ssim_tiles(const float* est, const float* tgt, int B, int T, int F, 
 void launch_score_final(const ScoreFinalArgs& a, int B, hipStream_t s);
 int64_t count_nonfinite(const float* p, int64_t n, hipStream_t s);  // debug aid, synchronises
 
+// stft_dft.hip: the front end of the scores at 16 kHz (vfx_audio_metrics_rate): |STFT| with n_fft 743, hop 160 as a DFT-matrix GEMM on
+// the f32-input MFMA, and the 80-band mel image.  An odd n_fft pads 371 samples on each side: 1 + (len - 1) / 160 frames.
+constexpr int kDftN = 743, kDftHop = 160, kDftBins = kDftN / 2 + 1, kDftMels = 80, kDftRate = 16000;
+constexpr int kDftK = 744;      // rows of the table: n, padded with a zero row to the MFMA's k step
+constexpr int kDftCols = 384;   // columns per part (w cos | -w sin) of the table: the bins padded to 12 tiles of 32
+constexpr int kDftStrip = 64;   // frames per workgroup
+constexpr int kDftMinLen = 6 * kDftHop + 1;  // 7 frames (the smallest SSIM image), and more than the 371-sample reflection
+__host__ __device__ inline int dft_frames(int len) { return 1 + (len - 1) / kDftHop; }
+// Where entry (n, bin, part: 0 = w cos, 1 = -w sin) of the (kDftK, 2 kDftCols) table sits: in MFMA fragment order.  A pass of the K loop
+// is 8 values of n = 4 k steps; the lane (bin, half) of a B fragment takes n = n0 + 2 k + half, k < 4, of both parts: 8 floats side by
+// side, the lanes of a half wave 32 bytes apart.
+constexpr int kDftPass = 8;
+inline size_t dft_table_index(int n, int bin, int part) {
+  const int pass = n / kDftPass, half = n & 1, k = (n % kDftPass) >> 1;
+  return (((size_t)pass * 2 + half) * kDftCols + bin) * kDftPass + part * (kDftPass / 2) + k;
+}
+struct Score16kTables {
+  float* table = nullptr;    // kDftK x 2 kDftCols floats at dft_table_index: the periodic Hann window times cos and -sin of
+                             // 2 pi (k n mod 743) / 743; row 743 and the bins from 372 up are zeros
+  float* fb_val = nullptr;   // packed non-zeros of the (372, 80) mel filterbank, band-major, as FrontEndTables'
+  int* fb_start = nullptr;   // [80]
+  int* fb_off = nullptr;     // [81]
+  std::vector<float> fb_host;  // (372, 80) as loaded ("mel16k.fb" of VFX_MODEL_FRONTEND); empty: the float64 HTK table
+};
+// wav (B, L), clip b = its first lens[b] samples (kDftMinLen <= lens[b] <= L; lens: device) -> sp (B, T, 372), mel (B, T, 80); rows at
+// or past a clip's dft_frames are zeros.  A frame's values depend on its clip's samples alone.
+void launch_stft_dft(const Score16kTables& t, const float* wav, int B, int L, int T, const int* lens, float* sp, float* mel,
+                     hipStream_t s);
+
 // stoi.hip: STOI (Taal, Hendriks, Heusdens, Jensen 2011) of the clips of a padded batch, float64 from the first multiply on
 constexpr int kStoiRate = 10000, kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiSegment = 30;
 constexpr int kStoiMaxUp = 1024;        // reduced up factor: k_stoi_resample stages the phases of whole tap steps in LDS
@@ -861,6 +890,7 @@ struct vfx_handle {
   vfx_config cfg{};
   std::map<std::string, vfx::HostTensor> staged[6];
   vfx::FrontEndTables fe;
+  vfx::Score16kTables fe16;  // the 743-point front end of the scores at 16 kHz, built on first use (ensure_score16k_tables)
   vfx::DeviceBlob blob;  // front-end tables + weights
   std::shared_ptr<vfx::UNetWeights> unet[2];
   std::shared_ptr<vfx::VocoderWeights> voc;
@@ -889,6 +919,9 @@ struct vfx_handle {
 namespace vfx {
 void init_front_end(vfx_handle* h);
 void set_mel_filterbank(vfx_handle* h, const float* fb /*1025x128*/);
+// the tables of stft_dft.hip, uploaded on the first call; fb (372 x 80) or NULL: the filterbank to use from now on
+const Score16kTables& ensure_score16k_tables(vfx_handle* h);
+void set_score16k_filterbank(vfx_handle* h, const float* fb);
 void bind_plan(vfx_handle* h, Plan& plan);  // ensures the arena is large enough and rebases the plan on it
 std::string key_of(const char* tag, int B, int T, int x = 0);  // key of a cached plan (vfx_handle::plans)
 // What a model-stage entry point does with a plan: take it from the handle's cache (building and binding it as needed: `build`),

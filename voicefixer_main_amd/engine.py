@@ -83,6 +83,7 @@ class Engine:
         self.analysis_model = MODEL_UNET_MEL   # what restore_gsr(_varlen) runs (select_analysis)
         self._resample_taps = {}   # (up, down) -> the filter of resample_poly on the device
         self._stoi_taps = {}       # (up, down) -> Octave's resample filter (float64) on the device, for `stoi`
+        self._score16k_fb = False  # the 16 kHz scoring filterbank has been handed to the library (_score_tables)
         self._resample_each_cache = collections.OrderedDict()   # (M, dtype) -> resample_poly's unscaled filter on the device, LRU
 
     def close(self):
@@ -263,10 +264,23 @@ class Engine:
                    "vfx_spectral_metrics")
         return out
 
-    def audio_metrics(self, est, target, lengths=None):
-        """AudioMetrics.evaluation's nine scores (metrics.METRIC_KEYS order) of waveform pairs at 44.1 kHz: est, target (B, L) or
-        (L,), pair b = the first lengths[b] samples of row b (default: all L; 2646 <= lengths[b] <= L) -> (B, 9) float64 on the
-        device (vfx_audio_metrics)."""
+    score_rates = (44100, 16000)   # the rates audio_metrics takes: the reference's two front ends (evaluation_proc/metrics.py:37-51)
+
+    def _score_tables(self, rate):
+        """Before the first call at 16 kHz: hand the library the reference's float32 evaluation of MelScale(80, 16000, 372) -- what
+        set_mel_filterbank is to the 44.1 kHz table.  (Not through load_state_dict: the strict twin's state stays the models'.)"""
+        if int(rate) == 16000 and not self._score16k_fb:
+            from .models import MelScale
+            fb = np.ascontiguousarray(MelScale.filterbank(372, 80, 16000, 8000.0).numpy(), dtype=np.float32)
+            _lib.check(self.lib.vfx_load_tensor(self.h, MODEL_FRONTEND, b"mel16k.fb", fb.ctypes.data_as(ctypes.c_void_p),
+                                                (ctypes.c_int64 * 2)(*fb.shape), 2), "vfx_load_tensor(mel16k.fb)")
+            _lib.check(self.lib.vfx_finalize_weights(self.h, MODEL_FRONTEND), "vfx_finalize_weights")
+            self._score16k_fb = True
+
+    def audio_metrics(self, est, target, lengths=None, rate=44100):
+        """AudioMetrics.evaluation's nine scores (metrics.METRIC_KEYS order) of waveform pairs at `rate` Hz (one of score_rates): est,
+        target (B, L) or (L,), pair b = the first lengths[b] samples of row b (default: all L; 2646 <= lengths[b] <= L at 44.1 kHz,
+        961 at 16 kHz) -> (B, 9) float64 on the device (vfx_audio_metrics_rate; at 44.1 kHz vfx_audio_metrics, bit for bit)."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
         if est.dim() == 1:
             est, target = est[None], target[None]
@@ -274,8 +288,9 @@ class Engine:
             raise ValueError("audio_metrics: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
         est, _, B, L, lengths = _clip_rows(est, lengths, "audio_metrics")
         out = torch.empty((B, _lib.N_AUDIO_METRICS), device=self.device, dtype=torch.float64)
-        _lib.check(self.lib.vfx_audio_metrics(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
-                                              self._stream()), "vfx_audio_metrics")
+        self._score_tables(rate)
+        _lib.check(self.lib.vfx_audio_metrics_rate(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), int(rate),
+                                                   _ptr(out), self._stream()), "vfx_audio_metrics")
         return out
 
     STOI_RATE = 10000
@@ -1129,6 +1144,22 @@ class Engine:
         _lib.check(_lib.load_test().vfx_op_sisdr(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), _ptr(out),
                                                  self._stream()), "vfx_op_sisdr")
         return out
+
+    def op_score_spectrogram(self, wav, lengths=None, rate=16000):
+        """The two images audio_metrics scores, of one signal (vfx_op_score_spectrogram): wav (B, L) or (L,), clip b = its first
+        lengths[b] samples -> (sp (B, T, 372), mel (B, T, 80)) at 16 kHz, (B, T, 1025) and (B, T, 128) at 44.1 kHz; T = the frames of
+        the longest clip (1 + (n - 1) // 160, n // 441 + 1), rows at or past a clip's own frames are zeros."""
+        wav = _dev_f32(wav, self.device)
+        wav, _, B, L, lengths = _clip_rows(wav, lengths, "op_score_spectrogram")
+        rate = int(rate)
+        hop, F, M = (160, 372, 80) if rate == 16000 else (self.cfg.hop, self.cfg.n_fft // 2 + 1, self.cfg.n_mels)
+        T = max([1 + (n - 1) // 160 if rate == 16000 else n // hop + 1 for n in lengths] + [1])
+        sp = torch.empty((B, T, F), device=self.device, dtype=torch.float32)
+        mel = torch.empty((B, T, M), device=self.device, dtype=torch.float32)
+        self._score_tables(rate)
+        _lib.check(_lib.load_test().vfx_op_score_spectrogram(self.h, _ptr(wav), B, L, (ctypes.c_int * max(B, 1))(*lengths), rate,
+                                                             _ptr(sp), _ptr(mel), self._stream()), "vfx_op_score_spectrogram")
+        return sp, mel
 
     STOI_STAGES = ("resampled", "mask", "powers", "tob")
 

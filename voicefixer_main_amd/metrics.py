@@ -1,7 +1,9 @@
 """Scoring of restored test sets: the drop-in for evaluation_proc.metrics.AudioMetrics and eval.py's aggregate_score / gather_score.
 
-`AudioMetrics.evaluation` (evaluation_proc/metrics.py:55-81) returns these keys, computed on the GPU by vfx_audio_metrics
-(include/vfx.h; Engine.audio_metrics):
+`AudioMetrics.evaluation` (evaluation_proc/metrics.py:55-81) returns these keys, computed on the GPU by vfx_audio_metrics_rate
+(include/vfx.h; Engine.audio_metrics) with the front end the reference picks from the target's sample rate
+(evaluation_proc/metrics.py:37-51): n_fft 2048, hop 441 and 128 mel bands at 44.1 kHz; n_fft 743, hop 160 and 80 mel bands at 16 kHz
+(an odd n_fft: 371 samples of reflect padding on each side, 1 + (n - 1) // 160 frames):
 
     sisdr, lsd, non_log_sispec, sispec, ssim, final_mel_lsd, final_non_log_mel_sispec, final_mel_sispec, final_mel_ssim
 
@@ -14,9 +16,10 @@ pinned against the pystoi package.
 What differs from the reference, on purpose:
   * STOI is opt-in (`stoi=True`); PESQ and the bsseval scores are not computed, and their keys are absent (no implementation to pin
     them against).
-  * Only 44.1 kHz targets: any other rate raises ValueError, like the reference's "Bad Samplerate" for rates it has no STFT for
-    (its 16 kHz branch is not implemented).  An est file at another rate than its target, or of another length, makes that pair
-    an error: speechmetrics would zero-pad the shorter signal and librosa.load would resample est.
+  * 44.1 kHz and 16 kHz targets (the rates in the engine's `score_rates`; an engine without that attribute scores 44.1 kHz only): any
+    other rate raises ValueError, like the reference's "Bad Samplerate" for rates it has no STFT for.  An est file at another rate
+    than its target, or of another length, makes that pair an error: speechmetrics would zero-pad the shorter signal and
+    librosa.load would resample est.
   * aggregate_score leaves a pair that fails out of the table and its mean; the reference records the previous pair's scores
     under the failed pair's name again.
 """
@@ -35,6 +38,8 @@ METRIC_KEYS = ("sisdr", "lsd", "non_log_sispec", "sispec", "ssim",
                "final_mel_lsd", "final_non_log_mel_sispec", "final_mel_sispec", "final_mel_ssim")
 SAMPLE_RATE = 44100
 MIN_SAMPLES = 6 * 441   # 7 STFT frames: skimage's 7 x 7 SSIM rejects a smaller spectrogram
+# rate -> (hop, fewest samples that give 7 STFT frames): T = n // 441 + 1 at n_fft 2048; T = 1 + (n - 1) // 160 at the odd n_fft 743
+FRONT_ENDS = {SAMPLE_RATE: (441, MIN_SAMPLES), 16000: (160, 6 * 160 + 1)}
 
 
 def read_list(fname):
@@ -59,17 +64,20 @@ def _wav_info(path):
 
 
 class AudioMetrics:
-    """evaluation_proc/metrics.py:20-106 at 44.1 kHz.  `engine`: an Engine (or anything with `device` and
+    """evaluation_proc/metrics.py:20-106 at 44.1 kHz or 16 kHz.  `engine`: an Engine (or anything with `device` and
     `audio_metrics(est, target, lengths)` -- and, for `stoi=True`, `stoi(est, target, lengths, fs)`); default: a new Engine on cuda:0.
+    A rate other than 44100 must be in the engine's `score_rates`, and is handed to it as `audio_metrics(..., rate=rate)`.
     stoi=True adds the key "stoi" after "sisdr"."""
 
     def __init__(self, rate, engine=None, stoi=False):
-        if int(rate) != SAMPLE_RATE:
-            raise ValueError("Bad Samplerate: %s (only %d Hz test sets are scored)" % (rate, SAMPLE_RATE))
-        self.rate = int(rate)
-        if engine is None:
+        if engine is None and int(rate) in FRONT_ENDS:
             from .engine import Engine
             engine = Engine("cuda:0")
+        rates = (SAMPLE_RATE,) + tuple(getattr(engine, "score_rates", ()))
+        if int(rate) not in rates or int(rate) not in FRONT_ENDS:
+            raise ValueError("Bad Samplerate: %s (test sets at %s Hz are scored)" % (rate, " or ".join(str(r) for r in sorted(set(rates)))))
+        self.rate = int(rate)
+        self.hop, self.min_samples = FRONT_ENDS[self.rate]
         self.engine = engine
         self.stoi = bool(stoi)
         self.keys = METRIC_KEYS[:1] + ("stoi",) + METRIC_KEYS[1:] if self.stoi else METRIC_KEYS
@@ -87,14 +95,14 @@ class AudioMetrics:
 
     def _check_pair(self, est, target):
         (n_e, sr_e), (n_t, sr_t) = _wav_info(est), _wav_info(target)
-        if sr_t != SAMPLE_RATE:
-            raise ValueError("Bad Samplerate: %s is at %d Hz" % (target, sr_t))
+        if sr_t != self.rate:
+            raise ValueError("Bad Samplerate: %s is at %d Hz, the test set at %d Hz" % (target, sr_t, self.rate))
         if sr_e != sr_t:
             raise ValueError("%s is at %d Hz, its target %s at %d Hz" % (est, sr_e, target, sr_t))
         if n_e != n_t:
             raise ValueError("%s has %d samples, its target %s %d" % (est, n_e, target, n_t))
-        if n_t < MIN_SAMPLES:
-            raise ValueError("%s has %d samples: SSIM needs at least %d (7 STFT frames)" % (target, n_t, MIN_SAMPLES))
+        if n_t < self.min_samples:
+            raise ValueError("%s has %d samples: SSIM needs at least %d (7 STFT frames)" % (target, n_t, self.min_samples))
         return n_t
 
     def evaluation_list(self, pairs, max_batch=128):
@@ -118,8 +126,8 @@ class AudioMetrics:
             lengths, idx = [], []
             for j, (n, i) in enumerate(chunk):
                 try:
-                    e = handlers.load_wav(pairs[i][0], SAMPLE_RATE)
-                    t = handlers.load_wav(pairs[i][1], SAMPLE_RATE)
+                    e = handlers.load_wav(pairs[i][0], self.rate)
+                    t = handlers.load_wav(pairs[i][1], self.rate)
                 except Exception as ex:  # noqa: BLE001
                     results[i] = ex
                     continue
@@ -130,9 +138,13 @@ class AudioMetrics:
                 continue
             k = len(idx)
             e_dev, t_dev = torch.from_numpy(est[:k]).to(dev), torch.from_numpy(tgt[:k]).to(dev)
-            scores = self.engine.audio_metrics(e_dev, t_dev, lengths).cpu().numpy().tolist()
+            if self.rate == SAMPLE_RATE:   # (three arguments: what an engine without `score_rates` takes)
+                scores = self.engine.audio_metrics(e_dev, t_dev, lengths)
+            else:
+                scores = self.engine.audio_metrics(e_dev, t_dev, lengths, rate=self.rate)
+            scores = scores.cpu().numpy().tolist()
             if self.stoi:
-                st = self.engine.stoi(e_dev, t_dev, lengths, fs=SAMPLE_RATE).cpu().numpy().tolist()
+                st = self.engine.stoi(e_dev, t_dev, lengths, fs=self.rate).cpu().numpy().tolist()
                 scores = [row[:1] + [st[j]] + row[1:] for j, row in enumerate(scores)]
             for j, i in enumerate(idx):
                 results[i] = {key: float(v) for key, v in zip(self.keys, scores[j])}
