@@ -376,6 +376,45 @@ int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* len
                   float* hq_out, float* aug_out, float* noisy, void* stream);
 
 /*
+ * A padded batch of clips quantised to 2 ** bins levels of their own peak: MagicalEffects.quantification
+ * (dataloaders/augmentation/magical_effects.py:178-187) per clip, one of the array effects of the training degradation chain.
+ *   x (B, ldx) device, float32 (x_f64 = 0) or float64 (x_f64 = 1), clip b = the first lengths[b] samples of row b (HOST int64[B], each
+ *   >= 1; what a row holds past them is never read); bins HOST int[B], each in 0..16;
+ *   y (B, ldy) device float64: row b receives lengths[b] samples and zeros from there up to ldy;
+ *   peaks (B) device in x's dtype, or NULL: max |x| of every clip.
+ * Per clip, with level = 2 ** bins and the levels L_j = -1 + (2 j + 1) / level, j < level (exact doubles; the reference's np.linspace
+ * gives the same values bit for bit): p = max |x| in x's dtype (NaN if a sample is); s = x / p, one correctly rounded division in x's
+ * dtype; k = the number of levels below (double)s, a NaN s counting as above all of them -- np.digitize(s, L, right=True); idx = k - 1,
+ * and idx = -1, for a sample at or below the lowest level, is the TOP level as NumPy's negative index makes it (the negative peak -p
+ * comes out as +(1 - 1 / level) p); y = L_idx * (double)p, one double multiplication.  k is settled by comparisons of s with the exact
+ * levels, so y equals the host function bit for bit; zero, infinite and NaN peaks take the same steps (a silent clip gives zeros, a
+ * clip with a NaN gives NaN throughout).  A clip's result depends on the clip alone: not on the batch, the row stride or the alignment.
+ * Fails, launching nothing and leaving y as it is, for B outside 1..1024, an empty clip, a length above ldx or ldy, bins outside
+ * 0..16, or a NULL other than peaks.
+ */
+int vfx_quantize(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* bins, double* y,
+                 int64_t ldy, void* peaks, void* stream);
+
+/*
+ * A stretch of every clip of a padded batch silenced and its two edges smoothed: MagicalEffects.time_dropout
+ * (magical_effects.py:169-176) with tools/others/audio_op.py:152-174 `smooth` per clip.
+ *   x, lengths as in vfx_quantize; starts, ends HOST int64[B]: the sample range [start, end) of clip b, 0 <= start <= end (the
+ *   reference's int(length * start) and int(length * start + length * trunk_length)); an end past the clip is cut to its length;
+ *   smooth HOST double[96 * 25]: the matrix M of `smooth` with its defaults -- the 96 samples it writes are M times the 25 knots it
+ *   reads, every fourth sample of the 100 around the centre (cubic interpolation is linear in the knots); kept in a device buffer of the
+ *   handle and uploaded again only when its contents change;
+ *   y (B, ldy) device in x's dtype, not overlapping x: row b receives lengths[b] samples and zeros from there up to ldy.
+ * Per clip of n samples: y = x with y[start : min(end, n)] = 0; then for c = start and c = end, in that order, if c >= 50 and
+ * n - c >= 50: the knots y[c - 50 + 4 i], i < 25, are read after everything before them has been written (the second patch may overlap
+ * the first and the zeroed range), and y[c - 50 + t] = sum_i M[t][i] knot_i for t < 96, the sum in double in ascending i, rounded once
+ * to x's dtype.  Outside the two patches y is x or zero, bit for bit.  A clip's result depends on the clip alone.
+ * Fails, launching nothing and leaving y as it is, for B outside 1..1024, an empty clip, a length above ldx or ldy, start < 0,
+ * end < start, or a NULL argument.
+ */
+int vfx_time_dropout(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int64_t* starts,
+                     const int64_t* ends, const double* smooth, void* y, int64_t ldy, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

@@ -69,6 +69,10 @@ SIGNATURES = {
     "vfx_mix_noise": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p,
                               POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "vfx_quantize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int), c_void_p, c_int64, c_void_p,
+                             c_void_p]),
+    "vfx_time_dropout": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                 POINTER(ctypes.c_double), c_void_p, c_int64, c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_audio_metrics_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),

@@ -653,6 +653,50 @@ int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* len
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// array effects (MagicalEffects.quantification and time_dropout on the device: effects.hip)
+// ---------------------------------------------------------------------------------------------
+// what the two entry points check of a batch of clips; -> nothing, or throws
+static void check_fx_clips(const char* who, int B, int64_t ldx, int64_t ldy, const int64_t* lengths) {
+  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "%s: %d clips (need 1 <= B <= %d)", who, B, kMaxVarlenClips);
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] >= 1, "%s: clip %d is empty (%lld samples)", who, b, (long long)lengths[b]);
+    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 2 * kFxChunk,
+              "%s: clip %d has %lld samples, the rows hold %lld and %lld", who, b, (long long)lengths[b], (long long)ldx, (long long)ldy);
+  }
+}
+
+int vfx_quantize(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* bins, double* y,
+                 int64_t ldy, void* peaks, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && bins && y && (x_f64 == 0 || x_f64 == 1), "vfx_quantize: bad argument");
+  check_fx_clips("vfx_quantize", B, ldx, ldy, lengths);
+  for (int b = 0; b < B; ++b)
+    VFX_CHECK(bins[b] >= 0 && bins[b] <= kFxMaxBins, "vfx_quantize: clip %d: %d bins (need 0 <= bins <= %d)", b, bins[b], kFxMaxBins);
+  auto* const bits = reinterpret_cast<unsigned long long*>(h->fx_ws.ensure(h, (size_t)kMaxVarlenClips * sizeof(unsigned long long), 0));
+  launch_quantize(x, x_f64, B, ldx, lengths, bins, y, ldy, peaks, bits, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+int vfx_time_dropout(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int64_t* starts,
+                     const int64_t* ends, const double* smooth, void* y, int64_t ldy, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && starts && ends && smooth && y && (x_f64 == 0 || x_f64 == 1), "vfx_time_dropout: bad argument");
+  check_fx_clips("vfx_time_dropout", B, ldx, ldy, lengths);
+  for (int b = 0; b < B; ++b)
+    VFX_CHECK(starts[b] >= 0 && ends[b] >= starts[b], "vfx_time_dropout: clip %d: bad range [%lld, %lld) (need 0 <= start <= end)", b,
+              (long long)starts[b], (long long)ends[b]);
+  constexpr size_t kSmooth = (size_t)kFxSmoothRows * kFxSmoothKnots;
+  if (h->fx_smooth_seen.size() != kSmooth || memcmp(h->fx_smooth_seen.data(), smooth, kSmooth * sizeof(double)) != 0) {
+    memcpy(h->fx_smooth.stage(h, kSmooth * sizeof(double)), smooth, kSmooth * sizeof(double));
+    h->fx_smooth.upload(kSmooth * sizeof(double), static_cast<hipStream_t>(stream));
+    h->fx_smooth_seen.assign(smooth, smooth + kSmooth);
+  }
+  launch_time_dropout(x, x_f64, B, ldx, lengths, starts, ends, reinterpret_cast<const double*>(h->fx_smooth.dev.p), y, ldy,
+                      static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

@@ -645,6 +645,24 @@ void launch_mix_noise(int form, int B, int64_t ld, const int64_t* lengths, const
                       const double* scale, float* const out[5], char* ws, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// array effects (effects.hip): MagicalEffects.quantification and time_dropout
+// ---------------------------------------------------------------------------------------------
+constexpr int kFxChunk = 4096;     // samples of a clip per workgroup of the element-wise passes
+constexpr int kFxMaxClips = 128;   // clips per launch: their lengths, bins and indices are kernel arguments
+constexpr int kFxMaxBins = 16;     // level = 2 ** bins <= 65536
+constexpr int kFxSmoothHalf = 50, kFxSmoothStep = 4;                                       // smooth()'s smooth_samples and interval
+constexpr int kFxSmoothKnots = 2 * kFxSmoothHalf / kFxSmoothStep;                          // 25 knots: patch[0], patch[4], .., patch[96]
+constexpr int kFxSmoothRows = (kFxSmoothKnots - 1) * kFxSmoothStep;                        // 96 samples written: patch[0 .. 95]
+// x, y, peaks (or NULL), bits (B slots): device; lengths, bins: HOST (B).  The caller has checked 1 <= lengths[b] <= min(ldx, ldy) and
+// 0 <= bins[b] <= kFxMaxBins.  y[b, lengths[b] .. ldy) = 0.
+void launch_quantize(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* bins, double* y, int64_t ldy,
+                     void* peaks, unsigned long long* bits, hipStream_t s);
+// x, y (x's dtype), smooth (kFxSmoothRows, kFxSmoothKnots): device; lengths, starts, ends: HOST (B).  The caller has checked the lengths
+// as above and 0 <= starts[b] <= ends[b].  y[b, lengths[b] .. ldy) = 0.
+void launch_time_dropout(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int64_t* starts, const int64_t* ends,
+                         const double* smooth, void* y, int64_t ldy, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {
@@ -908,6 +926,9 @@ struct vfx_handle {
   vfx::GrowBuffer sos_ws;    // vfx_sosfiltfilt's forward pass over the extended clips (float64)
   vfx::StagedUpload sos_bank;  // vfx_sosfiltfilt_bank's designs: coefficients and zi of every section (sosfilt_pack_bank)
   vfx::GrowBuffer mix_ws;   // vfx_mix_noise's per-clip peaks, level ratios and chunk sums
+  vfx::GrowBuffer fx_ws;    // vfx_quantize's per-clip peaks (bit patterns)
+  vfx::StagedUpload fx_smooth;          // vfx_time_dropout's smoothing matrix on the device ...
+  std::vector<double> fx_smooth_seen;   // ... and what it holds: uploaded again only when the caller's matrix differs
   vfx::GrowBuffer rs_taps;  // vfx_resample_each's scaled taps of the designs of a call (at most 11 MB per design)
   vfx::StagedUpload rs_table;  // vfx_resample_each's design and clip tables
   bool rs_natural_taps = false;  // debug switch (vfx_debug_resample_each_layout): the scaled taps in natural order, not phase-major

@@ -720,6 +720,69 @@ class Engine:
                                           _ptr(out.get("aug")), _ptr(out.get("noisy")), self._stream()), "vfx_mix_noise")
         return {k: v[0] for k, v in out.items()} if squeeze else out
 
+    # ------------------------------------------------------------------ array effects (MagicalEffects.quantification, time_dropout)
+    MAX_QUANT_BINS = 16
+
+    def _fx_rows(self, x, lengths, name):
+        """x (B, L) or (L,), float32 or float64 -> (x on the device as (B, L), squeeze, B, L, lengths)"""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if x.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: x must be float32 or float64, got %s" % (name, x.dtype))
+        if x.dim() not in (1, 2):
+            raise ValueError("%s: x must be (B, L) or (L,), got %s" % (name, tuple(x.shape)))
+        x, squeeze, B, L, lengths = _clip_rows(x.to(self.device).contiguous(), lengths, name)
+        if B == 0:
+            raise ValueError("%s: no clips" % name)
+        return x, squeeze, B, L, lengths
+
+    @staticmethod
+    def _fx_per_clip(v, B, name, what):
+        v = [int(v)] * B if np.ndim(v) == 0 else [int(u) for u in v]
+        if len(v) != B:
+            raise ValueError("%s: %d %s for %d clips" % (name, len(v), what, B))
+        return v
+
+    @staticmethod
+    def _fx_out(_y, B, L, dtype, device, name):
+        """the result tensor: every element is written, zeros at and past a clip's length"""
+        if _y is None:
+            return torch.empty((B, L), device=device, dtype=dtype)
+        if _y.shape != (B, L) or _y.dtype != dtype or not _y.is_contiguous() or _y.device != device:
+            raise ValueError("%s: _y must be a contiguous (%d, %d) %s tensor on %s" % (name, B, L, dtype, device))
+        return _y
+
+    def quantize(self, x, bins, lengths=None, _y=None):
+        """MagicalEffects.quantification of every clip on the device: x (B, L) or (L,), float32 or float64; bins one int for all or
+        one per clip, each in 0..16; clip b = the first lengths[b] samples (default L) of row b, what the row holds past them is not
+        read.  -> (y, peaks): y float64 shaped like x, zero past each length, bit for bit simulate.quantification; peaks (B,) in
+        x's dtype (0-D for a 1-D x), max |x| of each clip.  A clip's result does not depend on the batch."""
+        x, squeeze, B, L, lengths = self._fx_rows(x, lengths, "quantize")
+        bins = self._fx_per_clip(bins, B, "quantize", "bins")
+        y = self._fx_out(_y, B, L, torch.float64, x.device, "quantize")
+        peaks = torch.empty((B,), device=x.device, dtype=x.dtype)
+        _lib.check(self.lib.vfx_quantize(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, (ctypes.c_int64 * B)(*lengths),
+                                         (ctypes.c_int * B)(*bins), _ptr(y), L, _ptr(peaks), self._stream()), "vfx_quantize")
+        return (y[0], peaks[0]) if squeeze else (y, peaks)
+
+    def time_dropout(self, x, starts, ends, lengths=None, _y=None):
+        """MagicalEffects.time_dropout of every clip on the device: x and lengths as in `quantize`; starts, ends: the sample range
+        [start, end) to silence, one pair for all or one per clip, 0 <= start <= end (simulate.time_dropout's int(length * start)
+        and int(length * start + length * trunk_length)).  -> tensor shaped like x in x's dtype, zero past each length: x with the
+        range zeroed and the 96-sample patches of `smooth` around start and around end, each skipped when its centre is closer than
+        50 samples to either end of the clip.  Outside the patches bit for bit the host function; inside, the 25-term float64 sum
+        of simulate.smooth_matrix() rounded once."""
+        from .simulate import smooth_matrix
+        x, squeeze, B, L, lengths = self._fx_rows(x, lengths, "time_dropout")
+        starts = self._fx_per_clip(starts, B, "time_dropout", "starts")
+        ends = self._fx_per_clip(ends, B, "time_dropout", "ends")
+        y = self._fx_out(_y, B, L, x.dtype, x.device, "time_dropout")
+        i64 = ctypes.c_int64 * B
+        _lib.check(self.lib.vfx_time_dropout(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, i64(*lengths), i64(*starts), i64(*ends),
+                                             smooth_matrix().ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _ptr(y), L,
+                                             self._stream()), "vfx_time_dropout")
+        return y[0] if squeeze else y
+
     def resunet_mel(self, mel_linear):
         """Generator.forward: linear mel (B,T,128) -> log10 mel (B,T,128)."""
         mel = _dev_f32(mel_linear, self.device)

@@ -17,7 +17,14 @@ same names, argument meaning and error behaviour:
   with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56); their ``..._list``
   forms mix whole lists of float32 clips on the device (Engine.mix_noise, csrc/mix.hip), ``hard_clip_list`` clips a list;
 * ``reverb_rir(frames, rir)``                              dataloaders/augmentation/magical_effects.py:158-167
-  (the `vctk_reverb` test set: convolution with a room impulse response; ``reverb_rir_list`` is its batch form on the device).
+  (the `vctk_reverb` test set: convolution with a room impulse response; ``reverb_rir_list`` is its batch form on the device);
+* ``quantification(samples, params)`` / ``time_dropout(frames, params)``   magical_effects.py:169-187, with ``smooth`` of
+  tools/others/audio_op.py:152-174; ``quantification_list`` / ``time_dropout_list`` are their batch forms on the device
+  (Engine.quantize, Engine.time_dropout, csrc/effects.hip);
+* ``array_effects(frames, effects, rirs)``: the tail of ``MagicalEffects.effect`` behind the sox chain (:81-108) -- LARGESCALE,
+  ``empty_c``, then reverb_rir, time_dropout and quant in dict order -- and ``array_effects_list``, whose clips stay on the device
+  between steps; ``draw_array_effects`` draws the dicts as ``RandomServer.generate`` does (random_server.py:135-217).  The sox effects
+  of the chain (tempo, speed, pitch, fade, ...) are the only ones without a device form: they are not built here at all.
 
 Everything is NumPy / SciPy on the host EXCEPT ``stft_hard``: its STFT -> mask -> ISTFT round trip is the hot path's own
 front-end and back-end (``vfx_stft_mel`` in its phase-emitting form and ``vfx_istft``), so it runs on the GPU through an
@@ -745,3 +752,307 @@ def hard_clip_list(clips, threshold, engine=None, to_host=True):
         y = torch.clamp(_clips.as_tensor(c), -threshold, threshold) if _clips.is_f32(c) else hard_clip(_clips.as_numpy(c), threshold)
         out.append(_clips.as_numpy(y) if to_host else _clips.to_device(y, _engine_or_default(engine).device))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the array effects of MagicalEffects.effect: dataloaders/augmentation/magical_effects.py:66-108, 169-190, tools/others/audio_op.py:152-174
+# and their draws, dataloaders/augmentation/random_server.py:135-217 with tools/pytorch/random_.py:36-45
+# ------------------------------------------------------------------------------------------------------------------
+EFFECT_TYPES = {      # RandomServer.effects_type: 0 = applied to the array, 1 / 1.1 = a sox effect of the chain, 3 = "anytime"
+    "tempo": 1, "speed": 1, "fade": 1.1, "pitch": 1, "treble": 1, "bass": 1, "tremolo": 1, "clip": 1, "reverse": 1,
+    "reverb_freeverb": 1, "reverb_rir": 0, "low_pass": 1, "high_pass": 1, "time_dropout": 0, "empty_c": 0, "empty_n": 0, "beep": 0,
+    "quant": 0, "anytime": 3,
+}
+MAX_QUANT_BINS = 16      # what the device quantiser takes (Engine.MAX_QUANT_BINS)
+
+
+def quantification(samples, params):
+    """MagicalEffects.quantification, params = [decision, bins]: the clip divided by its peak, every sample moved DOWN to the next of
+    the 2 ** bins levels linspace(-1 + 1 / level, 1 - 1 / level, level) strictly below it, times the peak -> float64.  A sample at or
+    below the lowest level gets index -1, which NumPy reads as the TOP level: the negative peak -p comes out as +(1 - 1 / level) p.
+    Kept.  A silent clip is 0 / 0 = NaN throughout (an invalid-value warning), NaN sorts above every level, and the top level times
+    a peak of 0 is 0."""
+    bins = params[1]
+    level = 2 ** bins
+    peak = np.max(np.abs(samples))
+    samples = samples / np.max(np.abs(samples))
+    space = np.linspace(start=-(1 / level) * level + (1 / level), stop=(1 / level) * level - (1 / level), num=level, endpoint=True)
+    index = np.digitize(samples, space, right=True) - 1
+    return space[index] * peak
+
+
+def smooth(signal, smooth_center, smooth_samples=50, interval=4):
+    """audio_op.smooth: the 2 * smooth_samples samples around smooth_center are replaced, all but the last `interval`, by the cubic
+    interpolation through every interval-th of them -- IN PLACE; a centre closer than smooth_samples to either end leaves the signal
+    as it is.  A 2-D signal is smoothed in its column 0 and returned as (samples, 1)."""
+    from scipy.interpolate import interp1d
+    if smooth_center < smooth_samples or signal.shape[0] - smooth_center < smooth_samples:
+        return signal
+    two_d = len(list(signal.shape)) > 1
+    if two_d:
+        signal = signal[:, 0]
+    first = smooth_center - smooth_samples
+    samples = signal[first:smooth_center + smooth_samples]
+    xnew = np.arange(samples.shape[0])
+    x = xnew[0::interval]
+    xnew = xnew[:x[-1]]
+    smoothed = interp1d(x, samples[0::interval], kind="cubic")(xnew)
+    signal[first:first + smoothed.shape[0]] = smoothed
+    return signal[:, None] if two_d else signal
+
+
+_smooth_matrix = None
+
+
+def smooth_matrix():
+    """`smooth` with its defaults as a matrix: the 96 samples it writes are M @ knots, knots = signal[c - 50 : c + 50 : 4] as
+    float64 -- cubic interpolation is linear in its knots, so column i of M (96, 25) is the interpolation of the i-th unit vector.
+    Built once with SciPy; read-only.  What Engine.time_dropout hands to the library."""
+    global _smooth_matrix
+    if _smooth_matrix is None:
+        from scipy.interpolate import interp1d
+        x, xnew = np.arange(0, 100, 4), np.arange(96)
+        m = np.stack([interp1d(x, e, kind="cubic")(xnew) for e in np.eye(25)], axis=1)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        m.setflags(write=False)
+        _smooth_matrix = m
+    return _smooth_matrix
+
+
+def _dropout_range(length, params):
+    """time_dropout's sample range: (int(length * start), int(length * start + length * trunk_length))"""
+    start, trunk_length = params[1]
+    return int(length * start), int(length * start + length * trunk_length)
+
+
+def time_dropout(frames, params):
+    """MagicalEffects.time_dropout, params = [decision, [start, trunk_length]] as fractions of the clip: that stretch is zeroed and
+    both its edges are smoothed (`smooth` around the first zeroed sample, then around the first sample behind the stretch) -- IN
+    PLACE, as the reference works."""
+    start, end = _dropout_range(frames.shape[0], params)
+    frames[start:end] = np.zeros_like(frames[start:end])
+    frames = smooth(frames, smooth_center=start)
+    frames = smooth(frames, smooth_center=end)
+    return frames
+
+
+def _array_steps(effects):
+    """The type-0 effects of one item's dict in dict order, as (name, params) -- "empty_c" alone when it is among them; ValueError
+    for a sox effect and for an unknown name."""
+    steps = []
+    for key in effects.keys():
+        if key not in EFFECT_TYPES:
+            raise ValueError("Unknown effect %s" % (key,))
+        if EFFECT_TYPES[key] != 0:
+            raise ValueError("array_effects: %s is an effect of the sox chain, which is not built here" % (key,))
+        if key in ("reverb_rir", "time_dropout", "quant", "empty_c"):
+            steps.append((key, effects[key]))
+    return [s for s in steps if s[0] == "empty_c"][:1] or steps
+
+
+def _rir_of(rirs, params):
+    if rirs is None:
+        raise ValueError("array_effects: reverb_rir needs the list of RIRs")
+    return rirs[params[1]]
+
+
+def array_effects(frames, effects, rirs=None):
+    """The tail of MagicalEffects.effect (magical_effects.py:81-108) for one clip, behind the sox chain: `effects` is the dict
+    name -> [decision, params] that RandomServer.generate (or `draw_array_effects`) returns, rirs the list of RIR arrays that
+    effects["reverb_rir"][1] indexes.  The input is not modified; the array keeps its dtype (the reference has made it float32 by
+    then).  LARGESCALE: a clip whose largest sample exceeds 10 is divided by 2 ** 15 first and multiplied by it at the end.
+    "empty_c" returns zeros straight away, before that rescale.  Otherwise the type-0 effects in dict order: reverb_rir,
+    time_dropout, quant; "empty_n" and "beep" are ignored, as the reference ignores them.  ValueError for a sox effect (types 1,
+    1.1, 3: the chain is not built here) and for an unknown name."""
+    steps = _array_steps(effects)
+    frames = np.array(frames)
+    large = bool(np.max(frames) > 10)
+    if large:
+        frames = frames / 2 ** 15
+    if frames.ndim > 1:
+        frames = np.squeeze(frames)
+    for key, params in steps:
+        if key == "empty_c":
+            return np.zeros_like(frames)
+        if key == "reverb_rir":
+            frames = reverb_rir(frames, _clips.as_numpy(_rir_of(rirs, params)))
+        elif key == "time_dropout":
+            frames = time_dropout(frames, params)
+        else:
+            frames = quantification(frames, params)
+    if large:
+        frames = frames * 2 ** 15
+    return frames
+
+
+def _random_select(probs, rng):
+    """random_.random_select: ONE chance for all the entries of `probs`"""
+    chance = int(rng.random() * 2 ** 31)
+    return [chance < p * 2 ** 31 for p in probs], chance
+
+
+def draw_array_effects(n, p_effects, effect_list, rir_nums, rng):
+    """RandomServer.generate(effect_list) for type-0 names, per item, in `effect_list` order, from the one generator: a name draws
+    its chance (`random_select` over p_effects[name]["prob"]) and is skipped when the first decision is false; otherwise its
+    parameters through `_uniform` -- reverb_rir [True, int(U(0, rir_nums))]; time_dropout [True, [start, trunk]] with start =
+    U(drop_range[0], drop_range[1] - max_segment), then trunk = U(0, max_segment); quant [decisions, int(U(*bins))]; empty_c,
+    empty_n, beep [True, None].  -> n dicts that `array_effects` takes."""
+    out = []
+    for _ in range(n):
+        item = {}
+        for name in effect_list:
+            if EFFECT_TYPES.get(name) != 0:
+                raise ValueError("draw_array_effects: %s is no array effect" % (name,))
+            p = p_effects[name]
+            decision, _chance = _random_select(p["prob"], rng)
+            if not decision[0]:
+                continue
+            if name == "reverb_rir":
+                item[name] = [True, int(_uniform(0, rir_nums, rng))]
+            elif name == "time_dropout":
+                start = _uniform(p["drop_range"][0], p["drop_range"][1] - p["max_segment"], rng)
+                trunk_length = _uniform(0.0, p["max_segment"], rng)
+                item[name] = [True, [start, trunk_length]]
+            elif name == "quant":
+                item[name] = [decision, int(_uniform(p["bins"][0], p["bins"][1], rng))]
+            else:
+                item[name] = [True, None]
+        out.append(item)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# batch forms of the array effects (Engine.quantize, Engine.time_dropout, csrc/effects.hip) and of the whole tail
+# ------------------------------------------------------------------------------------------------------------------
+_FX_DTYPES = (torch.float32, torch.float64)
+
+
+def _fx_dtype(c):
+    """The torch dtype of a clip the device effects take -- non-empty, 1-D, float32 or float64 -- or None"""
+    if len(list(c.shape)) != 1 or c.shape[0] == 0:
+        return None
+    for dtype in _FX_DTYPES:
+        if str(c.dtype).endswith(str(dtype).split(".")[-1]):
+            return dtype
+    return None
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _fx_list(clips, takes, call, host, engine, to_host):
+    """What the two list forms share: the clips i with takes(i) as padded batches of one dtype (rows padded to a multiple of 4: the
+    kernels' 16-byte accesses) through call(eng, x, idx, lens) -> (B, ld) tensor; every other item through host(i)."""
+    lengths = [c.shape[0] if len(list(c.shape)) else 0 for c in clips]
+    out = [None] * len(clips)
+    eng = engine      # the default Engine is created only when something needs the device
+    for dtype in _FX_DTYPES:
+        dev = [i for i in range(len(clips)) if _fx_dtype(clips[i]) == dtype and takes(i)]
+        for idx in _clips.batches(dev, lengths, MAX_BATCH):
+            eng = _engine_or_default(eng)
+            lens = [lengths[i] for i in idx]
+            x = _clips.pad([clips[i] for i in idx], eng.device, dtype, width=(lens[-1] + 3) // 4 * 4)
+            for i, row in zip(idx, _clips.unpad(call(eng, x, idx, lens), lens, to_host)):
+                out[i] = row
+    for i in range(len(clips)):
+        if out[i] is None:
+            y = host(i)
+            if not to_host:
+                eng = _engine_or_default(eng)
+                y = _clips.to_device(y, eng.device)
+            out[i] = y
+    return out
+
+
+def quantification_list(clips, bins, engine=None, to_host=True):
+    """`quantification` for a list of clips, bins one int for all or one per clip.  Non-empty 1-D float32 and float64 clips (NumPy or
+    device tensors) whose bins is an int in 0..16 are grouped by dtype, sorted by length and go through Engine.quantize as padded
+    batches of up to MAX_BATCH, bit for bit the host function; every other item takes the host function.  -> list in the caller's
+    order: float64 NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    bins = _per_clip(bins, len(clips), "quantification_list: bins")
+    return _fx_list(clips, lambda i: _is_int(bins[i]) and 0 <= bins[i] <= MAX_QUANT_BINS,
+                    lambda eng, x, idx, lens: eng.quantize(x, [int(bins[i]) for i in idx], lengths=lens)[0],
+                    lambda i: quantification(_clips.as_numpy(clips[i]), [True, bins[i]]), engine, to_host)
+
+
+def time_dropout_list(clips, params, engine=None, to_host=True):
+    """`time_dropout` for a list of clips, params = [decision, [start, trunk_length]] for all or one such per clip.  The sample range
+    of every clip is computed on the host exactly as the single-clip function computes it; non-empty 1-D float32 and float64 clips
+    with 0 <= start <= end go through Engine.time_dropout as padded batches of up to MAX_BATCH -- bit for bit the host function
+    outside the two smoothed patches, inside them to the rounding of a 25-term float64 sum (tests/test_gpu_array_effects.py) --,
+    every other item takes the host function on a copy.  The inputs are never modified.  -> list in the caller's order, each in
+    its clip's dtype: NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    params = list(params)
+    if not (params and isinstance(params[0], (list, tuple))):      # one [decision, [start, trunk_length]] for all
+        params = [params] * len(clips)
+    if len(params) != len(clips):
+        raise ValueError("time_dropout_list: params: %d entries for %d clips" % (len(params), len(clips)))
+    ranges = [_dropout_range(c.shape[0], p) if len(list(c.shape)) else (0, -1) for c, p in zip(clips, params)]
+    return _fx_list(clips, lambda i: 0 <= ranges[i][0] <= ranges[i][1],
+                    lambda eng, x, idx, lens: eng.time_dropout(x, [ranges[i][0] for i in idx], [ranges[i][1] for i in idx], lengths=lens),
+                    lambda i: time_dropout(np.array(_clips.as_numpy(clips[i])), params[i]), engine, to_host)
+
+
+def array_effects_list(clips, effects, rirs=None, engine=None, to_host=True):
+    """`array_effects` for a list of clips, effects[i] the dict of clip i.  Non-empty 1-D float32 and float64 clips stay on the
+    device from their first effect to the end: the LARGESCALE division and multiplication by 2 ** 15 and "empty_c" are exact torch
+    operations where the clip is; then, step position by step position, the clips whose next type-0 effect is the same are handed
+    together to `reverb_rir_list`, `time_dropout_list` or `quantification_list` with to_host=False -- exactly the composition of
+    those three --, and the results come down in one download per dtype at the end.  Every other clip takes `array_effects`.  All
+    the dicts are checked before anything runs.  -> list in the caller's order: NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    effects = list(effects)
+    if len(effects) != len(clips):
+        raise ValueError("array_effects_list: %d dicts for %d clips" % (len(effects), len(clips)))
+    steps = [_array_steps(e) for e in effects]
+    eng = engine
+    cur = [None] * len(clips)
+    large = [False] * len(clips)
+    chain = []      # the clips that walk the device chain
+    for i, c in enumerate(clips):
+        if _fx_dtype(c) is None:
+            cur[i] = array_effects(_clips.as_numpy(c), effects[i], rirs)
+            continue
+        t = _clips.as_tensor(c)
+        large[i] = bool(torch.max(t) > 10)
+        if steps[i] and steps[i][0][0] == "empty_c":
+            cur[i] = torch.zeros_like(t)
+            large[i] = False      # (returned before the rescale; zeros either way)
+            continue
+        cur[i] = t / 2 ** 15 if large[i] else t
+        chain.append(i)
+    for pos in range(max([len(steps[i]) for i in chain], default=0)):
+        for name in ("reverb_rir", "time_dropout", "quant"):
+            idx = [i for i in chain if len(steps[i]) > pos and steps[i][pos][0] == name]
+            if not idx:
+                continue
+            eng = _engine_or_default(eng)
+            group, par = [cur[i] for i in idx], [steps[i][pos][1] for i in idx]
+            if name == "reverb_rir":
+                if rirs is None:
+                    raise ValueError("array_effects: reverb_rir needs the list of RIRs")
+                ys = reverb_rir_list(group, rirs, rir_index=[p[1] for p in par], engine=eng, to_host=False)
+            elif name == "time_dropout":
+                ys = time_dropout_list(group, par, engine=eng, to_host=False)
+            else:
+                ys = quantification_list(group, [p[1] for p in par], engine=eng, to_host=False)
+            for i, y in zip(idx, ys):
+                cur[i] = y
+    for i in chain:
+        if large[i]:
+            cur[i] = cur[i] * 2 ** 15
+    if not to_host:
+        for i in range(len(clips)):
+            eng = _engine_or_default(eng)
+            cur[i] = _clips.to_device(cur[i], eng.device)
+        return cur
+    for dtype in _FX_DTYPES:      # one download per dtype for what is on the device
+        idx = [i for i in range(len(clips)) if isinstance(cur[i], torch.Tensor) and cur[i].is_cuda and cur[i].dtype == dtype]
+        if idx:
+            lens = [cur[i].shape[0] for i in idx]
+            for i, row in zip(idx, _clips.unpad(_clips.pad([cur[i] for i in idx], cur[idx[0]].device, dtype), lens, True)):
+                cur[i] = row
+    return [_clips.as_numpy(c) for c in cur]
