@@ -17,7 +17,7 @@ from voicefixer_main_amd import clips as vclips, simulate  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-C = 4096           # kFxChunk (csrc/vfx_internal.h): samples of a clip per workgroup of the element-wise passes
+C = 4096           # kClipChunk (csrc/clip_batch.h): samples of a clip per workgroup of the element-wise passes
 LENGTHS = [1, 2, 63, 64, 65, 255, 256, 257, C - 1, C, C + 1, 2 * C + 1, 3000]
 DTYPES = [np.float32, np.float64]
 BINS = [0, 1, 2, 3, 8, 12, 16]
@@ -312,6 +312,16 @@ def test_refusals(eng, dtype):
         eng.quantize(x.to(torch.float16), 3)
     with pytest.raises(ValueError):
         eng.time_dropout(x, [1, 2, 3], [4, 5, 6])
+    # the C entry points with a row stride of y that does not hold the clips, a negative one included
+    import ctypes
+    from voicefixer_main_amd.simulate import smooth_matrix
+    f64, lens, ptr = int(dtype == torch.float64), (ctypes.c_int64 * 2)(400, 400), lambda t: ctypes.c_void_p(t.data_ptr())
+    for ldy in (399, -1):
+        assert eng.lib.vfx_quantize(eng.h, ptr(x), f64, 2, 400, lens, (ctypes.c_int * 2)(3, 3), ptr(yq), ldy, None, None) != 0
+        assert b"the rows hold 400 and %d" % ldy in eng.lib.vfx_last_error()
+        assert eng.lib.vfx_time_dropout(eng.h, ptr(x), f64, 2, 400, lens, (ctypes.c_int64 * 2)(10, 10), (ctypes.c_int64 * 2)(100, 100),
+                                        smooth_matrix().ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(yd), ldy, None) != 0
+        assert b"the rows hold 400 and %d" % ldy in eng.lib.vfx_last_error()
     torch.cuda.synchronize()
     assert (yq == 7.0).all() and (yd == 7.0).all()      # nothing was launched
     q, _ = eng.quantize(x, [3, 16], _y=yq)              # ... and the same buffers take the good calls

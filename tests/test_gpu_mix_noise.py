@@ -16,7 +16,7 @@ from voicefixer_main_amd import simulate  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-C = 4096           # kMixChunk (csrc/vfx_internal.h): samples per workgroup, and per float64 partial sum of the level rule
+C = 4096           # kClipChunk (csrc/clip_batch.h): samples per workgroup, and per float64 partial sum of the level rule
 LENGTHS = [1, 2, 63, 64, 65, 255, 256, 257, C - 1, C, C + 1, 2 * C + 1, 3000]
 F32 = np.float32
 BAR = 16 * 2.0 ** -24      # the HQ forms against the float64 yardstick: see test_hq_forms_against_float64
@@ -129,6 +129,31 @@ def test_batch_invariance(eng, form):
                             noise_weight=weights[b], scale=scales[b], want_noisy=True)
         for k in got:
             assert own[k].shape == (n,) and torch.equal(got[k][b, :n], own[k]), "clip %d, %s" % (b, k)
+
+
+def test_second_slice_of_a_call(eng):
+    """130 clips in one call (128 clips travel per set of launches, kMixMaxClips) == rows 0-127 and rows 128-129 each in a call of
+    their own, bit for bit: form 2 with the noisy output, a weight and a scale per clip"""
+    B = 130
+    lengths = [(1, 65, 257, C - 1, C, C + 1, 3000)[b % 7] for b in range(B)]
+    L = C + 4
+    rng = np.random.default_rng(80)
+    batch = {}
+    for k, clips in zip(NAMES[2], _signals(4, lengths, seed=81)):
+        x = np.zeros((B, L), F32)
+        for b, c in enumerate(clips):
+            x[b, :len(c)] = c
+        batch[k] = torch.from_numpy(x).to(DEV)
+    weights, scales = [10 ** (s / 20) for s in rng.uniform(-5, 35, B)], list(rng.uniform(0.6, 1.0, B))
+
+    def run(lo, hi):
+        return eng.mix_noise(**{k: v[lo:hi] for k, v in batch.items()}, lengths=lengths[lo:hi], noise_weight=weights[lo:hi],
+                             scale=scales[lo:hi], want_noisy=True)
+    whole, head, tail = run(0, B), run(0, 128), run(128, B)
+    assert set(whole) == set(NAMES[2]) | {"noisy"}
+    for k in whole:
+        assert whole[k].shape == (B, L) and torch.equal(whole[k], torch.cat([head[k], tail[k]])), k
+        assert bool(torch.isfinite(whole[k]).all()) and all(bool(whole[k][b, :n].any()) for b, n in enumerate(lengths))
 
 
 @pytest.mark.parametrize("form", [1, 2])

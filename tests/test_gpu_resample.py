@@ -97,6 +97,28 @@ def test_resample_batch_with_lengths(eng, sr_in, sr_out):
         assert torch.equal(same[i, :n].cpu(), torch.from_numpy(clips[i])) and not same[i, n:].any(), i
 
 
+def test_resample_second_slice_of_a_call(eng):
+    """66 clips of 50 .. 500 samples at 3/2 in one call (64 clips travel per launch, kResampleMaxClips), the rows padded with 7.0:
+    every row is scipy's on that clip alone, zero past its output length"""
+    sr_in, sr_out = 32000, 48000
+    assert _pair(sr_in, sr_out) == (3, 2)
+    rng = np.random.default_rng(21)
+    B = 66
+    lengths = [int(v) for v in rng.integers(50, 501, B)]
+    lengths[63], lengths[64], lengths[65] = 500, 50, 499
+    batch = torch.full((B, 503), 7.0, dtype=torch.float32)
+    clips = [rng.uniform(-1, 1, n).astype(np.float32) for n in lengths]
+    for i, c in enumerate(clips):
+        batch[i, :len(c)] = torch.from_numpy(c)
+    y, out_lengths = eng.resample(batch.to(DEV), sr_in, sr_out, lengths=lengths)
+    y = y.cpu()
+    assert y.shape == (B, 750)
+    for i, c in enumerate(clips):
+        want = _scipy(c, sr_in, sr_out)
+        assert out_lengths[i] == want.shape[0] and torch.equal(y[i, :out_lengths[i]], want), i
+        assert not y[i, out_lengths[i]:].any(), i
+
+
 @pytest.mark.parametrize("sr_in,sr_out", [(48000, 44100), (16000, 44100), (8000, 44100), (44100, 16000)])
 def test_resample_windows_concatenate(eng, sr_in, sr_out):
     """Outputs over arbitrary [o0, o0 + n) windows, each from the minimal input window, concatenate to the whole result; a window

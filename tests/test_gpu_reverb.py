@@ -134,6 +134,30 @@ def test_rows_are_independent(eng):
             assert not y[b, lengths[b]:].any(), (normalize, b)
 
 
+def test_second_slice_of_a_call(eng):
+    """130 clips in one call (128 clips travel per launch, kReverbMaxClips) == rows 0-127 and rows 128-129 each in a call of their
+    own, y and peaks bit for bit, with the normalisation.  The index is explicit: the default b % R goes by the row in the call."""
+    rng = np.random.default_rng(8)
+    B = 130
+    lengths = [int(n) for n in rng.integers(33, 601, B)]
+    lengths[127], lengths[128], lengths[129] = 600, 33, 599
+    rir_lengths = [40, 7, 33]
+    index = [int(i) for i in rng.integers(0, 3, B)]
+    x, _ = _batch([(rng.uniform(-1, 1, n) * (0.05, 1.0)[b % 2]).astype(F32) for b, n in enumerate(lengths)])      # either side of 0.99
+    r, _ = _batch([rng.uniform(-1, 1, m).astype(F32) for m in rir_lengths])
+    xd, rd = torch.from_numpy(x).to(DEV), torch.from_numpy(r).to(DEV)
+
+    def run(lo, hi):
+        return eng.reverb_rir(xd[lo:hi], rd, rir_index=index[lo:hi], lengths=lengths[lo:hi], rir_lengths=rir_lengths, normalize=True)
+    (y, peaks), (y0, peaks0), (y1, peaks1) = run(0, B), run(0, 128), run(128, B)
+    assert y.shape == (B, 600) and torch.equal(y, torch.cat([y0, y1])) and torch.equal(peaks, torch.cat([peaks0, peaks1]))
+    scaled = peaks > 0.99
+    assert bool(scaled.any()) and not bool(scaled.all()) and bool((peaks > 0).all())
+    for b in (0, 127, 128, 129):      # and the rows are what the clip alone gives
+        own, pk = eng.reverb_rir(xd[b, :lengths[b]], rd[index[b], :rir_lengths[index[b]]], normalize=True)
+        assert torch.equal(y[b, :lengths[b]], own) and torch.equal(peaks[b], pk) and not bool(y[b, lengths[b]:].any())
+
+
 def test_peak_covers_the_tail(eng):
     """x = e_99 of 100 samples, h = 0.5 at tap 0 and 2.0 at tap 49: the written samples peak at 0.5, the full convolution at 2.0"""
     x = np.zeros(100, F32)

@@ -182,7 +182,7 @@ def test_errors_launch_nothing(eng):
     dbl = ctypes.POINTER(ctypes.c_double)
     y = torch.full((4, 500), 5.0, dtype=torch.float64, device=DEV)
 
-    def call(lengths, index, sections=(1, 2, 2, 5), padlens=(9, 12, 15, 33), Smax=5, scale=1.0):
+    def call(lengths, index, sections=(1, 2, 2, 5), padlens=(9, 12, 15, 33), Smax=5, scale=1.0, ldy=500):
         sos = np.zeros((4, Smax, 6))
         sos[..., 0] = sos[..., 3] = 1.0
         for f, d in enumerate(designs):
@@ -191,7 +191,7 @@ def test_errors_launch_nothing(eng):
         return eng.lib.vfx_sosfiltfilt_bank(eng.h, ctypes.c_void_p(batch.data_ptr()), 0, 4, 500, (ctypes.c_int64 * 4)(*lengths),
                                             (ctypes.c_int * 4)(*index), sos.ctypes.data_as(dbl), zi.ctypes.data_as(dbl),
                                             (ctypes.c_int * 4)(*sections), (ctypes.c_int * 4)(*padlens), 4, Smax,
-                                            ctypes.c_void_p(y.data_ptr()), 500, None)
+                                            ctypes.c_void_p(y.data_ptr()), ldy, None)
     assert call([500, 20, 20, 20], [0, 3, 1, 2]) != 0
     err = eng.lib.vfx_last_error()
     assert b"clip 1 " in err and b"20 samples" in err and b"which is 33" in err
@@ -201,6 +201,8 @@ def test_errors_launch_nothing(eng):
     assert call([500, 500, 500, 500], [0, 1, 2, 3], sections=(1, 2, 6, 5)) != 0 and b"6 sections" in eng.lib.vfx_last_error()
     assert call([500, 500, 500, 500], [0, 1, 2, 3], scale=2.0) != 0 and b"should be 1" in eng.lib.vfx_last_error()
     assert call([500, 501, 500, 500], [0, 1, 2, 3]) != 0
+    for ldy in (499, -1):      # a row stride of y that does not hold the clips, a negative one included
+        assert call([500, 500, 500, 500], [0, 1, 2, 3], ldy=ldy) != 0 and b"the rows hold 500 and %d" % ldy in eng.lib.vfx_last_error()
     torch.cuda.synchronize()
     assert bool((y == 5.0).all())
     with pytest.raises(RuntimeError, match="which is 33"):

@@ -111,6 +111,27 @@ def test_batch_with_lengths(eng, name):
             assert not y[i, n:].any(), (B, i, n)
 
 
+def test_second_slice_of_a_call(eng):
+    """130 clips of 100 .. 400 samples in one call (128 clips travel per launch pair, kSosMaxClips), a 2-section design, float32 and
+    float64 rows padded with 7.0: every row is SciPy on that clip alone and zero past its end"""
+    sos = DESIGNS["butter3"]
+    assert sos.shape[0] == 2
+    rng = np.random.default_rng(17)
+    B = 130
+    lengths = [int(v) for v in rng.integers(100, 401, B)]
+    lengths[127], lengths[128], lengths[129] = 400, 100, 399
+    for dtype in (torch.float32, torch.float64):
+        batch = torch.full((B, 405), 7.0, dtype=dtype)
+        clips = [torch.from_numpy(rng.uniform(-1, 1, n)).to(dtype) for n in lengths]
+        for i, c in enumerate(clips):
+            batch[i, :len(c)] = c
+        y = eng.sosfiltfilt(batch.to(DEV), sos, lengths=lengths).cpu()
+        assert y.dtype == torch.float64 and y.shape == batch.shape
+        for i, n in enumerate(lengths):
+            assert torch.equal(y[i, :n], torch.from_numpy(signal.sosfiltfilt(sos, clips[i].numpy()).copy())), (dtype, i, n)
+            assert not y[i, n:].any(), (dtype, i, n)
+
+
 def test_errors_launch_nothing(eng):
     import ctypes
     from voicefixer_main_amd import _lib
@@ -129,13 +150,16 @@ def test_errors_launch_nothing(eng):
     sos17 = np.ascontiguousarray(np.tile(sos[:1], (17, 1)))
     zi = np.zeros((17, 2))
 
-    def call(lengths, s, S):
+    def call(lengths, s, S, ldy=500):
         lens = (ctypes.c_int64 * 3)(*lengths)
         return eng.lib.vfx_sosfiltfilt(eng.h, ctypes.c_void_p(batch.data_ptr()), 0, 3, 500, lens, s.ctypes.data_as(dbl), S,
-                                       zi.ctypes.data_as(dbl), padlen, ctypes.c_void_p(y.data_ptr()), 500, None)
+                                       zi.ctypes.data_as(dbl), padlen, ctypes.c_void_p(y.data_ptr()), ldy, None)
     assert call([500, 500, 500], sos17, 17) != 0 and b"17 sections" in eng.lib.vfx_last_error()
     assert call([500, padlen, 500], np.ascontiguousarray(sos), sos.shape[0]) != 0 and b"greater than padlen" in eng.lib.vfx_last_error()
     assert call([500, 501, 500], np.ascontiguousarray(sos), sos.shape[0]) != 0
+    for ldy in (499, 0, -1):      # a row stride of y that does not hold the clips, a negative one included
+        assert call([500, 500, 500], np.ascontiguousarray(sos), sos.shape[0], ldy=ldy) != 0
+        assert b"the rows hold 500 and %d" % ldy in eng.lib.vfx_last_error()
     torch.cuda.synchronize()
     assert bool((y == 5.0).all())
     with pytest.raises(RuntimeError, match="17 sections"):

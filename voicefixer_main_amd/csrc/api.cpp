@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <numeric>
 
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 namespace vfx {
@@ -490,6 +491,32 @@ int vfx_resample(vfx_handle* h, const float* x, int B, int64_t ldx, int64_t x0, 
   VFX_API_END
 }
 
+// What every clip-batch entry point checks of its lengths before it launches anything: min_len <= lengths[b] <= ldx, <= *ldy (NULL: the
+// operation has no second stride to hold a clip to), <= cap -- what the operation's kernels take in 32-bit indices.  `more_than` names
+// what a minimum above 1 is one more than (sosfiltfilt's padlen); without it a clip below the minimum is empty, or negative where empty
+// clips are taken.  -> the longest clip, or throws
+static int64_t check_clip_lengths(const char* who, int B, const int64_t* lengths, int64_t min_len, const char* more_than, int64_t ldx,
+                                  const int64_t* ldy, int64_t cap) {
+  int64_t lmax = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long n = lengths[b];
+    if (more_than)
+      VFX_CHECK(n >= min_len, "%s: clip %d has %lld samples: the length must be greater than %s, which is %lld", who, b, n, more_than,
+                (long long)(min_len - 1));
+    else if (min_len <= 0)
+      VFX_CHECK(n >= min_len, "%s: clip %d has a negative length", who, b);
+    else
+      VFX_CHECK(n >= min_len, "%s: clip %d is empty (%lld samples)", who, b, n);
+    if (!ldy)
+      VFX_CHECK(n <= ldx && n <= cap, "%s: clip %d has %lld samples, the rows hold %lld", who, b, n, (long long)ldx);
+    else
+      VFX_CHECK(n <= ldx && n <= *ldy && n <= cap, "%s: clip %d has %lld samples, the rows hold %lld and %lld", who, b, n, (long long)ldx,
+                (long long)*ldy);
+    lmax = std::max(lmax, lengths[b]);
+  }
+  return lmax;
+}
+
 int64_t vfx_resample_each_out_len(int64_t n_in, int up, int down) {
   ResamplePair p;
   if (n_in < 0 || n_in > ((int64_t)1 << 46) || !resample_each_reduce(up, down, &p)) return -1;
@@ -521,10 +548,8 @@ int vfx_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ld
       VFX_CHECK(false, "vfx_resample_each: clip %d: the pair %lld/%lld (reduced) is past the cap max(up, down) <= %d", b,
                 (long long)(up[f] / g), (long long)(down[f] / g), kResampleEachMaxRate);
     }
-    VFX_CHECK(lens_in[b] >= 0, "vfx_resample_each: clip %d has a negative length", b);
-    VFX_CHECK(lens_in[b] <= ldx && lens_in[b] <= ((int64_t)1 << 46), "vfx_resample_each: clip %d has %lld samples, the rows hold %lld", b,
-              (long long)lens_in[b], (long long)ldx);
   }
+  check_clip_lengths("vfx_resample_each", B, lens_in, 0, nullptr, ldx, nullptr, (int64_t)1 << 46);
   for (int f = 0; f < F; ++f)  // (a design past the cap that no clip asks for)
     VFX_CHECK(taken[f], "vfx_resample_each: design %d: the pair %d/%d is past the cap max(up, down) <= %d after the gcd", f, up[f], down[f],
               kResampleEachMaxRate);
@@ -544,14 +569,7 @@ int vfx_sosfiltfilt(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx,
   VFX_CHECK(padlen >= 0 && padlen <= 3 * (2 * kSosMaxSections + 1), "vfx_sosfiltfilt: padlen %d (need 0 <= padlen <= %d)", padlen,
             3 * (2 * kSosMaxSections + 1));
   for (int i = 0; i < S; ++i) VFX_CHECK(sos[i * 6 + 3] == 1.0, "vfx_sosfiltfilt: sos[%d][3] = %g, should be 1", i, sos[i * 6 + 3]);
-  int64_t lmax = 0;
-  for (int b = 0; b < B; ++b) {
-    VFX_CHECK(lengths[b] > padlen, "vfx_sosfiltfilt: clip %d has %lld samples: the length must be greater than padlen, which is %d", b,
-              (long long)lengths[b], padlen);
-    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 1024,
-              "vfx_sosfiltfilt: clip %d has %lld samples, the rows hold %lld and %lld", b, (long long)lengths[b], (long long)ldx, (long long)ldy);
-    lmax = std::max(lmax, lengths[b]);
-  }
+  const int64_t lmax = check_clip_lengths("vfx_sosfiltfilt", B, lengths, padlen + 1, "padlen", ldx, &ldy, 0x7fffffff - 1024);
   const int64_t ldf = (lmax + 2 * padlen + 63) / 64 * 64;
   double* const f = reinterpret_cast<double*>(h->sos_ws.ensure(h, (size_t)std::min(B, kSosMaxClips) * ldf * sizeof(double), 0));
   launch_sosfiltfilt(x, x_f64, B, ldx, lengths, sos, S, zi, padlen, f, ldf, y, ldy, static_cast<hipStream_t>(stream));
@@ -575,16 +593,14 @@ int vfx_sosfiltfilt_bank(vfx_handle* h, const void* x, int x_f64, int B, int64_t
       VFX_CHECK(sos[((size_t)f * Smax + i) * 6 + 3] == 1.0, "vfx_sosfiltfilt_bank: design %d: sos[%d][3] = %g, should be 1", f, i,
                 sos[((size_t)f * Smax + i) * 6 + 3]);
   }
+  check_clip_lengths("vfx_sosfiltfilt_bank", B, lengths, INT64_MIN, nullptr, ldx, &ldy, 0x7fffffff - 1024);  // (no common minimum:)
   int64_t lext = 0;
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < B; ++b) {  // the minimum is the padlen of the clip's own design
     VFX_CHECK(filter_index[b] >= 0 && filter_index[b] < F, "vfx_sosfiltfilt_bank: clip %d asks for design %d of %d", b, filter_index[b], F);
     const int padlen = padlens[filter_index[b]];
     VFX_CHECK(lengths[b] > padlen,
               "vfx_sosfiltfilt_bank: clip %d has %lld samples: the length must be greater than padlen, which is %d for its design %d", b,
               (long long)lengths[b], padlen, filter_index[b]);
-    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 1024,
-              "vfx_sosfiltfilt_bank: clip %d has %lld samples, the rows hold %lld and %lld", b, (long long)lengths[b], (long long)ldx,
-              (long long)ldy);
     lext = std::max(lext, lengths[b] + 2 * padlen);
   }
   const int64_t ldf = (lext + 63) / 64 * 64;
@@ -611,15 +627,9 @@ int vfx_reverb_rir(vfx_handle* h, const float* x, int B, int64_t ldx, const int6
               kReverbMaxTaps);
     VFX_CHECK(rir_lengths[r] <= ldr, "vfx_reverb_rir: RIR %d has %lld taps, the rows hold %lld", r, (long long)rir_lengths[r], (long long)ldr);
   }
-  int64_t lmax = 0;
-  for (int b = 0; b < B; ++b) {
-    VFX_CHECK(lengths[b] >= 1, "vfx_reverb_rir: clip %d is empty (%lld samples)", b, (long long)lengths[b]);
-    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= 0x7fffffff - kReverbMaxTaps - 2 * kReverbTile,
-              "vfx_reverb_rir: clip %d has %lld samples, the rows of x hold %lld", b, (long long)lengths[b], (long long)ldx);
-    VFX_CHECK(!rir_index || (rir_index[b] >= 0 && rir_index[b] < R), "vfx_reverb_rir: clip %d asks for RIR %d of %d", b,
-              rir_index ? rir_index[b] : 0, R);
-    lmax = std::max(lmax, lengths[b]);
-  }
+  const int64_t lmax = check_clip_lengths("vfx_reverb_rir", B, lengths, 1, nullptr, ldx, nullptr, 0x7fffffff - kReverbMaxTaps - 2 * kReverbTile);
+  for (int b = 0; rir_index && b < B; ++b)
+    VFX_CHECK(rir_index[b] >= 0 && rir_index[b] < R, "vfx_reverb_rir: clip %d asks for RIR %d of %d", b, rir_index[b], R);
   VFX_CHECK(ldy >= lmax, "vfx_reverb_rir: ldy = %lld is too small for a clip of %lld samples", (long long)ldy, (long long)lmax);
   launch_reverb_rir(x, B, ldx, lengths, rirs, ldr, rir_lengths, rir_index, R, normalize, y, ldy, peaks, static_cast<hipStream_t>(stream));
   VFX_API_END
@@ -639,13 +649,7 @@ int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* len
   VFX_CHECK((form == 2) == (aug != nullptr), "vfx_mix_noise: form %d %s aug (aug goes with hq: form 2)", form, form == 2 ? "needs" : "takes no");
   VFX_CHECK((hq || !hq_out) && (aug || !aug_out), "vfx_mix_noise: form %d returns no %s", form, hq_out && !hq ? "hq" : "aug");
   VFX_CHECK(front_out || noise_out || hq_out || aug_out || noisy, "vfx_mix_noise: no output asked for");
-  int64_t lmax = 0;
-  for (int b = 0; b < B; ++b) {
-    VFX_CHECK(lengths[b] >= 1, "vfx_mix_noise: clip %d is empty (%lld samples)", b, (long long)lengths[b]);
-    VFX_CHECK(lengths[b] <= ld && lengths[b] <= 0x7fffffff - 2 * kMixChunk, "vfx_mix_noise: clip %d has %lld samples, the rows hold %lld", b,
-              (long long)lengths[b], (long long)ld);
-    lmax = std::max(lmax, lengths[b]);
-  }
+  const int64_t lmax = check_clip_lengths("vfx_mix_noise", B, lengths, 1, nullptr, ld, nullptr, 0x7fffffff - 2 * kClipChunk);
   char* const ws = h->mix_ws.ensure(h, mix_workspace_bytes(B, lmax), 0);
   const float* const in[4] = {front, noise, hq, aug};
   float* const out[5] = {front_out, noise_out, hq_out, aug_out, noisy};
@@ -656,21 +660,12 @@ int vfx_mix_noise(vfx_handle* h, int form, int B, int64_t ld, const int64_t* len
 // ---------------------------------------------------------------------------------------------
 // array effects (MagicalEffects.quantification and time_dropout on the device: effects.hip)
 // ---------------------------------------------------------------------------------------------
-// what the two entry points check of a batch of clips; -> nothing, or throws
-static void check_fx_clips(const char* who, int B, int64_t ldx, int64_t ldy, const int64_t* lengths) {
-  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "%s: %d clips (need 1 <= B <= %d)", who, B, kMaxVarlenClips);
-  for (int b = 0; b < B; ++b) {
-    VFX_CHECK(lengths[b] >= 1, "%s: clip %d is empty (%lld samples)", who, b, (long long)lengths[b]);
-    VFX_CHECK(lengths[b] <= ldx && lengths[b] <= ldy && lengths[b] <= 0x7fffffff - 2 * kFxChunk,
-              "%s: clip %d has %lld samples, the rows hold %lld and %lld", who, b, (long long)lengths[b], (long long)ldx, (long long)ldy);
-  }
-}
-
 int vfx_quantize(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* bins, double* y,
                  int64_t ldy, void* peaks, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(x && lengths && bins && y && (x_f64 == 0 || x_f64 == 1), "vfx_quantize: bad argument");
-  check_fx_clips("vfx_quantize", B, ldx, ldy, lengths);
+  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "vfx_quantize: %d clips (need 1 <= B <= %d)", B, kMaxVarlenClips);
+  check_clip_lengths("vfx_quantize", B, lengths, 1, nullptr, ldx, &ldy, 0x7fffffff - 2 * kClipChunk);
   for (int b = 0; b < B; ++b)
     VFX_CHECK(bins[b] >= 0 && bins[b] <= kFxMaxBins, "vfx_quantize: clip %d: %d bins (need 0 <= bins <= %d)", b, bins[b], kFxMaxBins);
   auto* const bits = reinterpret_cast<unsigned long long*>(h->fx_ws.ensure(h, (size_t)kMaxVarlenClips * sizeof(unsigned long long), 0));
@@ -682,7 +677,8 @@ int vfx_time_dropout(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx
                      const int64_t* ends, const double* smooth, void* y, int64_t ldy, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(x && lengths && starts && ends && smooth && y && (x_f64 == 0 || x_f64 == 1), "vfx_time_dropout: bad argument");
-  check_fx_clips("vfx_time_dropout", B, ldx, ldy, lengths);
+  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "vfx_time_dropout: %d clips (need 1 <= B <= %d)", B, kMaxVarlenClips);
+  check_clip_lengths("vfx_time_dropout", B, lengths, 1, nullptr, ldx, &ldy, 0x7fffffff - 2 * kClipChunk);
   for (int b = 0; b < B; ++b)
     VFX_CHECK(starts[b] >= 0 && ends[b] >= starts[b], "vfx_time_dropout: clip %d: bad range [%lld, %lld) (need 0 <= start <= end)", b,
               (long long)starts[b], (long long)ends[b]);

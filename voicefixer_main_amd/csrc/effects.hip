@@ -11,7 +11,7 @@
 // k is settled by a binary search that COMPARES s with the exact levels: no expression of s is ever rounded to an index (for a
 // float64 clip s + 1 can round onto a level that s itself lies beside).  An arithmetic guess corrected against its neighbours was
 // measured too and is no faster: the map pass is bound by its float64 stores.  Zero, infinite and NaN peaks take the same five steps.
-//   k_fx_peaks     reads x            -> p (atomicMax on the bit pattern of |x|, 32 or 64 bits: order-independent, NaN on top)
+//   k_fx_peaks     reads x            -> p (atomicMax on the bit pattern of |x|, 32 or 64 bits)
 //   k_fx_quantize  reads x, writes y  -> rows zero from the clip's length up to ldy
 //
 // Time drop-out, per clip (start <= end, the reference's int(length * start) and int(length * start + length * trunk_length)):
@@ -22,10 +22,9 @@
 //                     i, rounded once to the clip's dtype.  M (96, 25) is smooth()'s cubic interpolation as a matrix: the
 //                     not-a-knot spline through 25 equidistant knots is linear in the knots (simulate.smooth_matrix builds it).
 //
-// The element-wise passes are one grid over the batch (blockIdx.y = clip, blockIdx.x = chunk of kFxChunk samples of it); a thread's
-// samples are 16-byte groups (4 floats, 2 doubles) at ROW-RELATIVE indices c0 + G (tid + 256 k).  A group is one 16-byte access when
-// the row's base is 16-byte aligned and the group lies inside the row; the groups of a misaligned row, and the tail group of a clip,
-// go sample by sample.  A clip's result depends on the clip alone: not on the batch, the row stride or the alignment.
+// The element-wise passes (k_fx_peaks, k_fx_quantize, k_fx_drop_copy) are grids over the batch in clip_batch.h's sample groups: a
+// clip's result depends on the clip alone.
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 #pragma clang fp contract(off)
@@ -52,92 +51,26 @@ struct DropArgs {
 };
 
 template <typename T>
-struct FxType;
-template <>
-struct FxType<float> {
-  using Bits = unsigned;
-  static __device__ __forceinline__ Bits abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-  static __device__ __forceinline__ float from_bits(Bits u) { return __uint_as_float(u); }
-};
-template <>
-struct FxType<double> {
-  using Bits = unsigned long long;
-  static __device__ __forceinline__ Bits abs_bits(double v) { return (Bits)__double_as_longlong(v) & 0x7fffffffffffffffull; }
-  static __device__ __forceinline__ double from_bits(Bits u) { return __longlong_as_double((long long)u); }
-};
-
-template <typename T>
-struct alignas(16) FxGroup {
-  T v[16 / sizeof(T)];
-};
-
-__device__ __forceinline__ bool fx_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// samples [j, j + G) of a row of n samples, j a multiple of G; zeros at and past n
-template <typename T>
-__device__ __forceinline__ void fx_load(const T* row, bool vec, int64_t j, int64_t n, T (&v)[16 / sizeof(T)]) {
-  constexpr int G = 16 / sizeof(T);
-  if (vec && j + G <= n) {
-    const FxGroup<T> q = *reinterpret_cast<const FxGroup<T>*>(row + j);
-#pragma unroll
-    for (int e = 0; e < G; ++e) v[e] = q.v[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < G; ++e) v[e] = j + e < n ? row[j + e] : T(0);
-  }
-}
-
-// N values into a row of ld, from index j on (j a multiple of 16 / sizeof(T)), in 16-byte groups where they are whole and aligned
-template <typename T, int N>
-__device__ __forceinline__ void fx_store(T* row, bool vec, int64_t j, int64_t ld, const T (&v)[N]) {
-  constexpr int G = 16 / sizeof(T);
-  static_assert(N % G == 0, "whole groups");
-#pragma unroll
-  for (int g = 0; g < N; g += G) {
-    if (vec && j + g + G <= ld) {
-      FxGroup<T> q;
-#pragma unroll
-      for (int e = 0; e < G; ++e) q.v[e] = v[g + e];
-      *reinterpret_cast<FxGroup<T>*>(row + j + g) = q;
-    } else {
-#pragma unroll
-      for (int e = 0; e < G; ++e)
-        if (j + g + e < ld) row[j + g + e] = v[g + e];
-    }
-  }
-}
-
-template <typename T>
 __global__ __launch_bounds__(kFxThreads) void k_fx_peaks(const QuantArgs a) {
-  using F = FxType<T>;
+  using F = ClipType<T>;
   using Bits = typename F::Bits;
-  constexpr int G = 16 / sizeof(T), K = kFxChunk / (G * kFxThreads);
-  static_assert(kFxChunk == G * kFxThreads * K, "a chunk is whole groups of every thread");
+  constexpr int G = 16 / sizeof(T), K = kClipChunk / (G * kFxThreads);
+  static_assert(kClipChunk == G * kFxThreads * K, "a chunk is whole groups of every thread");
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kFxChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= n) return;
   const T* row = static_cast<const T*>(a.x) + (int64_t)b * a.ldx;
-  const bool vec = fx_aligned(row);
+  const bool vec = clip_aligned(row);
   T v[K][G];
 #pragma unroll
-  for (int k = 0; k < K; ++k) fx_load(row, vec, c0 + G * (threadIdx.x + kFxThreads * k), n, v[k]);
+  for (int k = 0; k < K; ++k) clip_load(row, vec, c0 + G * (threadIdx.x + kFxThreads * k), n, v[k]);
   Bits peak = 0;  // (a sample past n was loaded as +0: bit pattern 0)
 #pragma unroll
   for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int e = 0; e < G; ++e) peak = max(peak, F::abs_bits(v[k][e]));
-  // the wave's max in registers, the workgroup's through LDS, then ONE atomic per workgroup: the atomics of a clip all land on one
-  // address (and those of 16 clips on one cache line), where they take their turns
   __shared__ Bits wave_peak[kFxThreads / 64];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) peak = max(peak, (Bits)__shfl_xor(peak, d));
-  if ((threadIdx.x & 63) == 0) wave_peak[threadIdx.x >> 6] = peak;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kFxThreads / 64; ++w) peak = max(peak, wave_peak[w]);
-    if (peak) atomicMax(reinterpret_cast<Bits*>(a.bits + b), peak);
-  }
+  clip_commit_peak<kFxThreads>(peak, reinterpret_cast<Bits*>(a.bits + b), wave_peak);
 }
 
 __device__ __forceinline__ double fx_level(int j, double inv_level) { return -1.0 + (double)(2 * j + 1) * inv_level; }  // exact
@@ -161,10 +94,10 @@ __device__ __forceinline__ double fx_quantize(T x, T p, double pd, int level, do
 
 template <typename T>
 __global__ __launch_bounds__(kFxThreads) void k_fx_quantize(const QuantArgs a) {
-  using F = FxType<T>;
-  constexpr int G = 16 / sizeof(T), K = kFxChunk / (G * kFxThreads);
+  using F = ClipType<T>;
+  constexpr int G = 16 / sizeof(T), K = kClipChunk / (G * kFxThreads);
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kFxChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= a.ldy) return;
   const T p = F::from_bits(*reinterpret_cast<const typename F::Bits*>(a.bits + b));
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.peaks) static_cast<T*>(a.peaks)[b] = p;
@@ -172,7 +105,7 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_quantize(const QuantArgs a) {
   const double inv_level = 1.0 / (double)level, pd = (double)p;
   const T* row = static_cast<const T*>(a.x) + (int64_t)b * a.ldx;
   double* out = a.y + (int64_t)b * a.ldy;
-  const bool vin = fx_aligned(row), vout = fx_aligned(out);
+  const bool vin = clip_aligned(row), vout = clip_aligned(out);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int64_t j = c0 + G * (threadIdx.x + kFxThreads * k);
@@ -182,24 +115,24 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_quantize(const QuantArgs a) {
     for (int e = 0; e < G; ++e) y[e] = 0.0;
     if (j < n) {
       T v[G];
-      fx_load(row, vin, j, n, v);
+      clip_load(row, vin, j, n, v);
 #pragma unroll
       for (int e = 0; e < G; ++e)
         if (j + e < n) y[e] = fx_quantize(v[e], p, pd, level, inv_level);
     }
-    fx_store(out, vout, j, a.ldy, y);
+    clip_store(out, vout, j, a.ldy, y);
   }
 }
 
 template <typename T>
 __global__ __launch_bounds__(kFxThreads) void k_fx_drop_copy(const DropArgs a) {
-  constexpr int G = 16 / sizeof(T), K = kFxChunk / (G * kFxThreads);
+  constexpr int G = 16 / sizeof(T), K = kClipChunk / (G * kFxThreads);
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kFxChunk, start = a.start[b], end = a.end[b];
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk, start = a.start[b], end = a.end[b];
   if (c0 >= a.ldy) return;
   const T* row = static_cast<const T*>(a.x) + (int64_t)b * a.ldx;
   T* out = static_cast<T*>(a.y) + (int64_t)b * a.ldy;
-  const bool vin = fx_aligned(row), vout = fx_aligned(out);
+  const bool vin = clip_aligned(row), vout = clip_aligned(out);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int64_t j = c0 + G * (threadIdx.x + kFxThreads * k);
@@ -209,12 +142,12 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_drop_copy(const DropArgs a) {
     for (int e = 0; e < G; ++e) y[e] = T(0);
     if (j < n) {
       T v[G];
-      fx_load(row, vin, j, n, v);
+      clip_load(row, vin, j, n, v);
 #pragma unroll
       for (int e = 0; e < G; ++e)
         if (j + e < n && !(j + e >= start && j + e < end)) y[e] = v[e];
     }
-    fx_store(out, vout, j, a.ldy, y);
+    clip_store(out, vout, j, a.ldy, y);
   }
 }
 
@@ -245,7 +178,7 @@ __global__ __launch_bounds__(128) void k_fx_drop_smooth(const DropArgs a) {
 template <typename T>
 static void quantize_launches(const QuantArgs& a, int nb, int64_t nmax, hipStream_t s) {
   const dim3 block(kFxThreads);
-  const dim3 pgrid((unsigned)((nmax + kFxChunk - 1) / kFxChunk), (unsigned)nb), qgrid((unsigned)((a.ldy + kFxChunk - 1) / kFxChunk), (unsigned)nb);
+  const dim3 pgrid((unsigned)((nmax + kClipChunk - 1) / kClipChunk), (unsigned)nb), qgrid((unsigned)((a.ldy + kClipChunk - 1) / kClipChunk), (unsigned)nb);
   hipLaunchKernelGGL(k_fx_peaks<T>, pgrid, block, 0, s, a);
   VFX_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_fx_quantize<T>, qgrid, block, 0, s, a);
@@ -259,28 +192,23 @@ void launch_quantize(const void* x, int x_f64, int B, int64_t ldx, const int64_t
   QuantArgs a{};
   a.ldx = ldx;
   a.ldy = ldy;
-  for (int b0 = 0; b0 < B; b0 += kFxMaxClips) {  // the clips' lengths and bins travel as kernel arguments, kFxMaxClips per launch
-    const int nb = std::min(B - b0, kFxMaxClips);
-    int64_t nmax = 0;
-    for (int i = 0; i < nb; ++i) {
-      a.len[i] = (int)lengths[b0 + i];
-      a.bins[i] = bins[b0 + i];
-      nmax = std::max(nmax, lengths[b0 + i]);
-    }
-    a.x = static_cast<const char*>(x) + (size_t)b0 * ldx * esz;
-    a.y = y + (int64_t)b0 * ldy;
+  for_clip_slices<kFxMaxClips>(B, [&](int b0, int nb) {
+    const int64_t nmax = narrow_clip_lengths(lengths, b0, nb, a.len);
+    std::copy(bins + b0, bins + b0 + nb, a.bins);
+    a.x = slice_rows(x, b0, ldx, esz);
+    a.y = slice_rows(y, b0, ldy);
     a.bits = bits + b0;
-    a.peaks = peaks ? static_cast<char*>(peaks) + (size_t)b0 * esz : nullptr;
+    a.peaks = slice_rows(peaks, b0, 1, esz);
     if (x_f64)
       quantize_launches<double>(a, nb, nmax, s);
     else
       quantize_launches<float>(a, nb, nmax, s);
-  }
+  });
 }
 
 template <typename T>
 static void drop_launches(const DropArgs& a, int nb, hipStream_t s) {
-  const dim3 grid((unsigned)((a.ldy + kFxChunk - 1) / kFxChunk), (unsigned)nb);
+  const dim3 grid((unsigned)((a.ldy + kClipChunk - 1) / kClipChunk), (unsigned)nb);
   hipLaunchKernelGGL(k_fx_drop_copy<T>, grid, dim3(kFxThreads), 0, s, a);
   VFX_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_fx_drop_smooth<T>, dim3((unsigned)nb), dim3(128), 0, s, a);
@@ -294,22 +222,20 @@ void launch_time_dropout(const void* x, int x_f64, int B, int64_t ldx, const int
   a.smooth = smooth;
   a.ldx = ldx;
   a.ldy = ldy;
-  for (int b0 = 0; b0 < B; b0 += kFxMaxClips) {
-    const int nb = std::min(B - b0, kFxMaxClips);
+  for_clip_slices<kFxMaxClips>(B, [&](int b0, int nb) {
+    narrow_clip_lengths(lengths, b0, nb, a.len);
     for (int i = 0; i < nb; ++i) {
-      const int64_t n = lengths[b0 + i];
-      a.len[i] = (int)n;
       // an index past the clip zeroes nothing and is no centre of a patch (n - c < 50), and so is the clip's length
-      a.start[i] = (int)std::min(starts[b0 + i], n);
-      a.end[i] = (int)std::min(ends[b0 + i], n);
+      a.start[i] = (int)std::min(starts[b0 + i], lengths[b0 + i]);
+      a.end[i] = (int)std::min(ends[b0 + i], lengths[b0 + i]);
     }
-    a.x = static_cast<const char*>(x) + (size_t)b0 * ldx * esz;
-    a.y = static_cast<char*>(y) + (size_t)b0 * ldy * esz;
+    a.x = slice_rows(x, b0, ldx, esz);
+    a.y = slice_rows(y, b0, ldy, esz);
     if (x_f64)
       drop_launches<double>(a, nb, s);
     else
       drop_launches<float>(a, nb, s);
-  }
+  });
 }
 
 }  // namespace vfx

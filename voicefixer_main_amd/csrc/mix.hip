@@ -14,9 +14,8 @@
 //   6. scale      all of them * float(scale)
 //   7. noisy      noise_out + speech_out
 //
-// Passes over memory (each one grid over the batch: blockIdx.y = clip, blockIdx.x = chunk of kMixChunk samples of it):
-//   k_mix_peaks    reads every input                     -> p_x (atomicMax on the bit pattern of |x|: order-independent, a NaN lands
-//                                                            above every finite value, as np.max gives NaN)
+// Passes over memory (each one grid over the batch: blockIdx.y = clip, blockIdx.x = chunk of kClipChunk samples of it):
+//   k_mix_peaks    reads every input                     -> p_x (atomicMax on the bit pattern of |x|)
 //   k_mix_sums     forms 1, 2: reads speech, noise        -> per-chunk float64 sums of |speech * s1| and |noise / p_noise|
 //   k_mix_level    forms 1, 2: one wave per clip          -> the chunk sums added in index order, the level rule, float(ratio)
 //   k_mix_mixpeak  reads speech, noise                    -> max |noise2 + speech1|
@@ -25,10 +24,9 @@
 // division by a positive scalar), so steps 2-4 applied to p_x give them.  "max" over several signals is Python's max() over floats
 // in the host's argument order (a later value replaces the current one only when it compares greater), NaN behaviour included.
 //
-// A thread's samples are groups of 4 at ROW-RELATIVE indices c0 + 4 (tid + 256 k), k < kMixChunk / 1024: the float64 sums of a
-// chunk add the same samples in the same order whatever the row's address, so a clip's result is the same in any batch, at any row
-// stride.  A group is one 16-byte access when the row's base is 16-byte aligned and the group lies inside the row; the groups of a
-// misaligned row, and the tail group of a clip, go sample by sample (simulate pads the stride of its batches to a multiple of 4).
+// The sample groups of a thread and the peak commit are clip_batch.h's; the float64 sums of a chunk add the same samples in the same
+// order whatever the row's address (simulate pads the stride of its batches to a multiple of 4, which keeps every row on the fast path).
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 #pragma clang fp contract(off)
@@ -36,8 +34,8 @@
 namespace vfx {
 
 constexpr int kMixThreads = 256;
-constexpr int kMixGroups = kMixChunk / (4 * kMixThreads);  // groups of 4 samples per thread
-static_assert(kMixChunk == 4 * kMixThreads * kMixGroups, "a chunk is whole groups of every thread");
+constexpr int kMixGroups = kClipChunk / (4 * kMixThreads);  // groups of 4 samples per thread
+static_assert(kClipChunk == 4 * kMixThreads * kMixGroups, "a chunk is whole groups of every thread");
 enum { MIX_FRONT = 0, MIX_NOISE = 1, MIX_HQ = 2, MIX_AUG = 3, MIX_MIXTURE = 4 };  // rows of in / out / a clip's peaks
 
 struct MixLevel {
@@ -98,75 +96,43 @@ __device__ __forceinline__ MixScalars mix_scalars(const MixArgs& a, int b, bool 
   return s;
 }
 
-__device__ __forceinline__ bool mix_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// samples [j, j + 4) of a row of n samples, j a multiple of 4; zeros at and past n (the callers test j + e < n before they use one)
-__device__ __forceinline__ void mix_load4(const float* row, bool vec, int64_t j, int64_t n, float (&v)[4]) {
-  if (vec && j + 4 <= n) {
-    const float4 q = *reinterpret_cast<const float4*>(row + j);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = j + e < n ? row[j + e] : 0.f;
-  }
-}
-
-// ... and their store into a row of ld floats
-__device__ __forceinline__ void mix_store4(float* row, bool vec, int64_t j, int64_t ld, const float (&v)[4]) {
-  if (vec && j + 4 <= ld) {
-    *reinterpret_cast<float4*>(row + j) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (j + e < ld) row[j + e] = v[e];
-  }
-}
-
-__device__ __forceinline__ unsigned mix_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-
-// the wave's max in registers, then one atomic per wave
-__device__ __forceinline__ void mix_commit_peak(unsigned peak, unsigned* dst) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) peak = max(peak, (unsigned)__shfl_xor((int)peak, d));
-  if ((threadIdx.x & 63) == 0 && peak) atomicMax(dst, peak);
-}
-
 __global__ __launch_bounds__(kMixThreads) void k_mix_peaks(const MixArgs a) {
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kMixChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= n) return;
+  __shared__ unsigned wave_peak[4][kMixThreads / 64];  // a set per signal: no barrier between the commits
 #pragma unroll
   for (int sig = 0; sig < 4; ++sig) {
-    if (!a.in[sig]) continue;
+    if (!a.in[sig]) continue;  // (the same for every thread of the workgroup, as the return above)
     const float* row = a.in[sig] + (int64_t)b * a.ld;
-    const bool vec = mix_aligned(row);
+    const bool vec = clip_aligned(row);
     float v[kMixGroups][4];
 #pragma unroll
-    for (int k = 0; k < kMixGroups; ++k) mix_load4(row, vec, c0 + 4 * (threadIdx.x + kMixThreads * k), n, v[k]);
+    for (int k = 0; k < kMixGroups; ++k) clip_load(row, vec, c0 + 4 * (threadIdx.x + kMixThreads * k), n, v[k]);
     unsigned peak = 0;  // (a sample past n was loaded as +0: bit pattern 0)
 #pragma unroll
     for (int k = 0; k < kMixGroups; ++k)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) peak = max(peak, mix_abs_bits(v[k][e]));
-    mix_commit_peak(peak, a.peaks + b * kMixPeaks + sig);
+      for (int e = 0; e < 4; ++e) peak = max(peak, ClipType<float>::abs_bits(v[k][e]));
+    clip_commit_peak<kMixThreads>(peak, a.peaks + b * kMixPeaks + sig, wave_peak[sig]);
   }
 }
 
 __global__ __launch_bounds__(kMixThreads) void k_mix_sums(const MixArgs a) {
   __shared__ double wsum[kMixThreads / 64][2];
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kMixChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= n) return;
   const MixScalars sc = mix_scalars(a, b, false);
   const float* sp = a.in[a.form == 2 ? MIX_AUG : MIX_FRONT] + (int64_t)b * a.ld;
   const float* ns = a.in[MIX_NOISE] + (int64_t)b * a.ld;
-  const bool vsp = mix_aligned(sp), vns = mix_aligned(ns);
+  const bool vsp = clip_aligned(sp), vns = clip_aligned(ns);
   float x[kMixGroups][4], z[kMixGroups][4];
 #pragma unroll
   for (int k = 0; k < kMixGroups; ++k) {
     const int64_t j = c0 + 4 * (threadIdx.x + kMixThreads * k);
-    mix_load4(sp, vsp, j, n, x[k]);
-    mix_load4(ns, vns, j, n, z[k]);
+    clip_load(sp, vsp, j, n, x[k]);
+    clip_load(ns, vns, j, n, z[k]);
   }
   double s_sp = 0.0, s_ns = 0.0;  // the thread's samples in index order
 #pragma unroll
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(64) void k_mix_level(const MixArgs a) {
   __shared__ double tile[64][2];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int64_t n = a.len[b];
-  const int nch = (int)((n + kMixChunk - 1) / kMixChunk);
+  const int nch = (int)((n + kClipChunk - 1) / kClipChunk);
   const double* src = a.partial + (int64_t)b * a.nchunk * 2;
   double t_sp = 0.0, t_ns = 0.0;
   for (int c0 = 0; c0 < nch; c0 += 64) {
@@ -224,26 +190,27 @@ __global__ __launch_bounds__(64) void k_mix_level(const MixArgs a) {
 
 __global__ __launch_bounds__(kMixThreads) void k_mix_mixpeak(const MixArgs a) {
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kMixChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= n) return;
   const MixScalars sc = mix_scalars(a, b, true);
   const float* sp = a.in[a.form == 2 ? MIX_AUG : MIX_FRONT] + (int64_t)b * a.ld;
   const float* ns = a.in[MIX_NOISE] + (int64_t)b * a.ld;
-  const bool vsp = mix_aligned(sp), vns = mix_aligned(ns);
+  const bool vsp = clip_aligned(sp), vns = clip_aligned(ns);
   float x[kMixGroups][4], z[kMixGroups][4];
 #pragma unroll
   for (int k = 0; k < kMixGroups; ++k) {
     const int64_t j = c0 + 4 * (threadIdx.x + kMixThreads * k);
-    mix_load4(sp, vsp, j, n, x[k]);
-    mix_load4(ns, vns, j, n, z[k]);
+    clip_load(sp, vsp, j, n, x[k]);
+    clip_load(ns, vns, j, n, z[k]);
   }
   unsigned peak = 0;
 #pragma unroll
   for (int k = 0; k < kMixGroups; ++k)
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (c0 + 4 * (threadIdx.x + kMixThreads * k) + e < n) peak = max(peak, mix_abs_bits(sc.noise(z[k][e]) + sc.speech(x[k][e])));
-  mix_commit_peak(peak, a.peaks + b * kMixPeaks + MIX_MIXTURE);
+      if (c0 + 4 * (threadIdx.x + kMixThreads * k) + e < n) peak = max(peak, ClipType<float>::abs_bits(sc.noise(z[k][e]) + sc.speech(x[k][e])));
+  __shared__ unsigned wave_peak[kMixThreads / 64];
+  clip_commit_peak<kMixThreads>(peak, a.peaks + b * kMixPeaks + MIX_MIXTURE, wave_peak);
 }
 
 // float(1.0 / activelev(noise + speech, <the returned signals in the host's order>)): the mixture's peak from k_mix_mixpeak, the
@@ -270,7 +237,7 @@ __device__ __forceinline__ float mix_second_scale(const MixArgs& a, int b, const
 
 __global__ __launch_bounds__(kMixThreads) void k_mix_apply(const MixArgs a) {
   const int b = blockIdx.y;
-  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kMixChunk;
+  const int64_t n = a.len[b], c0 = (int64_t)blockIdx.x * kClipChunk;
   if (c0 >= a.ld) return;
   const MixScalars sc = mix_scalars(a, b, true);
   const float s2 = mix_second_scale(a, b, sc), scale = a.scale[b];
@@ -278,9 +245,9 @@ __global__ __launch_bounds__(kMixThreads) void k_mix_apply(const MixArgs a) {
   const int64_t row0 = (int64_t)b * a.ld;
   bool vin[4], vout[5];
 #pragma unroll
-  for (int sig = 0; sig < 4; ++sig) vin[sig] = a.in[sig] && mix_aligned(a.in[sig] + row0);
+  for (int sig = 0; sig < 4; ++sig) vin[sig] = a.in[sig] && clip_aligned(a.in[sig] + row0);
 #pragma unroll
-  for (int sig = 0; sig < 5; ++sig) vout[sig] = a.out[sig] && mix_aligned(a.out[sig] + row0);
+  for (int sig = 0; sig < 5; ++sig) vout[sig] = a.out[sig] && clip_aligned(a.out[sig] + row0);
 #pragma unroll
   for (int k = 0; k < kMixGroups; ++k) {
     const int64_t j = c0 + 4 * (threadIdx.x + kMixThreads * k);
@@ -296,7 +263,7 @@ __global__ __launch_bounds__(kMixThreads) void k_mix_apply(const MixArgs a) {
         const bool need = a.in[sig] && (a.out[sig] || (a.out[MIX_MIXTURE] && (sig == MIX_NOISE || sig == speech_sig)));
         if (!need) continue;
         float x[4];
-        mix_load4(a.in[sig] + row0, vin[sig], j, n, x);
+        clip_load(a.in[sig] + row0, vin[sig], j, n, x);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           if (j + e < n) y[sig][e] = ((sig == MIX_NOISE ? sc.noise(x[e]) : sc.speech(x[e])) * s2) * scale;
@@ -307,41 +274,37 @@ __global__ __launch_bounds__(kMixThreads) void k_mix_apply(const MixArgs a) {
     }
 #pragma unroll
     for (int sig = 0; sig < 5; ++sig)
-      if (a.out[sig]) mix_store4(a.out[sig] + row0, vout[sig], j, a.ld, y[sig]);
+      if (a.out[sig]) clip_store(a.out[sig] + row0, vout[sig], j, a.ld, y[sig]);
   }
 }
 
 size_t mix_workspace_bytes(int B, int64_t lmax) {
-  const size_t nb = (size_t)std::min(B, kMixMaxClips), nchunk = (size_t)((lmax + kMixChunk - 1) / kMixChunk);
+  const size_t nb = (size_t)std::min(B, kMixMaxClips), nchunk = (size_t)((lmax + kClipChunk - 1) / kClipChunk);
   return nb * (kMixPeaks * sizeof(unsigned) + sizeof(MixLevel) + nchunk * 2 * sizeof(double));
 }
 
 void launch_mix_noise(int form, int B, int64_t ld, const int64_t* lengths, const float* const in[4], const double* noise_weight,
                       const double* scale, float* const out[5], char* ws, hipStream_t s) {
-  int64_t lmax = 0;
-  for (int b = 0; b < B; ++b) lmax = std::max(lmax, lengths[b]);
+  const int64_t lmax = *std::max_element(lengths, lengths + B);
   const size_t nbmax = (size_t)std::min(B, kMixMaxClips);
   MixArgs a{};
   a.form = form;
   a.has_w = noise_weight != nullptr;
   a.ld = ld;
-  a.nchunk = (int)((lmax + kMixChunk - 1) / kMixChunk);
+  a.nchunk = (int)((lmax + kClipChunk - 1) / kClipChunk);
   a.partial = reinterpret_cast<double*>(ws);  // (the widest alignment first)
   a.level = reinterpret_cast<MixLevel*>(ws + nbmax * a.nchunk * 2 * sizeof(double));
   a.peaks = reinterpret_cast<unsigned*>(ws + nbmax * (a.nchunk * 2 * sizeof(double) + sizeof(MixLevel)));
-  for (int b0 = 0; b0 < B; b0 += kMixMaxClips) {  // the clips' lengths and scalars travel as kernel arguments, kMixMaxClips per launch
-    const int nb = std::min(B - b0, kMixMaxClips);
-    int64_t nmax = 0;
+  for_clip_slices<kMixMaxClips>(B, [&](int b0, int nb) {  // the scratch is reused: the launches are ordered on the stream
+    const int64_t nmax = narrow_clip_lengths(lengths, b0, nb, a.len);
     for (int i = 0; i < nb; ++i) {
-      a.len[i] = (int)lengths[b0 + i];
       a.w[i] = noise_weight ? (float)noise_weight[b0 + i] : 1.f;
       a.scale[i] = (float)scale[b0 + i];
-      nmax = std::max(nmax, lengths[b0 + i]);
     }
-    for (int sig = 0; sig < 4; ++sig) a.in[sig] = in[sig] ? in[sig] + (int64_t)b0 * ld : nullptr;
-    for (int sig = 0; sig < 5; ++sig) a.out[sig] = out[sig] ? out[sig] + (int64_t)b0 * ld : nullptr;
+    for (int sig = 0; sig < 4; ++sig) a.in[sig] = slice_rows(in[sig], b0, ld);
+    for (int sig = 0; sig < 5; ++sig) a.out[sig] = slice_rows(out[sig], b0, ld);
     VFX_HIP(hipMemsetAsync(a.peaks, 0, (size_t)nb * kMixPeaks * sizeof(unsigned), s));
-    const dim3 block(kMixThreads), grid((unsigned)((nmax + kMixChunk - 1) / kMixChunk), (unsigned)nb);
+    const dim3 block(kMixThreads), grid((unsigned)((nmax + kClipChunk - 1) / kClipChunk), (unsigned)nb);
     hipLaunchKernelGGL(k_mix_peaks, grid, block, 0, s, a);
     VFX_HIP(hipGetLastError());
     if (form != 0) {
@@ -352,10 +315,10 @@ void launch_mix_noise(int form, int B, int64_t ld, const int64_t* lengths, const
     }
     hipLaunchKernelGGL(k_mix_mixpeak, grid, block, 0, s, a);
     VFX_HIP(hipGetLastError());
-    const dim3 agrid((unsigned)((ld + kMixChunk - 1) / kMixChunk), (unsigned)nb);
+    const dim3 agrid((unsigned)((ld + kClipChunk - 1) / kClipChunk), (unsigned)nb);
     hipLaunchKernelGGL(k_mix_apply, agrid, block, 0, s, a);
     VFX_HIP(hipGetLastError());
-  }
+  });
 }
 
 }  // namespace vfx

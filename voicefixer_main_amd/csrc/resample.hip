@@ -10,6 +10,7 @@
 //
 // One lane per output, R outputs per lane 256 apart: a workgroup owns 256 R consecutive outputs of one clip, stages the taps and
 // the input span those outputs need in LDS once, then each lane walks its phase (the tap index steps down by `up` as k rises).
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 namespace vfx {
@@ -145,14 +146,11 @@ void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx,
   a.down = p.down;
   a.hl = p.hl;
   a.span_max = (int)(lds_floats - (2 * (int64_t)p.hl + 1 + 3) / 4 * 4);
-  for (int b0 = 0; b0 < B; b0 += kResampleMaxClips) {  // the clips' lengths travel as kernel arguments, kResampleMaxClips per launch
-    const int nbat = std::min(B - b0, kResampleMaxClips);
-    a.x = x + (int64_t)b0 * ldx;
-    a.y = y + (int64_t)b0 * ldy;
-    for (int i = 0; i < nbat; ++i) {
-      a.lens_in[i] = lens_in[b0 + i];
-      a.lens_out[i] = resample_out_len(lens_in[b0 + i], p);
-    }
+  for_clip_slices<kResampleMaxClips>(B, [&](int b0, int nbat) {
+    a.x = slice_rows(x, b0, ldx);
+    a.y = slice_rows(y, b0, ldy);
+    narrow_clip_lengths(lens_in, b0, nbat, a.lens_in);
+    for (int i = 0; i < nbat; ++i) a.lens_out[i] = resample_out_len(a.lens_in[i], p);
     const dim3 grid((unsigned)nb, (unsigned)nbat);
     if (p.R == 4)
       hipLaunchKernelGGL(k_resample_poly<4>, grid, dim3(256), (size_t)lds_floats * 4, s, a);
@@ -161,7 +159,7 @@ void launch_resample(const float* x, int B, int64_t ldx, int64_t x0, int64_t Lx,
     else
       hipLaunchKernelGGL(k_resample_poly<1>, grid, dim3(256), (size_t)lds_floats * 4, s, a);
     VFX_HIP(hipGetLastError());
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 // All N + M - 1 outputs of a clip are computed; the first N go to y, and every one of them -- rounded to float32 -- feeds the clip's
 // peak through an atomicMax on the bit pattern of |y| (order-independent; a NaN lands above every finite value).  k_reverb_scale then
 // does the reference's normalisation, (y / peak) * 0.98f where (double)peak > 0.99: NumPy's arithmetic on a float32 array.
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 namespace vfx {
@@ -171,19 +172,18 @@ void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* length
   a.ldy = ldy;
   ReverbScaleArgs sa{};
   sa.ldy = ldy;
-  for (int b0 = 0; b0 < B; b0 += kReverbMaxClips) {  // the clips' lengths travel as kernel arguments, kReverbMaxClips per launch
-    const int nb = std::min(B - b0, kReverbMaxClips);
-    a.x = x + (int64_t)b0 * ldx;
-    a.y = y + (int64_t)b0 * ldy;
+  for_clip_slices<kReverbMaxClips>(B, [&](int b0, int nb) {
+    a.x = slice_rows(x, b0, ldx);
+    a.y = slice_rows(y, b0, ldy);
     a.peaks = peaks ? reinterpret_cast<unsigned*>(peaks) + b0 : nullptr;
-    int64_t nfull = 0, nmax = 0;
+    const int64_t nmax = narrow_clip_lengths(lengths, b0, nb, a.len);
+    std::copy(a.len, a.len + nb, sa.len);
+    int64_t nfull = 0;
     for (int i = 0; i < nb; ++i) {
       const int r = rir_index ? rir_index[b0 + i] : (b0 + i) % R;
-      a.len[i] = sa.len[i] = (int)lengths[b0 + i];
       a.rir[i] = r;
       a.rir_len[i] = (int)rir_lengths[r];
       nfull = std::max(nfull, lengths[b0 + i] + rir_lengths[r] - 1);
-      nmax = std::max(nmax, lengths[b0 + i]);
     }
     const dim3 grid((unsigned)((nfull + kReverbTile - 1) / kReverbTile), (unsigned)nb);
     hipLaunchKernelGGL(k_reverb, grid, dim3(kReverbWaves * 64), 0, s, a);
@@ -195,7 +195,7 @@ void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* length
       hipLaunchKernelGGL(k_reverb_scale, sgrid, dim3(256), 0, s, sa);
       VFX_HIP(hipGetLastError());
     }
-  }
+  });
 }
 
 }  // namespace vfx

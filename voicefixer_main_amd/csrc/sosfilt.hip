@@ -18,6 +18,7 @@
 // writes the previous tile's outputs to global memory and fetches the next tile's inputs -- one coalesced row of 64 samples per
 // clip -- into the other LDS buffer; the waves meet at one barrier per tile.  The loop-carried chain per step is the four dependent
 // float64 operations of the z0 update, whatever the batch size: the pass is latency-bound, parallel over clips x sections only.
+#include "clip_batch.h"
 #include "vfx_internal.h"
 
 #pragma clang fp contract(off)
@@ -208,19 +209,19 @@ void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int6
   }
   const size_t lds = (size_t)2 * a.C * kSosRow * sizeof(double);  // at most 33 280 bytes
   const size_t elt = x_f64 ? sizeof(double) : sizeof(float);
-  for (int b0 = 0; b0 < B; b0 += kSosMaxClips) {  // the clips' lengths travel as kernel arguments, kSosMaxClips per launch
-    a.B = std::min(B - b0, kSosMaxClips);
-    a.x = static_cast<const char*>(x) + (size_t)b0 * ldx * elt;
-    a.f = f;  // the scratch is reused: the launches are ordered on the stream
-    a.y = y + (int64_t)b0 * ldy;
-    for (int i = 0; i < a.B; ++i) a.len[i] = (int)lengths[b0 + i];
+  a.f = f;  // the scratch is reused: the launches are ordered on the stream
+  for_clip_slices<kSosMaxClips>(B, [&](int b0, int nb) {
+    a.B = nb;
+    a.x = slice_rows(x, b0, ldx, elt);
+    a.y = slice_rows(y, b0, ldy);
+    narrow_clip_lengths(lengths, b0, nb, a.len);
     const dim3 grid((unsigned)((a.B + a.C - 1) / a.C));
     for (int bwd = 0; bwd < 2; ++bwd) {
       a.bwd = bwd;
       hipLaunchKernelGGL(k_sosfilt, grid, dim3(128), lds, s, a);
       VFX_HIP(hipGetLastError());
     }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -376,8 +377,7 @@ void launch_sosfiltfilt_bank(const void* x, int x_f64, int B, int64_t ldx, const
   a.ldy = ldy;
   a.x_f64 = x_f64;
   a.Smax = Smax;
-  for (int b0 = 0; b0 < B; b0 += kSosMaxClips) {
-    const int n = std::min(B - b0, kSosMaxClips);
+  for_clip_slices<kSosMaxClips>(B, [&](int b0, int n) {  // x and y stay whole: SosClip::row is the caller's row
     int order[kSosMaxClips];
     for (int i = 0; i < n; ++i) order[i] = b0 + i;
     std::stable_sort(order, order + n, [&](int p, int q) { return sections[filter_index[p]] < sections[filter_index[q]]; });
@@ -398,7 +398,7 @@ void launch_sosfiltfilt_bank(const void* x, int x_f64, int B, int64_t ldx, const
       hipLaunchKernelGGL(k_sosfilt_bank, dim3((unsigned)nblk), dim3(128), 0, s, a);
       VFX_HIP(hipGetLastError());
     }
-  }
+  });
 }
 
 }  // namespace vfx

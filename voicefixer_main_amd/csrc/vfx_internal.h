@@ -554,7 +554,7 @@ int64_t resample_out_len(int64_t n_in, const ResamplePair& p);  // ceil(n_in up 
 // end are zeros)
 void resample_window(int64_t n_in, const ResamplePair& p, int64_t o0, int64_t n, int64_t* k0, int64_t* k1);
 
-constexpr int kResampleMaxClips = 64;  // clips per launch: their lengths are kernel arguments
+constexpr int kResampleMaxClips = 64;  // clips per launch: their lengths are kernel arguments (the slices of clip_batch.h)
 struct ResampleArgs {
   const float* x;     // (clips, ldx): global input indices [x0, x0 + Lx) of each clip
   const float* taps;  // 2 hl + 1
@@ -586,7 +586,8 @@ struct ResampleEachClip {    // one clip of the call, for k_resample_each
 // up / down reduced by their gcd, hl = 10 max(up, down); false for up or down <= 0 or max(up, down) > kResampleEachMaxRate after it
 bool resample_each_reduce(int64_t up, int64_t down, ResamplePair* out);
 // x, y (x's dtype), taps (x's dtype): device; lens_in, pair_index (B), pairs (F, reduced), taps_at (F): HOST.  The caller has checked
-// 1 <= B <= kResampleEachMaxClips, 1 <= F <= kResampleEachMaxDesigns, the indices, 0 <= lens_in[b] <= ldx and 0 < n_out <= ldy.
+// 1 <= B <= kResampleEachMaxClips, 1 <= F <= kResampleEachMaxDesigns, the indices, 0 < n_out <= ldy and, with check_clip_lengths
+// (api.cpp), 0 <= lens_in[b] <= ldx.
 // y[b, n] for n < n_out: resample_poly's output n of clip b, zero at or past the clip's output length.
 void launch_resample_each(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lens_in, const int* pair_index,
                           const ResamplePair* pairs, const void* taps, const int64_t* taps_at, int F, void* y, int64_t ldy, int64_t n_out,
@@ -600,7 +601,8 @@ constexpr int kSosMaxSections = 16;
 constexpr int kSosMaxClips = 128;     // clips per launch: their lengths are kernel arguments
 int sosfilt_clips_per_wave(int S);    // 4 rows of min(16 / S, 8) clips
 // x (float32 or float64), f, y: device; lengths, sos (S, 6), zi (S, 2): HOST.  f (min(B, kSosMaxClips), ldf) receives the forward pass
-// over the extended clips, ldf >= max length + 2 padlen.  The caller has checked padlen < lengths[b] <= min(ldx, ldy) and 1 <= S <= 16.
+// over the extended clips, ldf >= max length + 2 padlen.  The caller has checked 1 <= S <= 16 and, with check_clip_lengths (api.cpp),
+// padlen < lengths[b] <= min(ldx, ldy).
 // Both passes of every clip; y[b, lengths[b] .. ldy) = 0.
 void launch_sosfiltfilt(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const double* sos, int S, const double* zi,
                         int padlen, double* f, int64_t ldf, double* y, int64_t ldy, hipStream_t s);
@@ -611,8 +613,9 @@ constexpr int kSosMaxBlocks = kSosMaxClips / 4 + kSosMaxSections;  // a block ta
 // sos (F, Smax, 6), zi (F, Smax, 2) HOST -> bank (F, Smax, kSosBankRow) HOST, what the kernel reads from device memory
 void sosfilt_pack_bank(const double* sos, const double* zi, int F, int Smax, double* bank);
 // x, f, y, bank (sosfilt_pack_bank's, uploaded): device; lengths, filter_index (B), sections, padlens (F): HOST.  f as above with
-// ldf >= max(length + 2 padlen of the clip's design).  The caller has checked the indices, 1 <= sections[.] <= Smax <= 16 and
-// padlens[filter_index[b]] < lengths[b] <= min(ldx, ldy).  One launch pair per kSosMaxClips clips, whatever their section counts.
+// ldf >= max(length + 2 padlen of the clip's design).  The caller has checked the indices, 1 <= sections[.] <= Smax <= 16,
+// lengths[b] <= min(ldx, ldy) with check_clip_lengths (api.cpp) and padlens[filter_index[b]] < lengths[b].  One launch pair per
+// kSosMaxClips clips, whatever their section counts.
 void launch_sosfiltfilt_bank(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* filter_index,
                              const double* bank, int Smax, const int* sections, const int* padlens, double* f, int64_t ldf, double* y,
                              int64_t ldy, hipStream_t s);
@@ -625,9 +628,9 @@ constexpr int kReverbTapBlock = 1024;   // taps per f32 fma chain; the block sum
 constexpr int kReverbMaxTaps = 1 << 20; // longest RIR the entry point takes
 constexpr int kReverbMaxClips = 128;    // clips per launch: their lengths are kernel arguments
 // x, rirs, y, peaks: device; lengths (B), rir_lengths (R), rir_index (B, or NULL = b % R): HOST.  The caller has checked
-// 1 <= lengths[b] <= min(ldx, ldy), 1 <= rir_lengths[r] <= min(ldr, kReverbMaxTaps) and the indices.  Row b of y receives the first
-// lengths[b] samples of clip b * rir, zeros up to ldy; peaks[b] (NULL: not wanted, normalize = 0 only) the largest |sample| of the whole
-// convolution; normalize: rows whose peak exceeds 0.99 are scaled to a peak of 0.98.
+// 1 <= lengths[b] <= min(ldx, ldy) with check_clip_lengths (api.cpp), 1 <= rir_lengths[r] <= min(ldr, kReverbMaxTaps) and the indices.
+// Row b of y receives the first lengths[b] samples of clip b * rir, zeros up to ldy; peaks[b] (NULL: not wanted, normalize = 0 only)
+// the largest |sample| of the whole convolution; normalize: rows whose peak exceeds 0.99 are scaled to a peak of 0.98.
 void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* lengths, const float* rirs, int64_t ldr,
                        const int64_t* rir_lengths, const int* rir_index, int R, int normalize, float* y, int64_t ldy, float* peaks,
                        hipStream_t s);
@@ -635,30 +638,29 @@ void launch_reverb_rir(const float* x, int B, int64_t ldx, const int64_t* length
 // ---------------------------------------------------------------------------------------------
 // noise mixing (mix.hip): add_noise_and_scale and its with_HQ / with_HQ_with_Aug forms
 // ---------------------------------------------------------------------------------------------
-constexpr int kMixChunk = 4096;     // samples of a clip per workgroup; the float64 level sums are per chunk, combined in index order
 constexpr int kMixMaxClips = 128;   // clips per launch: their lengths, weights and scales are kernel arguments
 constexpr int kMixPeaks = 8;        // peak slots per clip: front, noise, hq, aug, the mixture (+ padding)
 size_t mix_workspace_bytes(int B, int64_t lmax);  // of `ws` below, for B clips of at most lmax samples
 // in (front, noise, hq, aug), out (front, noise, hq, aug, noisy): device (B, ld) or NULL; lengths, noise_weight (or NULL), scale: HOST (B).
-// The caller has checked the form's pointers and 1 <= lengths[b] <= ld.  Rows of every given output are zero from lengths[b] up to ld.
+// The caller has checked the form's pointers and, with check_clip_lengths (api.cpp), 1 <= lengths[b] <= ld.  Rows of every given output
+// are zero from lengths[b] up to ld.
 void launch_mix_noise(int form, int B, int64_t ld, const int64_t* lengths, const float* const in[4], const double* noise_weight,
                       const double* scale, float* const out[5], char* ws, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // array effects (effects.hip): MagicalEffects.quantification and time_dropout
 // ---------------------------------------------------------------------------------------------
-constexpr int kFxChunk = 4096;     // samples of a clip per workgroup of the element-wise passes
 constexpr int kFxMaxClips = 128;   // clips per launch: their lengths, bins and indices are kernel arguments
 constexpr int kFxMaxBins = 16;     // level = 2 ** bins <= 65536
 constexpr int kFxSmoothHalf = 50, kFxSmoothStep = 4;                                       // smooth()'s smooth_samples and interval
 constexpr int kFxSmoothKnots = 2 * kFxSmoothHalf / kFxSmoothStep;                          // 25 knots: patch[0], patch[4], .., patch[96]
 constexpr int kFxSmoothRows = (kFxSmoothKnots - 1) * kFxSmoothStep;                        // 96 samples written: patch[0 .. 95]
-// x, y, peaks (or NULL), bits (B slots): device; lengths, bins: HOST (B).  The caller has checked 1 <= lengths[b] <= min(ldx, ldy) and
-// 0 <= bins[b] <= kFxMaxBins.  y[b, lengths[b] .. ldy) = 0.
+// x, y, peaks (or NULL), bits (B slots): device; lengths, bins: HOST (B).  The caller has checked 1 <= lengths[b] <= min(ldx, ldy) with
+// check_clip_lengths (api.cpp) and 0 <= bins[b] <= kFxMaxBins.  y[b, lengths[b] .. ldy) = 0.
 void launch_quantize(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int* bins, double* y, int64_t ldy,
                      void* peaks, unsigned long long* bits, hipStream_t s);
 // x, y (x's dtype), smooth (kFxSmoothRows, kFxSmoothKnots): device; lengths, starts, ends: HOST (B).  The caller has checked the lengths
-// as above and 0 <= starts[b] <= ends[b].  y[b, lengths[b] .. ldy) = 0.
+// with check_clip_lengths (api.cpp), as above, and 0 <= starts[b] <= ends[b].  y[b, lengths[b] .. ldy) = 0.
 void launch_time_dropout(const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, const int64_t* starts, const int64_t* ends,
                          const double* smooth, void* y, int64_t ldy, hipStream_t s);
 

@@ -51,6 +51,38 @@ def _clip_rows(x, lengths, name=None, what="lengths"):
     return x, squeeze, B, L, lengths
 
 
+def _float_rows(x, device, name, other):
+    """x (B, L) or (L,), a tensor or anything NumPy takes -> a contiguous float32 or float64 tensor on `device`.  `other` is what
+    any other dtype does: a dtype -- x is converted to it --, or an exception class -- it is raised."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.asarray(x))
+    if x.dtype not in (torch.float32, torch.float64):
+        if not isinstance(other, torch.dtype):
+            raise other("%s: x must be float32 or float64, got %s" % (name, x.dtype))
+        x = x.to(other)
+    if x.dim() not in (1, 2):
+        raise ValueError("%s: x must be (B, L) or (L,), got %s" % (name, tuple(x.shape)))
+    return x.to(device).contiguous()
+
+
+def _per_clip(v, B, cast, name=None, what=None):
+    """One value for every clip, or one per clip -> a list of cast(value).  With `name`, a list of another size than B raises."""
+    v = [cast(v)] * B if np.ndim(v) == 0 else [cast(u) for u in v]
+    if name is not None and len(v) != B:
+        raise ValueError("%s: %d %s for %d clips" % (name, len(v), what, B))
+    return v
+
+
+def _result_rows(_y, shape, dtype, device, name):
+    """The result tensor of a method whose kernels write every element of it (zeros at and past a clip's length): a new one, or the
+    caller's `_y` when it is what a new one would be."""
+    if _y is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if _y.shape != shape or _y.dtype != dtype or not _y.is_contiguous() or _y.device != device:
+        raise ValueError("%s: _y must be a contiguous %s %s tensor on %s" % (name, tuple(shape), dtype, device))
+    return _y
+
+
 class Engine:
     """One libvfx handle on one GPU (not thread-safe, like the reference's module-level model)."""
 
@@ -244,8 +276,8 @@ class Engine:
         if x.dim() not in (1, 2):
             raise ValueError("stft_lowpass: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
         x, squeeze, B, L, lengths = _clip_rows(x, lengths, "stft_lowpass")
-        cut_bins = [int(cut_bins)] * B if np.ndim(cut_bins) == 0 else [int(v) for v in cut_bins]
-        if B == 0 or len(cut_bins) != B:
+        cut_bins = _per_clip(cut_bins, B, int, "stft_lowpass", "cut-off bins")
+        if B == 0:
             raise ValueError("stft_lowpass: %d cut-off bins for %d clips" % (len(cut_bins), B))
         y = torch.empty((B, L), device=self.device, dtype=torch.float32)
         _lib.check(self.lib.vfx_stft_lowpass(self.h, _ptr(x), B, L, (ctypes.c_int * B)(*lengths), (ctypes.c_int * B)(*cut_bins), _ptr(y),
@@ -494,25 +526,13 @@ class Engine:
         out_lengths[b] = ceil(lengths[b] up_b / down_b).  The distinct reduced pairs of a call are its designs; B > 128 is cut into
         calls of 128.  The unscaled filters come from SciPy's firwin on the host and are cached on the device per (M, dtype), least
         recently used evicted past RESAMPLE_EACH_CACHE_BYTES = 256 MiB (`_resample_each_taps`).  1-D x gives a 1-D y and an int."""
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x))
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError("resample_each: clips must be float32 or float64, got %s" % x.dtype)
-        if x.dim() not in (1, 2):
-            raise ValueError("resample_each: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
-        x, squeeze, B, L, lengths = _clip_rows(x.to(self.device).contiguous(), lengths, "resample_each")
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, "resample_each", TypeError), lengths, "resample_each")
         if B and (min(lengths) < 0 or max(lengths) > L):
             raise ValueError("resample_each: clips of %d .. %d samples in rows of %d" % (min(lengths), max(lengths), L))
-
-        def per_clip(v, name):
-            v = [int(v)] * B if np.ndim(v) == 0 else [int(r) for r in v]
-            if len(v) != B:
-                raise ValueError("resample_each: %d %s for %d clips" % (len(v), name, B))
-            if any(r <= 0 for r in v):
-                raise ValueError("resample_each: %s must be positive" % name)
-            return v
-
-        sr_in, sr_out = per_clip(sr_in, "sr_in"), per_clip(sr_out, "sr_out")
+        sr_in, sr_out = _per_clip(sr_in, B, int, "resample_each", "sr_in"), _per_clip(sr_out, B, int, "resample_each", "sr_out")
+        for rates, what in ((sr_in, "sr_in"), (sr_out, "sr_out")):
+            if any(r <= 0 for r in rates):
+                raise ValueError("resample_each: %s must be positive" % what)
         pairs = [self.resample_ratio(i, o) for i, o in zip(sr_in, sr_out)]
         for b, (up, down) in enumerate(pairs):
             if max(up, down) > 65536:
@@ -522,11 +542,7 @@ class Engine:
         n_out = max(out_lengths, default=0) if n_out is None else int(n_out)
         if n_out < 0:
             raise ValueError("resample_each: n_out = %d" % n_out)
-        if _y is None:      # (the kernel writes every element of y: zeros at or past a clip's output length)
-            _y = torch.empty((B, n_out), device=self.device, dtype=x.dtype)
-        elif _y.shape != (B, n_out) or _y.dtype != x.dtype or not _y.is_contiguous() or _y.device != x.device:
-            raise ValueError("resample_each: _y must be a contiguous (%d, %d) %s tensor on %s" % (B, n_out, x.dtype, x.device))
-        y = _y
+        y = _result_rows(_y, (B, n_out), x.dtype, x.device, "resample_each")
         if L == 0:
             y.zero_()
         for b0 in range(0, B if n_out and L else 0, self.MAX_RESAMPLE_EACH_CLIPS):
@@ -572,14 +588,7 @@ class Engine:
         a row is zero past it.  ValueError, with SciPy's wording, for a clip that is not longer than padlen and for a malformed sos."""
         sos = self._check_sos(sos)
         padlen = self.sosfiltfilt_padlen(sos)
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x))
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float64)
-        x = x.to(self.device).contiguous()
-        if x.dim() not in (1, 2):
-            raise ValueError("sosfiltfilt: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
-        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "sosfiltfilt")
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, "sosfiltfilt", torch.float64), lengths, "sosfiltfilt")
         if B == 0 or min(lengths) <= padlen:
             raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
         if max(lengths) > L:
@@ -603,14 +612,8 @@ class Engine:
         pair of launches takes the whole batch whatever its section counts.  ValueError, with SciPy's wording, for a malformed
         design and for a clip that is not longer than ITS design's padlen (the message carries that padlen)."""
         bank = [self._check_sos(sos) for sos in bank]
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x))
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float64)
-        x = x.to(self.device).contiguous()
-        if x.dim() not in (1, 2):
-            raise ValueError("sosfiltfilt_bank: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
-        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "sosfiltfilt_bank")
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, "sosfiltfilt_bank", torch.float64), lengths,
+                                               "sosfiltfilt_bank")
         F = len(bank)
         if B == 0 or not 1 <= F <= self.MAX_SOS_DESIGNS:
             raise ValueError("sosfiltfilt_bank: %d clips and %d designs (at most %d)" % (B, F, self.MAX_SOS_DESIGNS))
@@ -699,13 +702,8 @@ class Engine:
             sig = {k: v[None] for k, v in sig.items()}
         if B == 0:
             raise ValueError("mix_noise: no clips")
-
-        def per_clip(v, default):
-            v = default if v is None else v
-            return [float(v)] * B if np.ndim(v) == 0 else [float(u) for u in v]
-
-        scale = per_clip(scale, 1.0)
-        weight = None if noise_weight is None else per_clip(noise_weight, None)
+        scale = _per_clip(1.0 if scale is None else scale, B, float)
+        weight = None if noise_weight is None else _per_clip(noise_weight, B, float)
         if len(lengths) != B or len(scale) != B or (weight is not None and len(weight) != B):
             raise ValueError("mix_noise: %d lengths, %d scales and %s weights for %d clips"
                              % (len(lengths), len(scale), "no" if weight is None else len(weight), B))
@@ -723,43 +721,16 @@ class Engine:
     # ------------------------------------------------------------------ array effects (MagicalEffects.quantification, time_dropout)
     MAX_QUANT_BINS = 16
 
-    def _fx_rows(self, x, lengths, name):
-        """x (B, L) or (L,), float32 or float64 -> (x on the device as (B, L), squeeze, B, L, lengths)"""
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x))
-        if x.dtype not in (torch.float32, torch.float64):
-            raise ValueError("%s: x must be float32 or float64, got %s" % (name, x.dtype))
-        if x.dim() not in (1, 2):
-            raise ValueError("%s: x must be (B, L) or (L,), got %s" % (name, tuple(x.shape)))
-        x, squeeze, B, L, lengths = _clip_rows(x.to(self.device).contiguous(), lengths, name)
-        if B == 0:
-            raise ValueError("%s: no clips" % name)
-        return x, squeeze, B, L, lengths
-
-    @staticmethod
-    def _fx_per_clip(v, B, name, what):
-        v = [int(v)] * B if np.ndim(v) == 0 else [int(u) for u in v]
-        if len(v) != B:
-            raise ValueError("%s: %d %s for %d clips" % (name, len(v), what, B))
-        return v
-
-    @staticmethod
-    def _fx_out(_y, B, L, dtype, device, name):
-        """the result tensor: every element is written, zeros at and past a clip's length"""
-        if _y is None:
-            return torch.empty((B, L), device=device, dtype=dtype)
-        if _y.shape != (B, L) or _y.dtype != dtype or not _y.is_contiguous() or _y.device != device:
-            raise ValueError("%s: _y must be a contiguous (%d, %d) %s tensor on %s" % (name, B, L, dtype, device))
-        return _y
-
     def quantize(self, x, bins, lengths=None, _y=None):
         """MagicalEffects.quantification of every clip on the device: x (B, L) or (L,), float32 or float64; bins one int for all or
         one per clip, each in 0..16; clip b = the first lengths[b] samples (default L) of row b, what the row holds past them is not
         read.  -> (y, peaks): y float64 shaped like x, zero past each length, bit for bit simulate.quantification; peaks (B,) in
         x's dtype (0-D for a 1-D x), max |x| of each clip.  A clip's result does not depend on the batch."""
-        x, squeeze, B, L, lengths = self._fx_rows(x, lengths, "quantize")
-        bins = self._fx_per_clip(bins, B, "quantize", "bins")
-        y = self._fx_out(_y, B, L, torch.float64, x.device, "quantize")
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, "quantize", ValueError), lengths, "quantize")
+        if B == 0:
+            raise ValueError("quantize: no clips")
+        bins = _per_clip(bins, B, int, "quantize", "bins")
+        y = _result_rows(_y, (B, L), torch.float64, x.device, "quantize")
         peaks = torch.empty((B,), device=x.device, dtype=x.dtype)
         _lib.check(self.lib.vfx_quantize(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, (ctypes.c_int64 * B)(*lengths),
                                          (ctypes.c_int * B)(*bins), _ptr(y), L, _ptr(peaks), self._stream()), "vfx_quantize")
@@ -773,10 +744,11 @@ class Engine:
         50 samples to either end of the clip.  Outside the patches bit for bit the host function; inside, the 25-term float64 sum
         of simulate.smooth_matrix() rounded once."""
         from .simulate import smooth_matrix
-        x, squeeze, B, L, lengths = self._fx_rows(x, lengths, "time_dropout")
-        starts = self._fx_per_clip(starts, B, "time_dropout", "starts")
-        ends = self._fx_per_clip(ends, B, "time_dropout", "ends")
-        y = self._fx_out(_y, B, L, x.dtype, x.device, "time_dropout")
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, "time_dropout", ValueError), lengths, "time_dropout")
+        if B == 0:
+            raise ValueError("time_dropout: no clips")
+        starts, ends = _per_clip(starts, B, int, "time_dropout", "starts"), _per_clip(ends, B, int, "time_dropout", "ends")
+        y = _result_rows(_y, (B, L), x.dtype, x.device, "time_dropout")
         i64 = ctypes.c_int64 * B
         _lib.check(self.lib.vfx_time_dropout(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, i64(*lengths), i64(*starts), i64(*ends),
                                              smooth_matrix().ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _ptr(y), L,
