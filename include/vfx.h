@@ -415,6 +415,30 @@ int vfx_time_dropout(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx
                      const int64_t* ends, const double* smooth, void* y, int64_t ldy, void* stream);
 
 /*
+ * The fully specified part of MagicalEffects' sox chain (dataloaders/augmentation/magical_effects.py:41-64, 131-152) on a padded batch
+ * of float32 clips, a program per clip: the biquads low_pass, high_pass, bass and treble, clip and reverse.  Restated from published
+ * definitions and not pinned against sox; simulate.chain_effects is the host form a clip's result equals bit for bit.
+ *   x (B, ldx) device float32, clip b = the first lengths[b] samples of row b (HOST int64[B], each >= 1);
+ *   ops (B, K) HOST ints, 1 <= K <= 8: the steps of clip b in order, VFX_CHAIN_END ends a program short of K;
+ *   coef (B, K, 5) HOST doubles: b0 b1 b2 a1 a2 (a0 = 1) of a VFX_CHAIN_BIQUAD step, the factor in the first slot of a VFX_CHAIN_CLIP step;
+ *   y (B, ldy) device float32, not overlapping x: row b receives lengths[b] samples and zeros from there up to ldy.
+ * A run is a maximal stretch of biquads and reverses: entering it the clip is widened to float64 and limited to [-1, 1 - 2^-31]; a
+ * biquad is x_c = b0 x_n + z0, z0 = (b1 x_n - a1 x_c) + z1, z1 = b2 x_n - a2 x_c from a zero state -- every product and sum rounded on
+ * its own --, its output limited to that range again while the state keeps the unlimited value; a reverse flips the clip; the run's
+ * result is rounded once to float32.  A clip step clamps the float32 clip to [min * (float)factor, max * (float)factor], float32
+ * products of the minimum and maximum of the clip as it stands.  sox's rounding to multiples of 2^-31 is not modelled.
+ * Every clip has its own program; a run of up to four biquads is one launch whatever the programs of the batch, and a clip's result
+ * depends on the clip alone: not on the batch, the row stride, the alignment or its neighbours' programs.  A sample that is not
+ * finite changes no other clip; what its own clip becomes is not specified (the limit and the clamp send a NaN to their lower
+ * bound, where the host form keeps it).  Intermediate clips live in a scratch buffer of the handle, grown on demand, and the programs are uploaded on `stream`, so
+ * a call is no subject for hipGraph capture.  Fails, launching nothing and leaving y as it is, for B outside 1..1024, an empty clip,
+ * a length above ldx or ldy, K outside 1..8, an unknown op, more than four biquads in one run, or a NULL argument.
+ */
+enum { VFX_CHAIN_END = 0, VFX_CHAIN_BIQUAD = 1, VFX_CHAIN_CLIP = 2, VFX_CHAIN_REVERSE = 3 };
+int vfx_effect_chain(vfx_handle* h, const float* x, int B, int64_t ldx, const int64_t* lengths, const int* ops, const double* coef, int K,
+                     float* y, int64_t ldy, void* stream);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

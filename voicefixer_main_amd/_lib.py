@@ -73,6 +73,8 @@ SIGNATURES = {
                              c_void_p]),
     "vfx_time_dropout": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                  POINTER(ctypes.c_double), c_void_p, c_int64, c_void_p]),
+    "vfx_effect_chain": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_int), POINTER(ctypes.c_double), c_int,
+                                 c_void_p, c_int64, c_void_p]),
     "vfx_spectral_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_audio_metrics_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),

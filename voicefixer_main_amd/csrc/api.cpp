@@ -693,6 +693,37 @@ int vfx_time_dropout(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// effect chain (the biquads, clip and reverse of MagicalEffects' sox chain on the device: chain.hip)
+// ---------------------------------------------------------------------------------------------
+int vfx_effect_chain(vfx_handle* h, const float* x, int B, int64_t ldx, const int64_t* lengths, const int* ops, const double* coef, int K,
+                     float* y, int64_t ldy, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && ops && coef && y, "vfx_effect_chain: bad argument");
+  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "vfx_effect_chain: %d clips (need 1 <= B <= %d)", B, kMaxVarlenClips);
+  VFX_CHECK(K >= 1 && K <= kChainMaxOps, "vfx_effect_chain: programs of %d steps (need 1 <= K <= %d)", K, kChainMaxOps);
+  const int64_t lmax = check_clip_lengths("vfx_effect_chain", B, lengths, 1, nullptr, ldx, &ldy, 0x7fffffff - 2 * kClipChunk);
+  std::vector<ChainPass> passes;
+  std::vector<int> first;
+  chain_plan(B, lengths, ops, coef, K, passes, first);
+  bool uses[2] = {false, false};  // the scratch rows the passes name
+  for (const ChainPass& p : passes)
+    for (int i = 0; i < 2; ++i) uses[i] |= p.dst == CHAIN_BUF0 + i;
+  constexpr size_t kStats = (size_t)kChainMaxClips * kChainMaxPasses * 2 * sizeof(unsigned);
+  static_assert(kStats % 16 == 0, "the scratch rows behind the statistics stay 16-byte aligned");
+  const int64_t lds = (lmax + 3) / 4 * 4;
+  const size_t buf_bytes = (size_t)std::min(B, kChainMaxClips) * lds * sizeof(double);
+  char* const ws = h->chain_ws.ensure(h, kStats + ((size_t)uses[0] + uses[1]) * buf_bytes, 0);
+  double* const buf0 = uses[0] ? reinterpret_cast<double*>(ws + kStats) : nullptr;
+  double* const buf1 = uses[1] ? reinterpret_cast<double*>(ws + kStats + (uses[0] ? buf_bytes : 0)) : nullptr;
+  const size_t tab_bytes = passes.size() * sizeof(ChainPass);
+  memcpy(h->chain_tab.stage(h, tab_bytes), passes.data(), tab_bytes);
+  const ChainPass* const tab = reinterpret_cast<const ChainPass*>(h->chain_tab.upload(tab_bytes, static_cast<hipStream_t>(stream)));
+  launch_effect_chain(x, ldx, B, passes, first, tab, buf0, buf1, lds, reinterpret_cast<unsigned*>(ws), y, ldy,
+                      static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

@@ -113,6 +113,15 @@ __device__ __forceinline__ void clip_store(T* row, bool vec, int64_t j, int64_t 
   }
 }
 
+// the value one lane below within the 16-lane row (row_shr:1); lane 0 of a row gets 0.  What hands a sample from one section of a
+// skewed cascade to the next (sosfilt.hip, chain.hip).
+__device__ inline double row_shr1(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, 0x111, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
 // atomicMax(dst, the workgroup's largest `peak`) -- abs_bits patterns: order-independent, a NaN lands above every finite value, as
 // np.max gives NaN.  The wave's max in registers, the workgroup's through LDS, then ONE atomic per workgroup, none for a zero: the
 // atomics of a clip all land on one address (and those of 16 clips on one cache line), where they take their turns.  Every thread

@@ -38,14 +38,6 @@ struct SosArgs {
   int len[kSosMaxClips];
 };
 
-// the value one lane below within the 16-lane row (row_shr:1); lane 0 of a row gets 0
-__device__ inline double row_shr1(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x111, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-
 // sample n of the odd extension of x[0 .. len), 0 <= n < len + 2 padlen, len > padlen: computed in T, then widened
 template <typename T>
 __device__ inline double ext_at(const T* x, int64_t len, int padlen, int64_t n) {

@@ -665,6 +665,36 @@ void launch_time_dropout(const void* x, int x_f64, int B, int64_t ldx, const int
                          const double* smooth, void* y, int64_t ldy, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// effect chain (chain.hip): the biquads, clip and reverse of MagicalEffects' sox chain, a program per clip
+// ---------------------------------------------------------------------------------------------
+constexpr int kChainMaxOps = 8;                    // steps of one clip's program
+constexpr int kChainMaxStages = 4;                 // biquads of one launch of the cascade = of one sox run
+constexpr int kChainMaxClips = 128;                // clips per set of launches: their passes are kernel arguments
+constexpr int kChainMaxPasses = kChainMaxOps + 1;  // passes over one clip (a program of clips alone: the reduction, then one per clip)
+enum ChainEnd : uint8_t { CHAIN_NONE = 0, CHAIN_BUF0 = 1, CHAIN_BUF1 = 2, CHAIN_CALLER = 3 };  // where a pass reads (x) or writes (y)
+// One pass over one clip, in the order the kernels apply it: read at i, or at len - 1 - i (rev); clamp to the float32 bounds
+// (min, max of what pass stat_in stored) * factor (clamp); widen and limit to sox's range (limit); nbq biquads, each output limited;
+// round to float32 (round32; what goes to y always is); store, and leave the minimum and maximum of what was stored (stats).
+struct ChainPass {
+  double coef[kChainMaxStages][5];  // b0 b1 b2 a1 a2
+  float factor;
+  int row, slot, len;               // row of x and y; the clip's place in its slice: its row of the scratch and of the statistics
+  int stat_in, stat_out;            // slot * kChainMaxPasses + the pass's number
+  uint8_t nbq, rev, clamp, limit, round32, stats, src, dst;
+};
+// lengths, ops (B, K), coef (B, K, 5): HOST.  Cuts every program into passes: first[b] .. first[b + 1] of `passes` are clip b's.
+// Throws for an unknown op and for more than kChainMaxStages biquads in one run.
+void chain_plan(int B, const int64_t* lengths, const int* ops, const double* coef, int K, std::vector<ChainPass>& passes,
+                std::vector<int>& first);
+// x, y, tab (the uploaded passes), buf0, buf1 (min(B, kChainMaxClips), lds) doubles or NULL where no pass names them, stats
+// (kChainMaxClips * kChainMaxPasses * 2): device.  The caller has checked 1 <= lengths[b] <= min(ldx, ldy) with check_clip_lengths
+// (api.cpp).  Per slice of kChainMaxClips clips: round r runs pass r of every clip that has one, the cascades in one grid, the
+// element-wise passes in another.  y[b, lengths[b] .. ldy) = 0.
+void launch_effect_chain(const float* x, int64_t ldx, int B, const std::vector<ChainPass>& passes, const std::vector<int>& first,
+                         const ChainPass* tab, double* buf0, double* buf1, int64_t lds, unsigned* stats, float* y, int64_t ldy,
+                         hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // handle-side data structures
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {
@@ -931,6 +961,8 @@ struct vfx_handle {
   vfx::GrowBuffer fx_ws;    // vfx_quantize's per-clip peaks (bit patterns)
   vfx::StagedUpload fx_smooth;          // vfx_time_dropout's smoothing matrix on the device ...
   std::vector<double> fx_smooth_seen;   // ... and what it holds: uploaded again only when the caller's matrix differs
+  vfx::GrowBuffer chain_ws;      // vfx_effect_chain's intermediate clips between passes (float64) and their minima and maxima
+  vfx::StagedUpload chain_tab;   // vfx_effect_chain's passes (ChainPass)
   vfx::GrowBuffer rs_taps;  // vfx_resample_each's scaled taps of the designs of a call (at most 11 MB per design)
   vfx::StagedUpload rs_table;  // vfx_resample_each's design and clip tables
   bool rs_natural_taps = false;  // debug switch (vfx_debug_resample_each_layout): the scaled taps in natural order, not phase-major

@@ -755,6 +755,62 @@ class Engine:
                                              self._stream()), "vfx_time_dropout")
         return y[0] if squeeze else y
 
+    # ------------------------------------------------------------------ effect chain (the biquads, clip and reverse of the sox chain)
+    MAX_CHAIN_OPS = 8
+    MAX_CHAIN_STAGES = 4
+    _CHAIN_OPS = {"biquad": 1, "clip": 2, "reverse": 3}
+
+    @classmethod
+    def effect_chain_supported(cls, program):
+        """Whether `effect_chain` takes this program: known steps, at most 8 of them, at most 4 biquads between two clip steps."""
+        if len(program) > cls.MAX_CHAIN_OPS or any(step[0] not in cls._CHAIN_OPS for step in program):
+            return False
+        run = 0
+        for step in program:
+            run = 0 if step[0] == "clip" else run + (step[0] == "biquad")
+            if run > cls.MAX_CHAIN_STAGES:
+                return False
+        return True
+
+    def effect_chain(self, x, programs, lengths=None):
+        """The biquads, clip and reverse of MagicalEffects' sox chain on the device, a program per clip: x (B, L) or (L,), made
+        float32; programs: one program for all, or one per clip, a program being a sequence of steps ("biquad", (b0, b1, b2, a1, a2))
+        -- simulate.biquad_design's --, ("clip", factor) and ("reverse",), at most 8 of them with at most 4 biquads between two clip
+        steps; clip b = the first lengths[b] samples (default L) of row b.  -> float32 tensor shaped like x, zero past each
+        length, bit for bit simulate.chain_effects for a clip of finite samples; a clip's result does not depend on the batch."""
+        x = _dev_f32(x, self.device)
+        if x.dim() not in (1, 2):
+            raise ValueError("effect_chain: x must be (B, L) or (L,), got %s" % (tuple(x.shape),))
+        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "effect_chain")
+        if B == 0:
+            raise ValueError("effect_chain: no clips")
+        programs = list(programs)
+        if all(len(step) > 0 and isinstance(step[0], str) for step in programs):      # one program (an empty one included) for all
+            programs = [programs] * B
+        if len(programs) != B:
+            raise ValueError("effect_chain: %d programs for %d clips" % (len(programs), B))
+        for b, program in enumerate(programs):
+            if not self.effect_chain_supported(program):
+                raise ValueError("effect_chain: clip %d: the device takes at most %d steps of %s with at most %d biquads between two "
+                                 "clip steps, got %s" % (b, self.MAX_CHAIN_OPS, sorted(self._CHAIN_OPS), self.MAX_CHAIN_STAGES,
+                                                         [step[0] for step in program]))
+        K = max(1, max(len(p) for p in programs))
+        ops = np.zeros((B, K), dtype=np.int32)
+        coef = np.zeros((B, K, 5), dtype=np.float64)
+        for b, program in enumerate(programs):
+            for k, step in enumerate(program):
+                ops[b, k] = self._CHAIN_OPS[step[0]]
+                if step[0] == "biquad":
+                    coef[b, k] = step[1]
+                elif step[0] == "clip":
+                    coef[b, k, 0] = step[1]
+        y = torch.empty((B, L), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.vfx_effect_chain(self.h, _ptr(x), B, L, (ctypes.c_int64 * B)(*lengths),
+                                             ops.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                             coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K, _ptr(y), L, self._stream()),
+                   "vfx_effect_chain")
+        return y[0] if squeeze else y
+
     def resunet_mel(self, mel_linear):
         """Generator.forward: linear mel (B,T,128) -> log10 mel (B,T,128)."""
         mel = _dev_f32(mel_linear, self.device)

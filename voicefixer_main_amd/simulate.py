@@ -23,8 +23,12 @@ same names, argument meaning and error behaviour:
   (Engine.quantize, Engine.time_dropout, csrc/effects.hip);
 * ``array_effects(frames, effects, rirs)``: the tail of ``MagicalEffects.effect`` behind the sox chain (:81-108) -- LARGESCALE,
   ``empty_c``, then reverb_rir, time_dropout and quant in dict order -- and ``array_effects_list``, whose clips stay on the device
-  between steps; ``draw_array_effects`` draws the dicts as ``RandomServer.generate`` does (random_server.py:135-217).  The sox effects
-  of the chain (tempo, speed, pitch, fade, ...) are the only ones without a device form: they are not built here at all.
+  between steps; ``draw_array_effects`` draws the dicts as ``RandomServer.generate`` does (random_server.py:135-217);
+* ``chain_effects(frames, effects)``: the sox chain in front of that tail (:41-64), as far as it is fully specified -- the biquads
+  ``low_pass``, ``high_pass``, ``bass`` and ``treble`` (``biquad_design``), ``clip`` and ``reverse``, restated from published
+  definitions and not pinned against sox --, ``magical_effects`` the whole of ``MagicalEffects.effect``, ``draw_effects`` the draws
+  of every name; ``chain_effects_list`` / ``magical_effects_list`` are their batch forms on the device (Engine.effect_chain,
+  csrc/chain.hip).  No device form, and no host form either: tempo, speed, pitch, fade, tremolo and reverb_freeverb.
 
 Everything is NumPy / SciPy on the host EXCEPT ``stft_hard``: its STFT -> mask -> ISTFT round trip is the hot path's own
 front-end and back-end (``vfx_stft_mel`` in its phase-emitting form and ``vfx_istft``), so it runs on the GPU through an
@@ -871,18 +875,24 @@ def array_effects(frames, effects, rirs=None):
         frames = frames / 2 ** 15
     if frames.ndim > 1:
         frames = np.squeeze(frames)
+    frames, emptied = _array_tail(frames, steps, rirs)
+    if large and not emptied:
+        frames = frames * 2 ** 15
+    return frames
+
+
+def _array_tail(frames, steps, rirs):
+    """`_array_steps`' steps on an array this function may modify -> (result, whether "empty_c" returned zeros)"""
     for key, params in steps:
         if key == "empty_c":
-            return np.zeros_like(frames)
+            return np.zeros_like(frames), True
         if key == "reverb_rir":
             frames = reverb_rir(frames, _clips.as_numpy(_rir_of(rirs, params)))
         elif key == "time_dropout":
             frames = time_dropout(frames, params)
         else:
             frames = quantification(frames, params)
-    if large:
-        frames = frames * 2 ** 15
-    return frames
+    return frames, False
 
 
 def _random_select(probs, rng):
@@ -917,6 +927,182 @@ def draw_array_effects(n, p_effects, effect_list, rir_nums, rng):
                 item[name] = [decision, int(_uniform(p["bins"][0], p["bins"][1], rng))]
             else:
                 item[name] = [True, None]
+        out.append(item)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the sox chain of MagicalEffects.effect (magical_effects.py:41-64, 110-156), as far as it is fully specified: the biquads low_pass,
+# high_pass, bass and treble, clip and reverse.  RESTATED from published definitions (the RBJ audio-EQ-cookbook biquads that sox's
+# biquads.c implements; WavAugment's clip) and NOT pinned: neither sox nor the `augment` package was at hand.  What is checked is what
+# SciPy and torch can check (tests/test_effect_chain_host.py); a machine that has sox is what would pin it.  NOT modelled: sox's
+# rounding of every sample to a multiple of 2^-31, and the six effects left out -- tempo, speed, pitch, fade, tremolo, reverb_freeverb.
+# ------------------------------------------------------------------------------------------------------------------
+CHAIN_BIQUADS = ("low_pass", "high_pass", "bass", "treble")
+CHAIN_NOT_BUILT = ("tempo", "speed", "pitch", "fade", "tremolo", "reverb_freeverb")
+SOX_MIN, SOX_MAX = -1.0, 1.0 - 2.0 ** -31      # sox's 32-bit sample range
+
+
+def biquad_design(name, value, fs=44100):
+    """(b0, b1, b2, a1, a2), a0 = 1, in float64 with Python's math: low_pass / high_pass -- value = the cut-off in Hz, a two-pole
+    Butterworth, equal to scipy.signal.butter(2, value, fs=fs) --; bass / treble -- value = the gain in dB, a shelf of slope 0.5 around
+    100 Hz / 3000 Hz: `value` dB at DC / at Nyquist, 0 dB at the other end; a gain of 0 is the identity (1, 0, 0, 0, 0).  ValueError
+    unless 0 < f < fs / 2."""
+    import math
+    if name not in CHAIN_BIQUADS:
+        raise ValueError("biquad_design: %s is no biquad of the chain" % (name,))
+    f = float(value) if name in ("low_pass", "high_pass") else (100.0 if name == "bass" else 3000.0)
+    if not 0 < f < fs / 2:
+        raise ValueError("biquad_design: %s: the frequency %r must lie inside (0, %r)" % (name, f, fs / 2))
+    w0 = 2 * math.pi * f / fs
+    c, s = math.cos(w0), math.sin(w0)
+    if name in ("low_pass", "high_pass"):
+        alpha = s / (2 * math.sqrt(0.5))
+        if name == "low_pass":
+            b = ((1 - c) / 2, 1 - c, (1 - c) / 2)
+        else:
+            b = ((1 + c) / 2, -(1 + c), (1 + c) / 2)
+        a = (1 + alpha, -2 * c, 1 - alpha)
+    else:
+        gain = float(value)
+        if gain == 0:
+            return (1.0, 0.0, 0.0, 0.0, 0.0)
+        A = math.exp(gain / 40 * math.log(10))
+        alpha = s / 2 * math.sqrt((A + 1 / A) * (1 / 0.5 - 1) + 2)
+        q = 2 * math.sqrt(A) * alpha
+        if name == "bass":
+            b = (A * ((A + 1) - (A - 1) * c + q), 2 * A * ((A - 1) - (A + 1) * c), A * ((A + 1) - (A - 1) * c - q))
+            a = ((A + 1) + (A - 1) * c + q, -2 * ((A - 1) + (A + 1) * c), (A + 1) + (A - 1) * c - q)
+        else:
+            b = (A * ((A + 1) + (A - 1) * c + q), -2 * A * ((A - 1) + (A + 1) * c), A * ((A + 1) + (A - 1) * c - q))
+            a = ((A + 1) - (A - 1) * c + q, 2 * ((A - 1) - (A + 1) * c), (A + 1) - (A - 1) * c - q)
+    return (b[0] / a[0], b[1] / a[0], b[2] / a[0], a[1] / a[0], a[2] / a[0])
+
+
+def _chain_steps(effects, sample_rate=44100):
+    """The chain part of one item's dict as the program Engine.effect_chain takes, in `generate_effect_chain`'s order -- fade first
+    (not built: ValueError), then the type-1 names in dict order: ("biquad", design), ("clip", 1 / params[1]), ("reverse",).  The
+    type-0 names are the tail's.  ValueError for the six effects that are not built, for "anytime" and for an unknown name."""
+    for key in effects.keys():
+        if key not in EFFECT_TYPES:
+            raise ValueError("Unknown effect %s" % (key,))
+        if key in CHAIN_NOT_BUILT or EFFECT_TYPES[key] == 3:
+            raise ValueError("chain_effects: %s is not built here" % (key,))
+    steps = []
+    for key in effects.keys():
+        if EFFECT_TYPES[key] != 1:
+            continue
+        if key in CHAIN_BIQUADS:
+            steps.append(("biquad", biquad_design(key, float(effects[key][1]), sample_rate)))
+        elif key == "clip":
+            steps.append(("clip", float(1 / effects[key][1])))
+        else:
+            steps.append(("reverse",))
+    return steps
+
+
+def _run_program(x, steps):
+    """A program of `_chain_steps` on a float32 array -> float32 array (a new one)"""
+    from scipy.signal import sosfilt
+    k = 0
+    while k < len(steps):
+        if steps[k][0] == "clip":      # WavAugment's Python effect: x.clamp_(min=x.min() * factor, max=x.max() * factor) in float32
+            factor = np.float32(steps[k][1])
+            lo, hi = np.float32(x.min()) * factor, np.float32(x.max()) * factor
+            x = np.minimum(np.maximum(x, lo), hi)
+            k += 1
+            continue
+        w = np.clip(x.astype(np.float64), SOX_MIN, SOX_MAX)      # a sox run: up to the next clip step
+        while k < len(steps) and steps[k][0] != "clip":
+            if steps[k][0] == "reverse":
+                w = w[::-1]
+            else:
+                b0, b1, b2, a1, a2 = steps[k][1]
+                w = np.clip(sosfilt(np.array([[b0, b1, b2, 1.0, a1, a2]]), np.ascontiguousarray(w)), SOX_MIN, SOX_MAX)
+            k += 1
+        x = w.astype(np.float32)
+    return np.ascontiguousarray(x)
+
+
+def chain_effects(frames, effects, sample_rate=44100):
+    """The sox chain of MagicalEffects.effect for one clip, as far as it is built here: `effects` is the dict name -> [decision,
+    params] of RandomServer.generate (or `draw_effects`); its type-0 names are left to `array_effects`.  The clip is made float32
+    (and squeezed), the input is not modified, the result is float32.  A sox run is a maximal stretch of low_pass, high_pass, bass,
+    treble and reverse: the clip is widened to float64 and limited to sox's range [-1, 1 - 2^-31], every biquad is
+    scipy.signal.sosfilt of `biquad_design`'s section from a zero state with its output limited again (the state keeps the unlimited
+    value), reverse flips, and the run's result is rounded once to float32.  clip, between runs, clamps the float32 clip to
+    [min * factor, max * factor], factor = float32(1 / params[1]), float32 products.  ValueError for tempo, speed, pitch, fade,
+    tremolo, reverb_freeverb, "anytime" and unknown names.  Restated, not pinned against sox; its rounding to multiples of 2^-31 is
+    not modelled."""
+    steps = _chain_steps(effects, sample_rate)
+    x = np.array(_clips.as_numpy(frames), dtype=np.float32)
+    if x.ndim > 1:
+        x = np.squeeze(x)
+    return _run_program(x, steps)
+
+
+def _tail_effects(effects):
+    return {key: effects[key] for key in effects.keys() if EFFECT_TYPES.get(key) == 0}
+
+
+def magical_effects(frames, effects, rirs=None, sample_rate=44100):
+    """The whole of MagicalEffects.effect (magical_effects.py:66-108) for one clip and one drawn dict: the clip is made float32;
+    LARGESCALE is decided once, on that input -- a largest sample above 10 divides the clip by 2 ** 15 here and multiplies the
+    result by it at the very end --; `chain_effects`; then the type-0 tail as `array_effects` runs it ("empty_c" gives zeros).  Both
+    parts are checked before anything runs."""
+    steps = _chain_steps(effects, sample_rate)
+    tail = _array_steps(_tail_effects(effects))
+    x = np.array(_clips.as_numpy(frames), dtype=np.float32)
+    large = bool(x.size and np.max(x) > 10)
+    if large:
+        x /= np.float32(2 ** 15)
+    if x.ndim > 1:
+        x = np.squeeze(x)
+    x, emptied = _array_tail(_run_program(x, steps), tail, rirs)
+    if large and not emptied:
+        x = x * 2 ** 15
+    return x
+
+
+def draw_effects(n, p_effects, effect_list, rir_nums, rng):
+    """RandomServer.generate(effect_list) / `do` (random_server.py:135-217) per item, for every name it knows, in `effect_list` order
+    from the one generator -- consumed exactly as a loop over `do` consumes it, also for the names nothing here runs.  A name draws
+    its chance and is skipped when the first decision is false; then tempo, speed, pitch [decisions, U(up range) if the second
+    decision holds else U(down range)]; treble, bass, tremolo [decisions, U(level)]; clip [decisions, U(louder_time)]; low_pass,
+    high_pass [decisions, U(their range)]; reverse [True, None]; fade [True, [U(in portion), U(out portion)]]; reverb_freeverb
+    [True, [U(reverb_level), U(dumping_factor), U(room_size)]]; "anytime" [True, its four values]; the type-0 names as
+    `draw_array_effects` draws them.  -> n dicts that `magical_effects` takes."""
+    ranges = {"treble": "level", "bass": "level", "tremolo": "level", "clip": "louder_time", "low_pass": "low_pass_range",
+              "high_pass": "high_pass_range"}
+    out = []
+    for _ in range(n):
+        item = {}
+        for name in effect_list:
+            if name not in EFFECT_TYPES:
+                raise ValueError("Unknown effect %s" % (name,))
+            if EFFECT_TYPES[name] == 0:
+                item.update(draw_array_effects(1, p_effects, [name], rir_nums, rng)[0])
+                continue
+            p = p_effects[name]
+            sample = lambda key: float(_uniform(p[key][0], p[key][1], rng))      # noqa: E731
+            decision, _chance = _random_select(p["prob"], rng)
+            if not decision[0]:
+                continue
+            if name in ("tempo", "speed"):
+                item[name] = [decision, sample("speed_up_range" if decision[1] else "speed_down_range")]
+            elif name == "pitch":
+                item[name] = [decision, sample("pitch_up_range" if decision[1] else "pitch_down_range")]
+            elif name in ranges:
+                item[name] = [decision, sample(ranges[name])]
+            elif name == "reverse":
+                item[name] = [True, None]
+            elif name == "fade":
+                item[name] = [True, [sample("fade_in_portion"), sample("fade_out_portion")]]
+            elif name == "reverb_freeverb":
+                item[name] = [True, [sample("reverb_level"), sample("dumping_factor"), sample("room_size")]]
+            else:      # "anytime"
+                item[name] = [True, [sample("inner_segment_scale"), sample("overall_scale"), sample("first_segment_portion"),
+                                     sample("snr_range")]]
         out.append(item)
     return out
 
@@ -1056,3 +1242,112 @@ def array_effects_list(clips, effects, rirs=None, engine=None, to_host=True):
             for i, row in zip(idx, _clips.unpad(_clips.pad([cur[i] for i in idx], cur[idx[0]].device, dtype), lens, True)):
                 cur[i] = row
     return [_clips.as_numpy(c) for c in cur]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# batch forms of the chain (Engine.effect_chain, csrc/chain.hip) and of the whole of MagicalEffects.effect
+# ------------------------------------------------------------------------------------------------------------------
+def _chain_on_device(clips, programs, eng, large=None):
+    """clips[i] (1-D, non-empty; any dtype: made float32 where it is) through programs[i] on the device -> float32 device rows, each
+    bit for bit `_run_program`.  large[i]: the clip is divided by 2 ** 15 first (LARGESCALE; exact torch division).  Padded batches
+    of up to MAX_BATCH sorted by length; a row with a sample that is not finite is computed by the host function instead."""
+    lengths = [c.shape[0] for c in clips]
+    out = [None] * len(clips)
+    for idx in _clips.batches(range(len(clips)), lengths, MAX_BATCH):
+        lens = [lengths[i] for i in idx]
+        rows = [_clips.as_tensor(clips[i]).to(device=eng.device, dtype=torch.float32) for i in idx]
+        if large is not None:
+            rows = [r / 2 ** 15 if large[i] else r for i, r in zip(idx, rows)]
+        x = _clips.pad(rows, eng.device, torch.float32, width=(lens[-1] + 3) // 4 * 4)
+        finite = torch.isfinite(x).all(dim=1).tolist()      # (one download per batch)
+        y = eng.effect_chain(x, [programs[i] for i in idx], lengths=lens)
+        for j, (i, row) in enumerate(zip(idx, _clips.unpad(y, lens, False))):
+            out[i] = row if finite[j] else _clips.to_device(_run_program(rows[j].cpu().numpy(), programs[i]), eng.device)
+    return out
+
+
+def _chain_takes(c, program):
+    """Whether the device chain takes this clip and its program: non-empty and 1-D, a program inside Engine.effect_chain's limits"""
+    from .engine import Engine
+    return len(list(c.shape)) == 1 and c.shape[0] > 0 and Engine.effect_chain_supported(program)
+
+
+def chain_effects_list(clips, effects, engine=None, to_host=True):
+    """`chain_effects` for a list of clips, effects[i] the dict of clip i.  Non-empty 1-D clips -- float32 after the reference's
+    conversion, which `chain_effects` applies to every dtype -- whose program the device takes (at most 8 steps; a dict cannot hold
+    more) go through Engine.effect_chain as padded batches of up to MAX_BATCH, sorted by length, every clip with its own program:
+    bit for bit `chain_effects`.  Every other clip, and a clip with a sample that is not finite, takes the host function.  All the
+    dicts are checked before anything runs.  -> list in the caller's order: float32 NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    effects = list(effects)
+    if len(effects) != len(clips):
+        raise ValueError("chain_effects_list: %d dicts for %d clips" % (len(effects), len(clips)))
+    programs = [_chain_steps(e) for e in effects]
+    eng = _engine_or_default(engine)
+    dev = [i for i in range(len(clips)) if _chain_takes(clips[i], programs[i])]
+    out = [None] * len(clips)
+    for i, row in zip(dev, _chain_on_device([clips[i] for i in dev], [programs[i] for i in dev], eng)):
+        out[i] = row
+    for i in range(len(clips)):
+        if out[i] is None:
+            out[i] = chain_effects(clips[i], effects[i])
+    return _deliver(out, eng, to_host)
+
+
+def _deliver(rows, eng, to_host):
+    """Results that are device tensors or host arrays -> all on the device, or all NumPy arrays after one download per dtype"""
+    if not to_host:
+        return [_clips.to_device(r, eng.device) for r in rows]
+    rows = list(rows)
+    for dtype in _FX_DTYPES:
+        idx = [i for i, r in enumerate(rows) if isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == dtype and r.dim() == 1
+               and r.shape[0] > 0]
+        if idx:
+            lens = [rows[i].shape[0] for i in idx]
+            for i, row in zip(idx, _clips.unpad(_clips.pad([rows[i] for i in idx], rows[idx[0]].device, dtype), lens, True)):
+                rows[i] = row
+    return [_clips.as_numpy(r) for r in rows]
+
+
+def magical_effects_list(clips, effects, rirs=None, engine=None, to_host=True):
+    """`magical_effects` for a list of clips, effects[i] the dict of clip i: device-resident from the first step to the last.  A
+    non-empty 1-D clip whose program the device takes is made float32 where it is, LARGESCALE is decided there and its division is an
+    exact torch operation, the chain runs through Engine.effect_chain (`chain_effects_list`'s batches), and the float32 rows go on,
+    without leaving the device, through `array_effects_list`'s steps for the type-0 names; the multiplication by 2 ** 15 comes last.
+    Bit for bit `magical_effects` wherever `array_effects_list` is bit for bit `array_effects`: through LARGESCALE, "empty_c" and the
+    quantiser; the device reverb rounds its sums otherwise than SciPy (inside its own bound, `reverb_rir_list`), and time_dropout's
+    smoothed patches agree to rounding.  Every other clip takes `magical_effects`.  All the dicts are checked before anything runs.
+    -> list in the caller's order: NumPy arrays (to_host), or device tensors."""
+    clips = list(clips)
+    effects = list(effects)
+    if len(effects) != len(clips):
+        raise ValueError("magical_effects_list: %d dicts for %d clips" % (len(effects), len(clips)))
+    programs = [_chain_steps(e) for e in effects]
+    tails = [_tail_effects(e) for e in effects]
+    for t in tails:
+        _array_steps(t)
+    eng = _engine_or_default(engine)
+    dev = [i for i in range(len(clips)) if _chain_takes(clips[i], programs[i])]
+    out = [None] * len(clips)
+    if dev:
+        rows = [_clips.as_tensor(clips[i]).to(device=eng.device, dtype=torch.float32) for i in dev]
+        large = [bool(v) for v in (_clips.pad(rows, eng.device, torch.float32).max(dim=1).values > 10).tolist()]
+        # (a padded row's zeros cannot lift a maximum above 10)
+        chained = _chain_on_device(rows, [programs[i] for i in dev], eng, large=large)
+        # `array_effects_list` decides LARGESCALE for itself on what it is given.  The chain never raises a clip's largest sample
+        # above max(it, 1), so only a clip that was above 10 * 2 ** 15 can still be above 10 here: such a row takes the host tail
+        emptied = [[s[0] for s in _array_steps(tails[i])][:1] == ["empty_c"] for i in dev]
+        over = [bool(v) for v in (_clips.pad(chained, eng.device, torch.float32).max(dim=1).values > 10).tolist()]
+        keep = [j for j in range(len(dev)) if not over[j]]
+        done = dict(zip(keep, array_effects_list([chained[j] for j in keep], [tails[dev[j]] for j in keep], rirs, engine=eng,
+                                                 to_host=False)))
+        for j, i in enumerate(dev):
+            if over[j]:      # (rare: the host tail, which takes the steps without the LARGESCALE decision)
+                y = _clips.to_device(_array_tail(chained[j].cpu().numpy(), _array_steps(tails[i]), rirs)[0], eng.device)
+            else:
+                y = done[j]
+            out[i] = y * 2 ** 15 if large[j] and not emptied[j] else y
+    for i in range(len(clips)):
+        if out[i] is None:
+            out[i] = magical_effects(clips[i], effects[i], rirs)
+    return _deliver(out, eng, to_host)
