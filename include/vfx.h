@@ -234,6 +234,39 @@ int vfx_restore_gsr_varlen(vfx_handle* h, const float* wav, int B, int Lmax, con
 int vfx_restore_ssr_varlen(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out, void* stream);
 
 /*
+ * vfx_restore_gsr_varlen with the targets of the clips: the restore and the four mel scores handler() returns for a file with a
+ * target (eval_gsr_voicefixer.py:56-64), in one call.  wav, lengths, wav_out, logmel_out, flags: as vfx_restore_gsr_varlen, whose
+ * launches run unchanged -- both outputs are bit for bit those of that call.  target (B, Lmax) device: clip b of it = its first
+ * target_lengths[b] samples (HOST int[B]; NULL: lengths).  metrics_out (B, VFX_N_HANDLER_METRICS) device doubles, per clip over its
+ * own T_b = lengths[b] / hop + 1 frames, with
+ *   lg  = the model's log10 estimate (logmel_out), unclipped          lin = 10 ** min(lg, 5)   (from_log, in float32)
+ *   den = what the vocoder receives: lin, times the amp_to_original_f ratio when flags bit0 is set (float32)
+ *   tgt = the target's linear mel: mel(|STFT| clamped at 1e-8) of the target at its own length (float32)
+ *   0 mel-lsd             LSD(den, tgt) = mean_t sqrt(mean_f log10(tgt^2 / (den + 1e-12)^2 + 1e-12)^2)
+ *   1 mel-sispec          SiSpec(lg, log10(max(tgt, 1e-8)))
+ *   2 mel-non-log-sispec  SiSpec(lin, tgt) -- before unify_energy, as the reference takes it
+ *   3 mel-ssim            skimage structural_similarity(den, tgt, win_size=7), data_range 2
+ * SiSpec(e, g) = 10 log10(pt / (pn + 1e-12) + 1e-12), s = <e,g> / (<g,g> + 1e-8), pt = s^2 <g,g>, pn = max(<e,e> - 2 s <e,g> + pt, 0).
+ * Every sum runs in float64 over the clip's own frames in an order fixed by the clip alone: a clip's four numbers do not depend on
+ * the batch it is in, and no row at or past its frames is read.  The target mel and the partial sums live in handle scratch that
+ * grows only for a call with a target.  Sub-batched as vfx_restore_gsr_varlen.
+ * Fails -- naming the clip, before anything is launched -- when target_lengths[b] / hop != lengths[b] / hop (the reference's
+ * frame-count mismatch), when a clip has fewer than 7 frames (lengths[b] < 6 hop = 2646: skimage refuses the image), when
+ * lengths[b] or target_lengths[b] is outside (n_fft/2, Lmax], and for a NULL target or metrics_out.
+ */
+#define VFX_N_HANDLER_METRICS 4
+int vfx_restore_gsr_varlen_scored(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                  const int* target_lengths, float* wav_out, float* logmel_out, double* metrics_out, int flags,
+                                  void* stream);
+
+/* The spectrogram-domain twin (eval_ssr_unet.py:116-126): vfx_restore_ssr_varlen, whose launches run unchanged, then the same four
+ * scores of (est, tgt), est = mel(|STFT| clamped at 1e-8) of the restored clip wav_out[b] at its own length, tgt as above:
+ * LSD(est, tgt), SiSpec(log10(max(est, 1e-8)), log10(max(tgt, 1e-8))), SiSpec(est, tgt), SSIM(est, tgt).  Same arithmetic, same
+ * failure cases, and still one padded frame count per call. */
+int vfx_restore_ssr_varlen_scored(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                  const int* target_lengths, float* wav_out, double* metrics_out, void* stream);
+
+/*
  * Long-audio chunkers: the two `LambdaOverlapAdd` classes (tools/dsp/overlapadd.py:337-480 and
  * tools/dsp/overlapadd_boxcar.py:338-513) segment a signal, run the network per chunk and stitch.  The
  * network call stays with the caller (all equal-length chunks as ONE batch); these are the two data

@@ -173,6 +173,15 @@ int vfx_op_ssim(vfx_handle* h, const float* est, const float* target, int B, int
 /* The SI-SDR of vfx_audio_metrics alone (k_sisdr_slabs + k_score_final): est[b, :lens[b]] against target[b, :lens[b]] of (B, L)
  * device tensors; lens HOST int[B], 1 <= lens[b] <= L -> out (B) device doubles.  Synchronises. */
 int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target, int B, int L, const int* lens, double* out, void* stream);
+/* The scoring launches of the scored GSR restore entry alone (k_handler_frames, k_ssim_tiles, k_handler_final) on caller tensors:
+ * logmel, den, target_mel (B, T, 128) device -- the model's log10 estimate, what the vocoder receives, the target's linear mel --,
+ * clip b = their first frames[b] rows (HOST int[B], 7 <= frames[b] <= T) -> out (B, 4) device doubles: mel-lsd, mel-sispec,
+ * mel-non-log-sispec, mel-ssim as include/vfx.h defines them.  Synchronises. */
+int vfx_op_handler_metrics(vfx_handle* h, const float* logmel, const float* den, const float* target_mel, int B, int T, const int* frames,
+                           double* out, void* stream);
+/* Those of the scored SSR restore entry (k_score_frames, k_ssim_tiles, k_handler_final): the same four of (est_mel, target_mel). */
+int vfx_op_mel_metrics(vfx_handle* h, const float* est_mel, const float* target_mel, int B, int T, const int* frames, double* out,
+                       void* stream);
 /* The two images vfx_audio_metrics_rate scores, of one signal: wav (B, Lmax) device, clip b = its first lengths[b] samples (lengths HOST
  * int[B], the bounds of vfx_audio_metrics_rate at that rate) -> sp (B, T, 372) and mel (B, T, 80) at rate 16000 (k_stft_dft), (B, T, 1025)
  * and (B, T, 128) at rate 44100 (k_stft_mel); T = the frames of the longest clip, rows at or past a clip's own frames are zeros.

@@ -23,6 +23,7 @@ FLAG_NEGATIVE_INPUT = 1
 FLAG_F16_SATURATED = 2   # precision 2: an activation of the vocoder left the fp16 range and was clamped
 FLAG_PEAK_NORMALISED = 4  # vfx_restore_gsr divided a clip by its peak (the reference's "Exceed energy limit" warning)
 N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metrics
+N_HANDLER_METRICS = 4     # VFX_N_HANDLER_METRICS: the columns of vfx_restore_*_varlen_scored
 
 
 class VfxConfig(ctypes.Structure):
@@ -91,6 +92,10 @@ SIGNATURES = {
     "vfx_restore_gsr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vfx_restore_gsr_varlen": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, c_void_p]),
     "vfx_restore_ssr_varlen": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_restore_gsr_varlen_scored": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
+                                              c_void_p, c_int, c_void_p]),
+    "vfx_restore_ssr_varlen_scored": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
+                                              c_void_p]),
     "vfx_take_flags": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "vfx_take_flags_masked": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int)]),
     "vfx_turn_begin": (c_int, [c_int, c_void_p]),
@@ -137,6 +142,8 @@ TEST_SIGNATURES = {
     "vfx_op_peak_trim": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_ssim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_handler_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_op_mel_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_op_score_spectrogram": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "vfx_op_stoi_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),

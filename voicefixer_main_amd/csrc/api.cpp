@@ -981,8 +981,13 @@ static int padded_group(int n) { return n <= 2 ? n : (n <= 8 ? (n + 1) / 2 * 2 :
 //     caller buckets by it) -- and a clip's rows past T_b are zeros like the network's own time padding (unet.py:75-77);
 //   * vocoder: every launch stops the clip at its own length (zero padding, the k7 reflections, the tail of -4 frames);
 //   * peak normalisation and trim_center per clip; wav_out (B, Lmax) and logmel_out (B, Tmax, 128) are zero past a clip's end.
+//
+// With a target (vfx_restore_gsr_varlen_scored, which has checked the lengths): target (B, Lmax), clip b = its first target_lengths[b]
+// samples, metrics_out (B, VFX_N_HANDLER_METRICS) -- the handler's four mel scores (eval_gsr_voicefixer.py:56-64), scored where the
+// log10 estimate and what the vocoder receives both exist.  Without one (all three NULL) the launches and the scratch are the same as ever.
 static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out,
-                                    float* logmel_out, int flags, void* stream) {
+                                    float* logmel_out, int flags, void* stream, const float* target = nullptr,
+                                    const int* target_lengths = nullptr, double* metrics_out = nullptr) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(wav && wav_out && lengths && B > 0 && B <= kMaxVarlenClips, "bad argument");
   const int am = h->analysis_model;
@@ -1050,7 +1055,8 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   auto up = [](int64_t n) { return (size_t)((n + 63) / 64 * 64) * sizeof(float); };
   const size_t o_mel = 0, o_log = o_mel + up(nmel), o_den = o_log + up(nmel), o_gin = o_den + up(nmel), o_gout = o_gin + up(gmax),
                o_vmel = o_gout + up(gmax), o_long = o_vmel + up(vmel), o_ws = o_long + up(vlong), o_pk = o_ws + up(2 * B + 64),
-               o_end = o_pk + up(nmax + 64);
+               o_tmel = o_pk + up(nmax + 64), o_score = o_tmel + (target ? up(nmel) : 0),
+               o_end = o_score + (target ? handler_metrics_ws_bytes(B, T) : 0);  // (the last two: only a call with a target has them)
   // Handle-owned scratch beside the arena (grow-only): the tensors that travel BETWEEN the plans of one varlen call (every plan
   // places its own buffers from offset 0 of the arena).  Growing frees and re-allocates: the device is idle then (hipFree waits).
   char* const sc = h->scratch.ensure(h, o_end, 8, "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured "
@@ -1099,6 +1105,14 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   }
   if (logmel_out) launch_copy_rows_masked(lg, logmel_out, B, T, 128, d_t, s);
   launch_from_log(lg, mel, B, T, unify, ws, den, s, d_t);
+  // ---- the handler's scores against the target: its mel by pre() at its own length, then the clip's four numbers over its own frames
+  if (target) {
+    int* const d_tl = h->lens_row(LENS_TARGET_SAMPLES);
+    launch_set_frames(d_tl, target_lengths, B, s);
+    float* const tmel = reinterpret_cast<float*>(sc + o_tmel);
+    launch_stft_mel(h->fe, target, B, Lmax, T, tmel, nullptr, nullptr, nullptr, 0, hop, 1e-8f, s, d_tl);
+    launch_handler_metrics(lg, den, tmel, B, T, d_t, sc + o_score, metrics_out, s);
+  }
   // ---- the vocoder, one pass per run of clips: every launch stops a clip at its own length (round 5), so a run needs no common
   // padded frame count -- only the ResUNet does
   for (auto& r : runs) {
@@ -1135,11 +1149,51 @@ int vfx_restore_gsr_varlen(vfx_handle* h, const float* wav, int B, int Lmax, con
   });
 }
 
+// What the two scored entries check of a whole batch before any sub-batch launches: the pointers, both lengths of every clip inside
+// (n_fft/2, Lmax], at least 7 frames (skimage's 7 x 7 SSIM refuses a smaller image), and the reference's frame-count mismatch
+// (eval_gsr_voicefixer.py:56-64 compares an estimate of lengths[b] / hop + 1 frames with a target of target_lengths[b] / hop + 1)
+static int check_scored_batch(vfx_handle* h, const char* who, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                              const int* target_lengths, const float* wav_out, const double* metrics_out) {
+  VFX_API_BEGIN
+  VFX_CHECK(h != nullptr, "NULL handle");
+  VFX_CHECK(wav && wav_out && lengths && B > 0 && Lmax > 0, "%s: bad argument", who);
+  VFX_CHECK(target, "%s: target is NULL (a call without targets is the entry without _scored)", who);
+  VFX_CHECK(metrics_out, "%s: metrics_out is NULL", who);
+  VFX_CHECK(h->cfg.n_mels == 128, "%s: needs 128 mel bands", who);
+  const int hop = h->cfg.hop, half = h->cfg.n_fft / 2;
+  for (int b = 0; b < B; ++b) {
+    const int Lb = lengths[b], Lt = target_lengths ? target_lengths[b] : Lb;
+    VFX_CHECK(Lb > half && Lb <= Lmax, "%s: clip %d has %d samples (need %d < length <= Lmax = %d)", who, b, Lb, half, Lmax);
+    VFX_CHECK(Lt > half && Lt <= Lmax, "%s: the target of clip %d has %d samples (need %d < length <= Lmax = %d)", who, b, Lt, half, Lmax);
+    VFX_CHECK(Lb / hop + 1 >= 7, "%s: clip %d has %d samples, %d frames: the scores need at least 7 frames (%d samples)", who, b, Lb,
+              Lb / hop + 1, 6 * hop);
+    VFX_CHECK(Lt / hop == Lb / hop, "%s: clip %d has %d frames (%d samples) but its target has %d (%d samples)", who, b, Lb / hop + 1, Lb,
+              Lt / hop + 1, Lt);
+  }
+  VFX_API_END
+}
+
+int vfx_restore_gsr_varlen_scored(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                  const int* target_lengths, float* wav_out, float* logmel_out, double* metrics_out, int flags,
+                                  void* stream) {
+  if (const int rc = check_scored_batch(h, "vfx_restore_gsr_varlen_scored", wav, target, B, Lmax, lengths, target_lengths, wav_out, metrics_out))
+    return rc;
+  if (!target_lengths) target_lengths = lengths;
+  const int T = Lmax / h->cfg.hop + 1;
+  return for_sub_batches(B, kMaxVarlenClips, [&](int b, int n) {
+    return vfx_restore_gsr_varlen_1(h, wav + (int64_t)b * Lmax, n, Lmax, lengths + b, wav_out + (int64_t)b * Lmax,
+                                    logmel_out ? logmel_out + (int64_t)b * T * 128 : nullptr, flags, stream, target + (int64_t)b * Lmax,
+                                    target_lengths + b, metrics_out + (int64_t)b * VFX_N_HANDLER_METRICS);
+  });
+}
+
 // The spectrogram-domain twin: the per-segment body of handler_ssr_unet (eval_ssr_unet.py:77-114: sp = |STFT(wav)|, model(sp, wav))
 // for a batch of clips of unequal length -- per clip the frames and reflection of its own length, the trunk's zero time padding
 // behind its own last frame (unet_v2.py:103-110), the ISTFT to its own length (fDomainHelper.py:30-32); zeros past its end.
 // Same requirement as vfx_restore_gsr_varlen: one padded frame count per call.
-static int vfx_restore_ssr_varlen_1(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out, void* stream) {
+// With a target (vfx_restore_ssr_varlen_scored): the four scores of eval_ssr_unet.py:116-126 on the mel of the restored clip and of its target
+static int vfx_restore_ssr_varlen_1(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out, void* stream,
+                                    const float* target = nullptr, const int* target_lengths = nullptr, double* metrics_out = nullptr) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(wav && wav_out && lengths && B > 0 && B <= kMaxVarlenClips, "bad argument");
   VFX_CHECK(h->unet[VFX_MODEL_UNET_SPEC], "vfx_restore_ssr_varlen: weights of the spectrogram ResUNet are not finalized");
@@ -1179,6 +1233,18 @@ static int vfx_restore_ssr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   });
   launch_istft(h->fe, reinterpret_cast<float*>(h->arena.p + plan->named["re"]), reinterpret_cast<float*>(h->arena.p + plan->named["im"]), B, T,
                Lmax, hop, wav_out, s, d_l);
+  if (target) {  // mel_out = mel(|STFT(out)|), target_mel = pre(target), both clamped at 1e-8 and framed at the clip's own length
+    const size_t nmel = ((size_t)B * T * 128 * sizeof(float) + 255) / 256 * 256;
+    char* const sc = h->scratch.ensure(h, 2 * nmel + handler_metrics_ws_bytes(B, T), 8, "the varlen scratch would have to grow from %zu to %zu "
+                                       "bytes, but a hipGraph was captured from plan '%s': run the largest scored batch once BEFORE capturing");
+    float* const emel = reinterpret_cast<float*>(sc);
+    float* const tmel = reinterpret_cast<float*>(sc + nmel);
+    int* const d_tl = h->lens_row(LENS_TARGET_SAMPLES);
+    launch_set_frames(d_tl, target_lengths, B, s);
+    launch_stft_mel(h->fe, wav_out, B, Lmax, T, emel, nullptr, nullptr, nullptr, 0, hop, 1e-8f, s, d_l);
+    launch_stft_mel(h->fe, target, B, Lmax, T, tmel, nullptr, nullptr, nullptr, 0, hop, 1e-8f, s, d_tl);
+    launch_mel_metrics(emel, tmel, B, T, d_t, sc + 2 * nmel, metrics_out, s);
+  }
   VFX_API_END
 }
 int vfx_restore_ssr_varlen(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out, void* stream) {
@@ -1186,6 +1252,18 @@ int vfx_restore_ssr_varlen(vfx_handle* h, const float* wav, int B, int Lmax, con
   const int T = Lmax / h->cfg.hop + 1;
   return for_sub_batches(B, std::min(kMaxVarlenClips, max_clips_per_launch(h, T, false, true, false)), [&](int b, int n) {
     return vfx_restore_ssr_varlen_1(h, wav + (int64_t)b * Lmax, n, Lmax, lengths + b, wav_out + (int64_t)b * Lmax, stream);
+  });
+}
+
+int vfx_restore_ssr_varlen_scored(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                  const int* target_lengths, float* wav_out, double* metrics_out, void* stream) {
+  if (const int rc = check_scored_batch(h, "vfx_restore_ssr_varlen_scored", wav, target, B, Lmax, lengths, target_lengths, wav_out, metrics_out))
+    return rc;
+  if (!target_lengths) target_lengths = lengths;
+  const int T = Lmax / h->cfg.hop + 1;
+  return for_sub_batches(B, std::min(kMaxVarlenClips, max_clips_per_launch(h, T, false, true, false)), [&](int b, int n) {
+    return vfx_restore_ssr_varlen_1(h, wav + (int64_t)b * Lmax, n, Lmax, lengths + b, wav_out + (int64_t)b * Lmax, stream,
+                                    target + (int64_t)b * Lmax, target_lengths + b, metrics_out + (int64_t)b * VFX_N_HANDLER_METRICS);
   });
 }
 

@@ -1142,6 +1142,40 @@ extern "C" int vfx_op_sisdr(vfx_handle* h, const float* est, const float* target
   return 0;
 }
 
+// the scoring launches of the two scored restore entries on caller tensors: logmel == NULL: those of the SSR entry on (den, target_mel)
+static int op_handler_metrics(const char* who, vfx_handle* h, const float* logmel, const float* den, const float* target_mel, int B, int T,
+                              const int* frames, double* out, void* stream) {
+  try {
+    VFX_CHECK(h && den && target_mel && frames && out && B > 0 && B <= 65535 && T >= 7, "%s: bad argument", who);
+    for (int b = 0; b < B; ++b) VFX_CHECK(frames[b] >= 7 && frames[b] <= T, "%s: clip %d has %d frames (need 7 .. T = %d)", who, b, frames[b], T);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const int* d_frames = upload_lens(sc.blob, frames, B);
+    char* ws = static_cast<char*>(sc.blob.alloc(handler_metrics_ws_bytes(B, T)));
+    if (logmel) launch_handler_metrics(logmel, den, target_mel, B, T, d_frames, ws, out, s);
+    else launch_mel_metrics(den, target_mel, B, T, d_frames, ws, out, s);
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int vfx_op_handler_metrics(vfx_handle* h, const float* logmel, const float* den, const float* target_mel, int B, int T,
+                                      const int* frames, double* out, void* stream) {
+  if (!logmel) {
+    set_error("vfx_op_handler_metrics: bad argument");
+    return 1;
+  }
+  return op_handler_metrics("vfx_op_handler_metrics", h, logmel, den, target_mel, B, T, frames, out, stream);
+}
+
+extern "C" int vfx_op_mel_metrics(vfx_handle* h, const float* est_mel, const float* target_mel, int B, int T, const int* frames, double* out,
+                                  void* stream) {
+  return op_handler_metrics("vfx_op_mel_metrics", h, nullptr, est_mel, target_mel, B, T, frames, out, stream);
+}
+
 extern "C" int vfx_op_score_spectrogram(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, int rate, float* sp,
                                         float* mel, void* stream) {
   try {

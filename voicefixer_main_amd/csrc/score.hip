@@ -8,6 +8,13 @@
 //                  positions, the inputs of the tile (38 x 70) in LDS, 7-wide row sums and a 7-row ring of them per thread
 //   k_score_final  one workgroup per clip: the slabs, frames and tiles of THAT clip summed in a fixed order, the formulas
 //
+// and the four mel scores a handler returns for a file with a target (eval_gsr_voicefixer.py:59-64, eval_ssr_unet.py:116-126):
+//
+//   k_handler_frames  k_score_frames for the GSR handler's operand mix: one wave per (clip, frame) reads the rows of the log10 estimate,
+//                     of what the vocoder receives and of the target mel ONCE -- the LSD term of (den, tgt), the inner products of
+//                     (lg, to_log(tgt)) and of (from_log(lg), tgt)
+//   k_handler_final   one workgroup per clip: its frame sums (of either frame kernel) and its SSIM tiles -> four numbers
+//
 // Slabs and tiles are cut from the clip's own extent (not from the batch's Lmax or T), and the final sums stop at the clip's own
 // count, so a clip's nine numbers do not depend on the batch it is scored in.  No float atomics, no frame at or past a clip's
 // `frames` is read.
@@ -48,6 +55,14 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[kWaves])
 #pragma unroll
   for (int k = 0; k < K; ++k) v[k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
   __syncthreads();
+}
+
+// SiSpec (metrics.py:89-95, energy_unify / pow_p_norm of utils.py:81-101): s = <e,g> / (|g|^2 + 1e-8), target s g
+__device__ __forceinline__ double sispec_db(double ee, double eg, double gg) {
+  const double s = eg / (gg + 1e-8);
+  const double pt = s * s * gg;
+  const double pn = fmax(ee - 2.0 * s * eg + pt, 0.0);
+  return 10.0 * log10(pt / (pn + 1e-12) + 1e-12);
 }
 
 }  // namespace
@@ -227,16 +242,9 @@ __global__ __launch_bounds__(256) void k_score_final(ScoreFinalArgs a) {
       }
       block_sum<7>(v, red);
       if (tid == 0) {
-        // SiSpec (metrics.py:89-95, energy_unify / pow_p_norm of utils.py:81-101): s = <e,g> / (|g|^2 + 1e-8), target s g
-        auto sispec = [](double ee, double eg, double gg) {
-          const double s = eg / (gg + 1e-8);
-          const double pt = s * s * gg;
-          const double pn = fmax(ee - 2.0 * s * eg + pt, 0.0);
-          return 10.0 * log10(pt / (pn + 1e-12) + 1e-12);
-        };
         out[1 + 4 * m] = v[0] / (double)rows;
-        out[2 + 4 * m] = sispec(v[1], v[2], v[3]);
-        out[3 + 4 * m] = sispec(v[4], v[5], v[6]);
+        out[2 + 4 * m] = sispec_db(v[1], v[2], v[3]);
+        out[3 + 4 * m] = sispec_db(v[4], v[5], v[6]);
       }
     }
     if (a.ssim_ws[m]) {
@@ -247,6 +255,77 @@ __global__ __launch_bounds__(256) void k_score_final(ScoreFinalArgs a) {
       block_sum<1>(v, red);
       if (tid == 0) out[4 + 4 * m] = v[0] / ((double)Ho * (double)Wo);
     }
+  }
+}
+
+// ws[(b * T + t) * 7 + k], t < frames[b], of three (B, T, 128) images -- lg the log10 estimate, den what the vocoder receives, tgt the
+// target's linear mel (eval_gsr_voicefixer.py:59-64):
+//   k = 0     sqrt(mean_f log10(tgt^2 / (den + 1e-12)^2 + 1e-12)^2)            the LSD term of (den, tgt)
+//   k = 1..3  <e,e>, <e,g>, <g,g> of e = lg, g = log10(max(tgt, 1e-8))         mel-sispec
+//   k = 4..6  the same of e = from_log(lg) (float32, k_from_log's value), g = tgt  mel-non-log-sispec (before unify_energy)
+__global__ __launch_bounds__(256) void k_handler_frames(const float* __restrict__ lg, const float* __restrict__ den,
+                                                        const float* __restrict__ tgt, int T, const int* __restrict__ frames,
+                                                        double* __restrict__ ws) {
+  constexpr int F = 128;
+  const int b = blockIdx.y;
+  const int t = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (t >= frames[b]) return;
+  const int64_t row = ((int64_t)b * T + t) * F;
+  double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int f = lane; f < F; f += 64) {
+    const float lf = lg[row + f];
+    const double gv = tgt[row + f];
+    const double d = (double)den[row + f] + 1e-12;
+    const double l = log10(gv * gv / (d * d) + 1e-12);
+    v[0] += l * l;
+    const double le = lf, lt = log10(fmax(gv, 1e-8));
+    v[1] += le * le;
+    v[2] += le * lt;
+    v[3] += lt * lt;
+    const double ev = from_log_value(lf);
+    v[4] += ev * ev;
+    v[5] += ev * gv;
+    v[6] += gv * gv;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) v[k] = wave_sum(v[k]);
+  if (lane == 0) {
+    double* w = ws + ((int64_t)b * T + t) * 7;
+    w[0] = sqrt(v[0] / (double)F);
+#pragma unroll
+    for (int k = 1; k < 7; ++k) w[k] = v[k];
+  }
+}
+
+// out[b * 4 + {0, 1, 2, 3}] = mel-lsd, mel-sispec, mel-non-log-sispec, mel-ssim of clip b from its frames_ws rows ([B][T][7]) and its
+// SSIM tile sums ([B][ssim_stride]), summed in an order fixed by its own frame count.  log_first: columns 1..3 of frames_ws hold the
+// log-domain inner products (k_handler_frames); 0: the linear ones (k_score_frames)
+__global__ __launch_bounds__(256) void k_handler_final(const double* __restrict__ frames_ws, int T, const int* __restrict__ frames,
+                                                       const double* __restrict__ ssim_ws, int64_t ssim_stride, int F, int log_first,
+                                                       double* __restrict__ out) {
+  __shared__ double red[7][kWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int rows = frames[b];
+  double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int t = tid; t < rows; t += 256) {
+    const double* w = frames_ws + ((int64_t)b * T + t) * 7;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) v[k] += w[k];
+  }
+  block_sum<7>(v, red);
+  const int Ho = rows - kSsimHalo, Wo = F - kSsimHalo;
+  const int n = (Ho + kSsimTileH - 1) / kSsimTileH * ((Wo + kSsimTileW - 1) / kSsimTileW);
+  double q[1] = {0.0};
+  for (int i = tid; i < n; i += 256) q[0] += ssim_ws[(int64_t)b * ssim_stride + i];
+  block_sum<1>(q, red);
+  if (tid == 0) {
+    double* o = out + (int64_t)b * VFX_N_HANDLER_METRICS;
+    const double a = sispec_db(v[1], v[2], v[3]), c = sispec_db(v[4], v[5], v[6]);
+    o[0] = v[0] / (double)rows;
+    o[1] = log_first ? a : c;
+    o[2] = log_first ? c : a;
+    o[3] = q[0] / ((double)Ho * (double)Wo);
   }
 }
 
@@ -269,6 +348,32 @@ void launch_ssim_tiles(const float* est, const float* tgt, int B, int T, int F, 
 void launch_score_final(const ScoreFinalArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL(k_score_final, dim3(B), dim3(256), 0, s, a);
   VFX_HIP(hipGetLastError());
+}
+
+static size_t handler_frames_bytes(int B, int T) { return ((size_t)B * T * 7 * sizeof(double) + 255) / 256 * 256; }
+
+size_t handler_metrics_ws_bytes(int B, int T) { return handler_frames_bytes(B, T) + (size_t)B * ssim_tiles(T, 128) * sizeof(double); }
+
+static void launch_handler_tail(const float* img, const float* tgt, int B, int T, const int* frames, char* ws, int log_first, double* out,
+                                hipStream_t s) {
+  double* const fr = reinterpret_cast<double*>(ws);
+  double* const ss = reinterpret_cast<double*>(ws + handler_frames_bytes(B, T));
+  launch_ssim_tiles(img, tgt, B, T, 128, frames, ss, s);
+  hipLaunchKernelGGL(k_handler_final, dim3(B), dim3(256), 0, s, fr, T, frames, ss, (int64_t)ssim_tiles(T, 128), 128, log_first, out);
+  VFX_HIP(hipGetLastError());
+}
+
+void launch_handler_metrics(const float* lg, const float* den, const float* tgt, int B, int T, const int* frames, char* ws, double* out,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(k_handler_frames, dim3((T + kWaves - 1) / kWaves, B), dim3(256), 0, s, lg, den, tgt, T, frames,
+                     reinterpret_cast<double*>(ws));
+  VFX_HIP(hipGetLastError());
+  launch_handler_tail(den, tgt, B, T, frames, ws, 1, out, s);
+}
+
+void launch_mel_metrics(const float* est, const float* tgt, int B, int T, const int* frames, char* ws, double* out, hipStream_t s) {
+  launch_score_frames(est, tgt, B, T, 128, frames, reinterpret_cast<double*>(ws), s);
+  launch_handler_tail(est, tgt, B, T, frames, ws, 0, out, s);
 }
 
 }  // namespace vfx

@@ -351,33 +351,41 @@ void launch_voc_final(const float* x, int x_f16, int B, int T, int C, const floa
 // ---------------------------------------------------------------------------------------------
 // handler() glue
 // ---------------------------------------------------------------------------------------------
-// from_log (pytorch_util.py:161-163): 10 ** min(x, 5).  With `sums` != null also accumulates the
-// per-clip energy of mel bins 5..24 of the estimate and of the input (amp_to_original_f,
-// tools/utils.py:50-55): sums[2b] += est, sums[2b+1] += target.
-// lens_t != nullptr (batches of clips of unequal length): only the lens_t[b] frames clip b really has count for its energies
-__global__ void k_from_log(const float* __restrict__ logmel, const float* __restrict__ mel_in, int T, int64_t total,
-                           float* __restrict__ sums, float* __restrict__ mel_out, const int* __restrict__ lens_t) {
+// from_log (pytorch_util.py:161-163): 10 ** min(x, 5).
+__global__ void k_from_log(const float* __restrict__ logmel, int64_t total, float* __restrict__ mel_out) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx < total) mel_out[idx] = from_log_value(logmel[idx]);
+}
+
+// The per-clip energies of amp_to_original_f (tools/utils.py:50-55): sums[2b] = the estimate's from_log over mel bins 5..24, sums[2b+1] =
+// the input's, over the clip's frames (lens_t[b], or all T).  One workgroup per clip, every thread a fixed stride of the clip's own
+// (frame, bin) pairs, then a fixed tree: the two sums depend on the clip alone -- not on the batch, the launch or the run, so everything
+// behind the scale can be compared bit for bit (a float atomicAdd per element would add them in an order that changes per launch).
+__global__ __launch_bounds__(256) void k_unify_sums(const float* __restrict__ logmel, const float* __restrict__ mel_in, int T,
+                                                    float* __restrict__ sums, const int* __restrict__ lens_t) {
+  __shared__ float red[2][4];
+  const int b = blockIdx.x;
+  const int n = (lens_t ? lens_t[b] : T) * 20;
   float e = 0.f, g = 0.f;
-  int64_t b = 0;
-  if (idx < total) {
-    const float v = exp10f(fminf(logmel[idx], 5.f));
-    mel_out[idx] = v;
-    const int f = idx & 127;
-    b = (idx >> 7) / T;
-    const int t = (int)((idx >> 7) - b * T);
-    if (sums && f >= 5 && f < 25 && (!lens_t || t < lens_t[b])) {
-      e = v;
-      g = mel_in[idx];
-    }
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int t = i / 20, f = 5 + i - t * 20;
+    const int64_t o = ((int64_t)b * T + t) * 128 + f;
+    e += from_log_value(logmel[o]);
+    g += mel_in[o];
   }
-  if (sums) {
-    // a block may straddle two clips only at a clip boundary; keep it simple: per-lane atomics
-    // are restricted to the 20 contributing bins.
-    if (e != 0.f || g != 0.f) {
-      atomicAdd(sums + 2 * b, e);
-      atomicAdd(sums + 2 * b + 1, g);
-    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    e += __shfl_xor(e, o);
+    g += __shfl_xor(g, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = e;
+    red[1][threadIdx.x >> 6] = g;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sums[2 * b] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    sums[2 * b + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
   }
 }
 
@@ -391,9 +399,8 @@ __global__ void k_scale_by_ratio(float* __restrict__ mel, int T, int64_t total, 
 void launch_from_log(const float* logmel, const float* mel_in, int B, int T, int unify, float* sums, float* mel_out,
                      hipStream_t s, const int* lens_t) {
   const int64_t total = (int64_t)B * T * 128;
-  if (unify) VFX_HIP(hipMemsetAsync(sums, 0, sizeof(float) * 2 * B, s));
-  hipLaunchKernelGGL(k_from_log, dim3(nblocks(total, 256)), dim3(256), 0, s, logmel, mel_in, T, total,
-                     unify ? sums : nullptr, mel_out, lens_t);
+  if (unify) hipLaunchKernelGGL(k_unify_sums, dim3(B), dim3(256), 0, s, logmel, mel_in, T, sums, lens_t);
+  hipLaunchKernelGGL(k_from_log, dim3(nblocks(total, 256)), dim3(256), 0, s, logmel, total, mel_out);
   if (unify) hipLaunchKernelGGL(k_scale_by_ratio, dim3(nblocks(total, 256)), dim3(256), 0, s, mel_out, T, total, sums);
   VFX_HIP(hipGetLastError());
 }

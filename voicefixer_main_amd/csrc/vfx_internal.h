@@ -147,7 +147,8 @@ enum LensRow {
   LENS_SCORE_SAMPLES = 10, LENS_SCORE_FRAMES = 11,                     // samples / frames of the vfx_audio_metrics sub-batch in flight
   LENS_LOWPASS_SAMPLES = 12, LENS_LOWPASS_CUT = 13,                    // samples / cut-off bin of the vfx_stft_lowpass sub-batch in flight
   LENS_STOI_SAMPLES = 14, LENS_STOI_OUT = 15, LENS_STOI_FRAMES = 16,   // input samples / 10 kHz samples / frames of the vfx_stoi sub-batch in flight
-  kLensRows = 17
+  LENS_TARGET_SAMPLES = 17,                                            // samples of the targets of a vfx_restore_*_varlen_scored call
+  kLensRows = 18
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -454,6 +455,8 @@ void launch_peak_trim_varlen(const float* wav_long, int B, int64_t Llong, int L,
                              const float* peak, float* out, hipStream_t s, int* flags);
 void launch_from_log(const float* logmel, const float* mel_in, int B, int T, int unify, float* sums, float* mel_out,
                      hipStream_t s, const int* lens_t = nullptr);
+// from_log of one value (pytorch_util.py:161-163): the one expression behind k_from_log and the handler scores of score.hip
+__device__ __forceinline__ float from_log_value(float logmel) { return exp10f(fminf(logmel, 5.f)); }
 // peak (device, [B]): each clip's peak as the vocoder tail left it; flags: VFX_FLAG_PEAK_NORMALISED when a clip was divided by its peak
 void launch_peak_trim(const float* wav_long, int B, int64_t Llong, int L, const float* peak, float* out, hipStream_t s,
                       int* flags = nullptr);
@@ -484,6 +487,16 @@ void launch_score_frames(const float* est, const float* tgt, int B, int T, int F
 // ws [B][ssim_tiles(T, F)]
 void launch_ssim_tiles(const float* est, const float* tgt, int B, int T, int F, const int* frames, double* ws, hipStream_t s);
 void launch_score_final(const ScoreFinalArgs& a, int B, hipStream_t s);
+// The four mel scores a handler writes per file (eval_gsr_voicefixer.py:59-64, eval_ssr_unet.py:116-126) for (B, T, 128) images, clip b =
+// its first frames[b] rows (device, >= 7): out (B, VFX_N_HANDLER_METRICS) = mel-lsd, mel-sispec, mel-non-log-sispec, mel-ssim.
+// ws: handler_metrics_ws_bytes(B, T) bytes, 256-byte aligned (the per-frame sums, then the SSIM tile sums).
+//   launch_handler_metrics  the GSR handler's operand mix: lg = the model's log10 estimate, den = what the vocoder receives, tgt = the
+//                           target's linear mel (k_handler_frames, k_ssim_tiles on (den, tgt), k_handler_final)
+//   launch_mel_metrics      the SSR handler's: all four of (est, tgt) (k_score_frames, k_ssim_tiles, k_handler_final)
+size_t handler_metrics_ws_bytes(int B, int T);
+void launch_handler_metrics(const float* lg, const float* den, const float* tgt, int B, int T, const int* frames, char* ws, double* out,
+                            hipStream_t s);
+void launch_mel_metrics(const float* est, const float* tgt, int B, int T, const int* frames, char* ws, double* out, hipStream_t s);
 int64_t count_nonfinite(const float* p, int64_t n, hipStream_t s);  // debug aid, synchronises
 
 // stft_dft.hip: the front end of the scores at 16 kHz (vfx_audio_metrics_rate): |STFT| with n_fft 743, hop 160 as a DFT-matrix GEMM on

@@ -908,6 +908,39 @@ class Engine:
         _lib.check(self.lib.vfx_restore_ssr_varlen(self.h, _ptr(wav), B, L, arr, _ptr(out), self._stream()), "vfx_restore_ssr_varlen")
         return out
 
+    def _scored_args(self, target, target_lengths, B, L, name):
+        """The target half of the two scored entries -> (target on the device or None, its lengths as the C int array or None)."""
+        if target is not None:
+            target = _dev_f32(target, self.device)
+            target = target[None] if target.dim() == 1 else target
+            if tuple(target.shape) != (B, L):
+                raise ValueError("%s: target %s must have the shape of wav, (%d, %d)" % (name, tuple(target.shape), B, L))
+        return target, self._lens_arg(target_lengths, B, name)
+
+    def restore_gsr_varlen_scored(self, wav, lengths, target, target_lengths=None, unify_energy=False, want_logmel=False, out=None):
+        """restore_gsr_varlen with the clips' targets (vfx_restore_gsr_varlen_scored): target (B, Lmax), clip b of it = its first
+        target_lengths[b] samples (default: lengths) -> (restored (B, Lmax), scores (B, 4) float64 on the device[, logmel]).  The
+        restored clips and the log-mel are those of restore_gsr_varlen bit for bit; the columns are models.HANDLER_METRIC_KEYS'
+        order: mel-lsd, mel-sispec, mel-non-log-sispec, mel-ssim (eval_gsr_voicefixer.py:56-64), per clip over its own frames."""
+        wav, B, L, arr, out = self._varlen_args(wav, lengths, out, "restore_gsr_varlen_scored")
+        target, tarr = self._scored_args(target, target_lengths, B, L, "restore_gsr_varlen_scored")
+        logmel = torch.empty((B, self.frames(L), N_MELS), device=self.device, dtype=torch.float32) if want_logmel else None
+        scores = torch.empty((B, _lib.N_HANDLER_METRICS), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_restore_gsr_varlen_scored(self.h, _ptr(wav), _ptr(target), B, L, arr, tarr, _ptr(out), _ptr(logmel),
+                                                          _ptr(scores), int(bool(unify_energy)), self._stream()),
+                   "vfx_restore_gsr_varlen_scored")
+        return (out, scores, logmel) if want_logmel else (out, scores)
+
+    def restore_ssr_varlen_scored(self, wav, lengths, target, target_lengths=None, out=None):
+        """restore_ssr_varlen with the clips' targets (vfx_restore_ssr_varlen_scored; eval_ssr_unet.py:116-126) -> (restored (B, Lmax),
+        scores (B, 4) float64 on the device, the same columns)."""
+        wav, B, L, arr, out = self._varlen_args(wav, lengths, out, "restore_ssr_varlen_scored")
+        target, tarr = self._scored_args(target, target_lengths, B, L, "restore_ssr_varlen_scored")
+        scores = torch.empty((B, _lib.N_HANDLER_METRICS), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_restore_ssr_varlen_scored(self.h, _ptr(wav), _ptr(target), B, L, arr, tarr, _ptr(out), _ptr(scores),
+                                                          self._stream()), "vfx_restore_ssr_varlen_scored")
+        return out, scores
+
     def check_negative_input(self):
         """`to_log`'s assert alone (pytorch_util.py:158): reads and clears ONLY the negative-input bit -- a saturation bit a
         deferred vocoder check still has to see stays raised."""
@@ -946,6 +979,13 @@ class Engine:
         """restore_gsr_varlen + check_flags (cf. restore_gsr_checked)."""
         res = self.restore_gsr_varlen(wav, lengths, unify_energy=unify_energy, out=out)
         again = self.check_flags(lambda e: e.restore_gsr_varlen(wav, lengths, unify_energy=unify_energy, out=out))
+        return res if again is None else again
+
+    def restore_gsr_varlen_scored_checked(self, wav, lengths, target, target_lengths=None, unify_energy=False, out=None):
+        """restore_gsr_varlen_scored + check_flags: a batch the 16-bit vocoder clamped is restored AND scored again on the strict twin."""
+        res = self.restore_gsr_varlen_scored(wav, lengths, target, target_lengths, unify_energy=unify_energy, out=out)
+        again = self.check_flags(lambda e: e.restore_gsr_varlen_scored(wav, lengths, target, target_lengths, unify_energy=unify_energy,
+                                                                       out=out))
         return res if again is None else again
 
     def vocoder_checked(self, mel_linear):
@@ -1225,6 +1265,27 @@ class Engine:
         out = torch.empty(B, device=self.device, dtype=torch.float64)
         _lib.check(_lib.load_test().vfx_op_ssim(self.h, _ptr(est), _ptr(target), B, T, F, (ctypes.c_int * B)(*rows), _ptr(out),
                                                 self._stream()), "vfx_op_ssim")
+        return out
+
+    def op_handler_metrics(self, logmel, den, target_mel, frames=None):
+        """The scoring launches of restore_gsr_varlen_scored alone (vfx_op_handler_metrics): (B, T, 128) images -- the log10 estimate, what
+        the vocoder receives, the target's linear mel --, clip b = their first frames[b] rows -> (B, 4) float64."""
+        logmel, den, target_mel = (_dev_f32(t, self.device) for t in (logmel, den, target_mel))
+        B, T, _ = logmel.shape
+        frames = _clip_rows(logmel[:, :, 0], frames, "op_handler_metrics")[4]
+        out = torch.full((B, _lib.N_HANDLER_METRICS), float("nan"), device=self.device, dtype=torch.float64)
+        _lib.check(_lib.load_test().vfx_op_handler_metrics(self.h, _ptr(logmel), _ptr(den), _ptr(target_mel), B, T,
+                                                           (ctypes.c_int * B)(*frames), _ptr(out), self._stream()), "vfx_op_handler_metrics")
+        return out
+
+    def op_mel_metrics(self, est_mel, target_mel, frames=None):
+        """The scoring launches of restore_ssr_varlen_scored alone (vfx_op_mel_metrics): the same four scores of (est_mel, target_mel)."""
+        est_mel, target_mel = _dev_f32(est_mel, self.device), _dev_f32(target_mel, self.device)
+        B, T, _ = est_mel.shape
+        frames = _clip_rows(est_mel[:, :, 0], frames, "op_mel_metrics")[4]
+        out = torch.full((B, _lib.N_HANDLER_METRICS), float("nan"), device=self.device, dtype=torch.float64)
+        _lib.check(_lib.load_test().vfx_op_mel_metrics(self.h, _ptr(est_mel), _ptr(target_mel), B, T, (ctypes.c_int * B)(*frames),
+                                                       _ptr(out), self._stream()), "vfx_op_mel_metrics")
         return out
 
     def op_sisdr(self, est, target, lengths=None):

@@ -315,6 +315,51 @@ def _resample_list(engine, wavs, sample_rate):
     return clips.unpad(y, out_lengths, to_host=False)
 
 
+# the keys of the dict a handler returns for a file with a target (eval_gsr_voicefixer.py:59-64, eval_ssr_unet.py:121-126), in the
+# column order of Engine.restore_gsr_varlen_scored / restore_ssr_varlen_scored
+HANDLER_METRIC_KEYS = ("mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim")
+MIN_SCORED_SAMPLES = 6 * 441   # 7 STFT frames: skimage's 7 x 7 SSIM refuses a smaller mel image
+
+
+def _restore_scored_list(engine, call, wavs, targets, max_batch, bucket_key, bucket_len, name):
+    """The list layer of the two restore_scored_list methods: clips and their targets sorted by length (longest first, as
+    dist.restore_sharded_lengths orders restore_list's), up to `max_batch` of one `bucket_key` per call, both padded to
+    `bucket_len(longest)`; `call(x, lengths, t, target_lengths)` -> (restored (B, Lmax), scores (B, 4) on the device).  ONE
+    device-to-host copy of the (B, 4) block per batch.  -> (restored clips, [{key: score}]) in input order."""
+    from . import dist as vdist
+    if vdist.world_rank()[0] > 1:
+        raise RuntimeError("%s: scored sets are restored by one process (a process group of %d ranks is initialised)"
+                           % (name, vdist.world_rank()[0]))
+    if len(wavs) != len(targets):
+        raise ValueError("%s: %d clips and %d targets" % (name, len(wavs), len(targets)))
+    hop = engine.hop
+    lengths = [int(w.shape[-1]) for w in wavs]
+    tlens = [int(t.shape[-1]) for t in targets]
+    for i, (n, m) in enumerate(zip(lengths, tlens)):
+        if n < MIN_SCORED_SAMPLES:
+            raise ValueError("%s: clip %d has %d samples: the scores need at least %d (7 STFT frames)" % (name, i, n, MIN_SCORED_SAMPLES))
+        if n // hop != m // hop:
+            raise ValueError("%s: clip %d has %d frames but its target has %d" % (name, i, n // hop + 1, m // hop + 1))
+    buckets = {}
+    for i, n in enumerate(lengths):
+        buckets.setdefault(bucket_key(n), []).append(i)
+    restored, scores = [None] * len(wavs), [None] * len(wavs)
+    for k in sorted(buckets, reverse=True):
+        idx = sorted(buckets[k], key=lambda i: (-lengths[i], i))
+        for a in range(0, len(idx), max_batch):
+            chunk = idx[a:a + max_batch]
+            lens, tl = [lengths[i] for i in chunk], [tlens[i] for i in chunk]
+            width = bucket_len(max(lens))
+            x = clips.pad([wavs[i].reshape(-1) for i in chunk], engine.device, torch.float32, width=width)
+            t = clips.pad([targets[i].reshape(-1) for i in chunk], engine.device, torch.float32, width=width)
+            out, block = call(x, lens, t, tl)
+            block = block.cpu().tolist()     # the batch's one device-to-host copy of scores
+            for j, i in enumerate(chunk):
+                restored[i] = out[j, :lengths[i]]
+                scores[i] = {key: float(v) for key, v in zip(HANDLER_METRIC_KEYS, block[j])}
+    return restored, scores
+
+
 class _Base:
     def __init__(self, hp=None, channels=1, type_target="vocals", device="cuda:0", engine=None):
         self.hp = hp
@@ -502,6 +547,21 @@ class VoiceFixer(_Base):
         return vdist.restore_sharded_lengths(fn, wavs, self.device, max_batch=max_batch)
 
 
+    def restore_scored_list(self, wavs, targets, unify_energy=False, max_batch=128):
+        """restore_list for a test set WITH targets (every reference test list is `source target` pairs): lists of 1-D clips at
+        44.1 kHz -> (restored clips, [{"mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"} per clip]) in input order -- the
+        clips restore_list gives, and for each the dict handler() returns for that file (eval_gsr_voicefixer.py:56-64), scored on
+        the device inside the batched call (Engine.restore_gsr_varlen_scored) instead of one segment per call with four
+        device-to-host copies each.  A target must have its clip's frame count (len // 441) and a clip at least 2646 samples.
+        Single process: raises when a process group of more than one rank is initialised."""
+        eng = self.engine
+        if not eng.supports_varlen():
+            raise RuntimeError("restore_scored_list: this engine cannot run padded batches (Engine.supports_varlen)")
+        call = lambda x, lens, t, tl: eng.restore_gsr_varlen_scored_checked(x, lens, t, tl, unify_energy=unify_energy)
+        return _restore_scored_list(eng, call, wavs, targets, max_batch, lambda L: 0, lambda L: eng.padded_frames(L) * eng.hop - 1,
+                                    "VoiceFixer.restore_scored_list")
+
+
 class SSR_UNet(_Base):
     """models/ssr_unet.py:56-155 / models/gsr_unet.py (identical inference surface): the
     spectrogram-domain ResUNet of models/components/unet_v2.py."""
@@ -543,6 +603,15 @@ class SSR_UNet(_Base):
         fn.bucket_key = eng.padded_frames
         fn.bucket_len = lambda L: eng.padded_frames(L) * eng.hop - 1      # one plan per (B, bucket), cf. dist.checked_restore
         return vdist.restore_sharded_lengths(fn, wavs, self.device, max_batch=max_batch)
+
+
+    def restore_scored_list(self, wavs, targets, max_batch=16):
+        """restore_list for a test set with targets: -> (restored clips, [{"mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"}
+        per clip]) in input order, the dict handler_ssr_unet's reference returns per file (eval_ssr_unet.py:116-126), scored inside
+        the batched call (Engine.restore_ssr_varlen_scored).  Clips at 44.1 kHz; single process (cf. VoiceFixer.restore_scored_list)."""
+        eng = self.engine
+        return _restore_scored_list(eng, eng.restore_ssr_varlen_scored, wavs, targets, max_batch, eng.padded_frames,
+                                    lambda L: eng.padded_frames(L) * eng.hop - 1, "SSR_UNet.restore_scored_list")
 
 
 GSR_UNet = SSR_UNet
