@@ -135,6 +135,29 @@ int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, int B, int H,
 int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches, int cap,
                         int* nlaunch);
 
+/* The bi_gru / dnn analysis plans' launches (analysis.hip: k_dense, k_gru_seq), one PIECE at a time, for
+ * tests/test_gpu_analysis_launches.py.  The piece is appended to a plan of its own by the member of the plan builder that vfx_analysis_mel
+ * runs (build_analysis_piece -> AnalysisBuilder::lin1, proj, gru, lin4, lin6, fc), with the handle's own packed weights of `model`
+ * (VFX_MODEL_GRU_MEL / VFX_MODEL_DNN_MEL, finalized).  The plan is bound to the handle's arena, filled with NaN patterns, given the
+ * caller's inputs, run and synchronised.  Tensors on the device, (B, T, C) rows of fp32:
+ *   model    piece            input(s)                               output
+ *   GRU_MEL  "lin1"           (B, T, 128) linear mel                 (B, T, 256)    to_log + BN 0 -> Linear 1 -> BN 2.bn
+ *            "proj0"          (B, T, 256)                            (B, T, 1536)   both directions' W_ih x + b_ih + (b_hr, b_hz, 0)
+ *            "gru0", "gru1"   (B, T, 1536)                           (B, T, 512)    k_gru_seq of layer 0 / 1: [forward | backward]
+ *            "proj1"          (B, T, 512)                            (B, T, 1536)
+ *            "lin4"           (B, T, 512)                            (B, T, 256)    ReLU -> Linear 4 -> ReLU
+ *            "lin6"           (B, T, 256), (B, T, 128) linear mel    (B, T, 128)    Linear 6 + to_log(mel)
+ *   DNN_MEL  "fc0"            (B, T, 128) linear mel                 (B, T, 256)    to_log -> Linear 0 -> ReLU -> BN 2
+ *            "fc1" .. "fc3"   (B, T, 256 | 512 | 1024)               (B, T, 512 | 1024 | 512)   Linear -> ReLU -> BN
+ *            "fc4"            (B, T, 512)                            (B, T, 256)    Linear 12 -> ReLU
+ *            "fc5"            (B, T, 256), (B, T, 128) linear mel    (B, T, 128)    Linear 14 + to_log(mel)
+ * in: HOST array of nin device pointers, in_n the float count of each; out_n that of out -- checked against the plan's buffers, a
+ * mismatch fails the call.  lens: NULL or HOST int[B], 1 <= lens[b] <= T, B <= 1024: frames per clip, put on the device as
+ * vfx_analysis_mel does; rows at and past lens[b] are zero in out and never read from the inputs.  A negative mel value read by
+ * "lin1" / "fc0" raises VFX_FLAG_NEGATIVE_INPUT in the handle's flag word. */
+int vfx_op_analysis_piece(vfx_handle* h, int model, const char* piece, int B, int T, const int* lens, const float* const* in,
+                          const int64_t* in_n, int nin, float* out, int64_t out_n, void* stream);
+
 /* The STFT / ISTFT front end (stft.hip) and the glue launches between the models of a restore call (small_ops.hip), ONE launcher each
  * with the handle's own tables, for tests/test_gpu_frontend_launches.py.  Tensors on the device, per-clip lengths HOST int[B] or NULL;
  * every call synchronises.

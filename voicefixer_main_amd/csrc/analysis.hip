@@ -369,69 +369,153 @@ std::shared_ptr<AnalysisWeights> build_analysis_weights(vfx_handle* h, int model
 // ---------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------
-void build_analysis_mel(PlanBuilder& pb, int model, int B, int T, BufRef mel_linear, BufRef logmel_out) {
-  const AnalysisWeights* W = pb.h->analysis[model - VFX_MODEL_GRU_MEL].get();
-  VFX_CHECK(W, "analysis module %d: weights are not finalized", model);
-  const int64_t M = (int64_t)B * T;
+static BufRef arena_ref(size_t off) {
+  BufRef b;
+  b.off = off;
+  return b;
+}
+
+// one Linear: src / dst / mel are BufRefs (caller's tensors or arena slices)
+void AnalysisBuilder::dense(const DenseW& d, BufRef src, BufRef dst, int in_log, float in_scale, float in_shift, int in_relu,
+                            int out_relu, float out_scale, float out_shift, bool resid, BufRef mel) {
   Plan* pl = pb.plan;
   const int* lens_t = pb.lens_t;
+  const int64_t M = (int64_t)B * T;
+  const int T_ = T;
   auto res = [pl](const RunCtx& c, const BufRef& b) {
     return b.ext ? c.ext[b.slot] : reinterpret_cast<float*>(pl->bound_base + b.off);
   };
-  // one Linear: src / dst are BufRefs (caller's tensors or arena slices)
-  auto dense = [&](const DenseW& d, BufRef src, BufRef dst, int in_log, float in_scale, float in_shift, int in_relu, int out_relu,
-                   float out_scale, float out_shift, bool resid) {
-    pl->ops.push_back([=](const RunCtx& c) {
-      DenseArgs a{};
-      a.x = res(c, src);
-      a.wT = d.wT;
-      a.bias = d.bias;
-      a.resid = resid ? res(c, mel_linear) : nullptr;
-      a.y = res(c, dst);
-      a.lens_t = lens_t;
-      a.flags = c.flags;
-      a.M = M;
-      a.K = d.K;
-      a.N = d.N;
-      a.T = T;
-      a.in_log = in_log;
-      a.in_relu = in_relu;
-      a.out_relu = out_relu;
-      a.in_scale = in_scale;
-      a.in_shift = in_shift;
-      a.out_scale = out_scale;
-      a.out_shift = out_shift;
-      launch_dense(a, c.stream);
-    });
+  pl->ops.push_back([=](const RunCtx& c) {
+    DenseArgs a{};
+    a.x = res(c, src);
+    a.wT = d.wT;
+    a.bias = d.bias;
+    a.resid = resid ? res(c, mel) : nullptr;
+    a.y = res(c, dst);
+    a.lens_t = lens_t;
+    a.flags = c.flags;
+    a.M = M;
+    a.K = d.K;
+    a.N = d.N;
+    a.T = T_;
+    a.in_log = in_log;
+    a.in_relu = in_relu;
+    a.out_relu = out_relu;
+    a.in_scale = in_scale;
+    a.in_shift = in_shift;
+    a.out_scale = out_scale;
+    a.out_shift = out_shift;
+    launch_dense(a, c.stream);
+  });
+}
+
+void AnalysisBuilder::lin1(BufRef mel, BufRef out) {  // to_log -> BN 0 -> Linear 1 -> BN_GRU.bn
+  dense(W.dense[0], mel, out, 1, W.bn_scale[0], W.bn_shift[0], 0, 0, W.bn_scale[1], W.bn_shift[1], false, mel);
+}
+void AnalysisBuilder::proj(int layer, BufRef src, BufRef xp) {
+  dense(W.dense[1 + layer], src, xp, 0, 1.f, 0.f, 0, 0, 1.f, 0.f, false, src);
+}
+void AnalysisBuilder::gru(int layer, BufRef xp, BufRef out) {
+  Plan* pl = pb.plan;
+  const int* lens_t = pb.lens_t;
+  const float* whhT = W.whhT[layer];
+  const float* bhn = W.bhn[layer];
+  const int B_ = B, T_ = T;
+  auto res = [pl](const RunCtx& c, const BufRef& b) {
+    return b.ext ? c.ext[b.slot] : reinterpret_cast<float*>(pl->bound_base + b.off);
   };
-  auto arena = [](size_t off) {
-    BufRef b;
-    b.off = off;
+  pl->ops.push_back([=](const RunCtx& c) { launch_gru_seq(res(c, xp), B_, T_, lens_t, whhT, bhn, res(c, out), c.stream); });
+}
+void AnalysisBuilder::lin4(BufRef src, BufRef out) {  // ReLU -> Linear 4 -> ReLU
+  dense(W.dense[3], src, out, 0, 1.f, 0.f, 1, 1, 1.f, 0.f, false, src);
+}
+void AnalysisBuilder::lin6(BufRef src, BufRef mel, BufRef out) {  // Linear 6, + to_log(mel)
+  dense(W.dense[4], src, out, 0, 1.f, 0.f, 0, 0, 1.f, 0.f, true, mel);
+}
+void AnalysisBuilder::fc(int i, BufRef src, BufRef mel, BufRef out) {
+  VFX_CHECK(i >= 0 && i < 6, "dnn: no layer %d", i);
+  dense(W.dense[i], src, out, i == 0 ? 1 : 0, 1.f, 0.f, 0, i < 5 ? 1 : 0, i < 4 ? W.bn_scale[i] : 1.f, i < 4 ? W.bn_shift[i] : 0.f,
+        i == 5, mel);
+}
+
+static const AnalysisWeights& analysis_weights(PlanBuilder& pb, int model) {
+  VFX_CHECK(model == VFX_MODEL_GRU_MEL || model == VFX_MODEL_DNN_MEL, "model %d is not an analysis module", model);
+  const AnalysisWeights* W = pb.h->analysis[model - VFX_MODEL_GRU_MEL].get();
+  VFX_CHECK(W, "analysis module %d: weights are not finalized", model);
+  return *W;
+}
+
+void build_analysis_mel(PlanBuilder& pb, int model, int B, int T, BufRef mel_linear, BufRef logmel_out) {
+  AnalysisBuilder ab{pb, analysis_weights(pb, model), B, T};
+  const int64_t M = (int64_t)B * T;
+  if (model == VFX_MODEL_GRU_MEL) {
+    const BufRef a256 = arena_ref(pb.alloc_f(M * 256)), xp = arena_ref(pb.alloc_f(M * 1536)), h1 = arena_ref(pb.alloc_f(M * 512)),
+                 h2 = arena_ref(pb.alloc_f(M * 512));
+    ab.lin1(mel_linear, a256);
+    ab.proj(0, a256, xp);
+    ab.gru(0, xp, h1);
+    ab.proj(1, h1, xp);
+    ab.gru(1, xp, h2);
+    ab.lin4(h2, a256);
+    ab.lin6(a256, mel_linear, logmel_out);
+  } else {
+    const BufRef p = arena_ref(pb.alloc_f(M * 1024)), q = arena_ref(pb.alloc_f(M * 1024));
+    ab.fc(0, mel_linear, mel_linear, p);
+    ab.fc(1, p, mel_linear, q);
+    ab.fc(2, q, mel_linear, p);
+    ab.fc(3, p, mel_linear, q);
+    ab.fc(4, q, mel_linear, p);
+    ab.fc(5, p, mel_linear, logmel_out);
+  }
+}
+
+void build_analysis_piece(PlanBuilder& pb, int model, AnalysisPiece& pc) {
+  const std::string name = pc.name ? pc.name : "";
+  const int B = pc.B, T = pc.T;
+  VFX_CHECK(B > 0 && T > 0, "analysis piece: bad shape");
+  AnalysisBuilder ab{pb, analysis_weights(pb, model), B, T};
+  const int64_t M = (int64_t)B * T;
+  pc.nin = 0;
+  auto input = [&](int c) {
+    const BufRef b = arena_ref(pb.alloc_f(M * c));
+    pc.in_off[pc.nin] = b.off;
+    pc.in_n[pc.nin++] = M * c;
     return b;
   };
-  const auto& D = W->dense;
+  auto output = [&](int c) {
+    const BufRef b = arena_ref(pb.alloc_f(M * c));
+    pc.out_off = b.off;
+    pc.out_n = M * c;
+    return b;
+  };
   if (model == VFX_MODEL_GRU_MEL) {
-    const BufRef a256 = arena(pb.alloc_f(M * 256)), xp = arena(pb.alloc_f(M * 1536)), h1 = arena(pb.alloc_f(M * 512)),
-                 h2 = arena(pb.alloc_f(M * 512));
-    // to_log -> BN 0 -> Linear 1 -> BN_GRU.bn
-    dense(D[0], mel_linear, a256, 1, W->bn_scale[0], W->bn_shift[0], 0, 0, W->bn_scale[1], W->bn_shift[1], false);
-    for (int layer = 0; layer < 2; ++layer) {
-      dense(D[1 + layer], layer ? h1 : a256, xp, 0, 1.f, 0.f, 0, 0, 1.f, 0.f, false);
-      const float* whhT = W->whhT[layer];
-      const float* bhn = W->bhn[layer];
-      const BufRef out = layer ? h2 : h1;
-      pl->ops.push_back([=](const RunCtx& c) { launch_gru_seq(res(c, xp), B, T, lens_t, whhT, bhn, res(c, out), c.stream); });
+    if (name == "lin1") {
+      const BufRef mel = input(128);
+      ab.lin1(mel, output(256));
+    } else if (name == "proj0" || name == "proj1") {
+      const int layer = name[4] - '0';
+      const BufRef src = input(layer ? 512 : 256);
+      ab.proj(layer, src, output(1536));
+    } else if (name == "gru0" || name == "gru1") {
+      const BufRef xp = input(1536);
+      ab.gru(name[3] - '0', xp, output(512));
+    } else if (name == "lin4") {
+      const BufRef src = input(512);
+      ab.lin4(src, output(256));
+    } else if (name == "lin6") {
+      const BufRef src = input(256), mel = input(128);
+      ab.lin6(src, mel, output(128));
+    } else {
+      VFX_CHECK(false, "analysis piece: bi_gru has no piece '%s'", name.c_str());
     }
-    dense(D[3], h2, a256, 0, 1.f, 0.f, 1, 1, 1.f, 0.f, false);                 // ReLU -> Linear 4 -> ReLU
-    dense(D[4], a256, logmel_out, 0, 1.f, 0.f, 0, 0, 1.f, 0.f, true);         // Linear 6, + to_log(mel)
   } else {
-    const BufRef p = arena(pb.alloc_f(M * 1024)), q = arena(pb.alloc_f(M * 1024));
-    dense(D[0], mel_linear, p, 1, 1.f, 0.f, 0, 1, W->bn_scale[0], W->bn_shift[0], false);
-    dense(D[1], p, q, 0, 1.f, 0.f, 0, 1, W->bn_scale[1], W->bn_shift[1], false);
-    dense(D[2], q, p, 0, 1.f, 0.f, 0, 1, W->bn_scale[2], W->bn_shift[2], false);
-    dense(D[3], p, q, 0, 1.f, 0.f, 0, 1, W->bn_scale[3], W->bn_shift[3], false);
-    dense(D[4], q, p, 0, 1.f, 0.f, 0, 1, 1.f, 0.f, false);
-    dense(D[5], p, logmel_out, 0, 1.f, 0.f, 0, 0, 1.f, 0.f, true);
+    const int width[7] = {128, 256, 512, 1024, 512, 256, 128};
+    VFX_CHECK(name.size() == 3 && name.compare(0, 2, "fc") == 0 && name[2] >= '0' && name[2] <= '5',
+              "analysis piece: dnn has no piece '%s'", name.c_str());
+    const int i = name[2] - '0';
+    const BufRef src = input(width[i]);
+    const BufRef mel = i == 5 ? input(128) : src;
+    ab.fc(i, src, mel, output(width[i + 1]));
   }
 }
 

@@ -934,6 +934,52 @@ extern "C" int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, in
   return 0;
 }
 
+// ---- the bi_gru / dnn plans' launches, one at a time, built by the plan's own builder (analysis.hip: build_analysis_piece) -------------
+extern "C" int vfx_op_analysis_piece(vfx_handle* h, int model, const char* piece, int B, int T, const int* lens, const float* const* in,
+                                     const int64_t* in_n, int nin, float* out, int64_t out_n, void* stream) {
+  try {
+    VFX_CHECK(h && piece && in && in_n && out && B > 0 && T > 0 && (model == VFX_MODEL_GRU_MEL || model == VFX_MODEL_DNN_MEL),
+              "vfx_op_analysis_piece: bad argument");
+    VFX_CHECK(h->analysis[model - VFX_MODEL_GRU_MEL], "vfx_op_analysis_piece: the weights of model %d are not finalized", model);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Plan plan;
+    PlanBuilder pb{h, &plan, {}};
+    if (lens) {  // as vfx_analysis_mel_1: the handle's own row of frame counts, filled in stream order
+      VFX_CHECK(B <= kMaxVarlenClips, "vfx_op_analysis_piece: %d clips with frame counts (at most %d)", B, kMaxVarlenClips);
+      for (int b = 0; b < B; ++b)
+        VFX_CHECK(lens[b] >= 1 && lens[b] <= T, "vfx_op_analysis_piece: clip %d has %d frames (need 1 <= frames <= T = %d)", b, lens[b], T);
+      int* const d_f = h->lens_row(LENS_ANALYSIS_FRAMES);
+      launch_set_frames(d_f, lens, B, s);
+      pb.lens_t = d_f;
+    }
+    AnalysisPiece pc{};
+    pc.name = piece;
+    pc.B = B;
+    pc.T = T;
+    build_analysis_piece(pb, model, pc);
+    // the caller's tensors must be the plan's buffers element for element: nothing below copies by any other count
+    VFX_CHECK(nin == pc.nin, "vfx_op_analysis_piece: '%s' has %d inputs", piece, pc.nin);
+    for (int i = 0; i < nin; ++i)
+      VFX_CHECK(in[i] && in_n[i] == pc.in_n[i], "vfx_op_analysis_piece: input %d of '%s' has %lld floats", i, piece, (long long)pc.in_n[i]);
+    VFX_CHECK(out_n == pc.out_n, "vfx_op_analysis_piece: the output of '%s' has %lld floats", piece, (long long)pc.out_n);
+    plan.arena_bytes = pb.arena.high;
+    bind_plan(h, plan);
+    char* base = plan.bound_base;
+    // NaN patterns everywhere first (what the launch does not write stays NaN), then the inputs
+    VFX_HIP(hipMemsetAsync(base, 0xff, plan.arena_bytes, s));
+    for (int i = 0; i < nin; ++i)
+      VFX_HIP(hipMemcpyAsync(base + pc.in_off[i], in[i], (size_t)pc.in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RunCtx ctx{s, {}, h->d_flags, nullptr};
+    plan.run(ctx);
+    VFX_HIP(hipMemcpyAsync(out, base + pc.out_off, (size_t)pc.out_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VFX_HIP(hipStreamSynchronize(s));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}
+
 extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches,
                                    int cap, int* nlaunch) {
   try {

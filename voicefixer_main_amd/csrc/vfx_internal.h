@@ -1044,6 +1044,38 @@ int describe_unet_launches(const Plan& plan, int* out, int cap);
 void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_out, const BufRef* peak = nullptr);
 // bi_gru / dnn Generator.forward: linear mel (B,T,128) -> log-mel (B,T,128); pb.lens_t (frames per clip) or all T
 void build_analysis_mel(PlanBuilder& pb, int model, int B, int T, BufRef mel_linear, BufRef logmel_out);
+// The launches of those plans, one member each (analysis.hip): build_analysis_mel calls them in order, build_analysis_piece one of them.
+// Tensors are (B, T, C) rows, fp32; every member appends one launch over pb.lens_t (frames per clip) or all T.
+struct AnalysisBuilder {
+  PlanBuilder& pb;
+  const AnalysisWeights& W;
+  int B, T;
+  // bi_gru
+  void lin1(BufRef mel, BufRef out);              // to_log + BN 0 -> Linear 1 -> BN 2.bn: (., 128) linear mel -> (., 256)
+  void proj(int layer, BufRef src, BufRef xp);    // both directions' W_ih x + b_ih (+ b_hr, b_hz): (., 256 | 512) -> (., 1536)
+  void gru(int layer, BufRef xp, BufRef out);     // k_gru_seq: (., 1536) -> (., 512) = [forward | backward]
+  void lin4(BufRef src, BufRef out);              // ReLU -> Linear 4 -> ReLU: (., 512) -> (., 256)
+  void lin6(BufRef src, BufRef mel, BufRef out);  // Linear 6, + to_log(mel): (., 256) -> (., 128)
+  // dnn: layer i of 0..5 (Linear 3 i, or 14), widths 128, 256, 512, 1024, 512, 256, 128.  0: to_log in front; 0..4: ReLU behind, 0..3:
+  // then the BN; 5: + to_log(mel) (mel is read by layer 5 alone)
+  void fc(int i, BufRef src, BufRef mel, BufRef out);
+  // one k_dense launch; resid: y += to_log(mel)
+  void dense(const DenseW& d, BufRef src, BufRef dst, int in_log, float in_scale, float in_shift, int in_relu, int out_relu,
+             float out_scale, float out_shift, bool resid, BufRef mel);
+};
+// One launch of an analysis plan on its own, for libvfx_test.so (vfx_op_analysis_piece): appended by the AnalysisBuilder member that
+// build_analysis_mel runs, over input and output buffers of the piece's own in the arena, with pb's lens_t.  name: "lin1", "proj0",
+// "gru0", "proj1", "gru1", "lin4", "lin6" (VFX_MODEL_GRU_MEL), "fc0" .. "fc5" (VFX_MODEL_DNN_MEL); "lin6" and "fc5" have two inputs,
+// the second the linear mel.
+struct AnalysisPiece {
+  const char* name;
+  int B, T;
+  // filled by build_analysis_piece: arena byte offsets and float counts of the buffers
+  int nin;
+  size_t in_off[2], out_off;
+  int64_t in_n[2], out_n;
+};
+void build_analysis_piece(PlanBuilder& pb, int model, AnalysisPiece& piece);
 // d[0 .. B) = host[0 .. B) in stream order (kernel arguments: legal inside a stream capture); one row, unlike launch_set_lens
 void launch_set_frames(int* d, const int* host, int B, hipStream_t s);
 int64_t vocoder_out_len(const vfx_config& cfg, int T);

@@ -1257,6 +1257,24 @@ class Engine:
                                                         buf, 48, ctypes.byref(n)), "vfx_plan_unet_piece")
         return Engine._unet_launches(buf, min(n.value, 8))
 
+    # the bi_gru / dnn plans' launches, one at a time, built by the plan's own builder (include/vfx_test.h: vfx_op_analysis_piece)
+    ANALYSIS_PIECE_WIDTHS = {"lin1": 256, "proj0": 1536, "gru0": 512, "proj1": 1536, "gru1": 512, "lin4": 256, "lin6": 128,
+                             "fc0": 256, "fc1": 512, "fc2": 1024, "fc3": 512, "fc4": 256, "fc5": 128}
+
+    def op_analysis_piece(self, model, piece, inputs, lens=None):
+        """One launch of the analysis plan of `model` (MODEL_GRU_MEL: lin1, proj0, gru0, proj1, gru1, lin4, lin6; MODEL_DNN_MEL: fc0 ..
+        fc5) on device tensors (B, T, C) -> its output (B, T, C'), which starts as NaN.  inputs: one tensor, for lin6 / fc5 two (the
+        second the linear mel).  lens: frames per clip, as analysis_mel's `frames`."""
+        xs = [_dev_f32(x, self.device) for x in inputs]
+        B, T = xs[0].shape[:2]
+        out = torch.full((B, T, self.ANALYSIS_PIECE_WIDTHS[piece]), float("nan"), device=self.device)
+        pin = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+        nin = (ctypes.c_int64 * len(xs))(*[x.numel() for x in xs])
+        _lib.check(_lib.load_test().vfx_op_analysis_piece(
+            self.h, int(model), piece.encode(), B, T, self._lens_arg(lens, B, "op_analysis_piece"), pin, nin, len(xs), _ptr(out),
+            out.numel(), self._stream()), "vfx_op_analysis_piece")
+        return out
+
     def op_ssim(self, est, target, rows=None):
         """The SSIM kernels of audio_metrics alone: (B, T, F) images, image b = its first rows[b] rows -> (B,) float64."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
