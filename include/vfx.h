@@ -539,6 +539,29 @@ int vfx_audio_metrics_rate(vfx_handle* h, const float* est, const float* target,
 int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,
              const double* taps, int ntaps, double* out, void* stream);
 
+/*
+ * BSS Eval v4 "images" SDR, ISR and SAR (Vincent, Gribonval, Fevotte, IEEE TASLP 2006; the SiSEC 2018 form that speechmetrics calls
+ * with window = inf), specialised to one source, one channel and one window over the whole file; restated from this definition --
+ * not pinned against the museval package -- for a padded batch of (est, target) waveform pairs: est, target (B, Lmax) device floats,
+ * pair b = the first n = lengths[b] samples of row b; lengths is a HOST array int[B] with 1 <= lengths[b] <= Lmax.  flen = L, the taps
+ * of the allowed distortion filter: a multiple of 16 in [16, 512] (the reference uses 512); anything else is refused before the first
+ * launch.  out: (B, 3) device doubles, sdr, isr, sar.  With r the target and e the est, both promoted to float64:
+ *   1  a[k] = sum_t r[t] r[t + k], k < L; terms whose index falls outside [0, n) are zero
+ *   2  d[k] = sum_t e[t] r[t - k], k < L, likewise (the products of two floats are exact in float64: only the summation rounds)
+ *   3  (toeplitz(a) + EPS I) c = d, EPS = 2^-52, by the Levinson recursion
+ *   4  P[t] = sum_k c[k] r[t - k], t < n + L - 1; r and e are zero-padded to n + L - 1
+ *   5  Err = sum r^2, Eer = sum (e - r)^2, Epr = sum (P - r)^2, Epp = sum P^2, Eep = sum (e - P)^2 over t < n + L - 1
+ *   6  sdr = 10 log10(Err / Eer), isr = 10 log10(Err / Epr), sar = 10 log10(Epp / Eep); a denominator that is exactly 0 gives +inf; if
+ *      every sample of r, or every sample of e, is exactly 0, all three are NaN (the silent-source rule)
+ * Float64 from the first multiply on (the correlations and the projection on the f64 MFMA), every sum in an order fixed by the clip
+ * alone -- slabs of VFX_BSSEVAL_SLAB samples cut from the clip's own extent, combined in ascending order: a clip's scores do not depend
+ * on the batch it is in, on Lmax, nor on what lies at or past its length in its row; nothing there is read.  The workspace is the one
+ * of vfx_audio_metrics (sub-batched under 256 MiB).
+ */
+#define VFX_BSSEVAL_SLAB 8192
+int vfx_bsseval(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int flen, double* out,
+                void* stream);
+
 /* Read-and-clear the sticky device flags (synchronises `stream`). */
 int vfx_take_flags(vfx_handle* h, void* stream, int* flags_out);
 /* ... only the bits in `mask` (VFX_FLAG_*): the others stay raised for a later check. */

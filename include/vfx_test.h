@@ -221,6 +221,16 @@ int vfx_op_score_spectrogram(vfx_handle* h, const float* wav, int B, int Lmax, c
  * Synchronises. */
 int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int up, int down,
                       const double* taps, int ntaps, int stage, double* out, int64_t out_n, int* iout, int64_t iout_n, void* stream);
+/* One intermediate of a vfx_bsseval call -- the same arguments up to flen, B <= 1024 -- for the whole batch, to localise a failing
+ * score.  out is a DEVICE array of exactly out_n doubles:
+ *   stage 0  out (B, 2, flen): a and d
+ *   stage 1  out (B, flen): c
+ *   stage 2  out (B, 5): the energies Err, Eer, Epr, Epp, Eep
+ *   stage 3  out (B, Lmax + flen - 1): P, zeros past a clip's n + flen - 1 -- the one place P is stored: the projection kernel of the
+ *            product call, with its store enabled
+ * Synchronises. */
+int vfx_op_bsseval_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int flen, int stage,
+                         double* out, int64_t out_n, void* stream);
 /* Debug switch of a handle, for measurements: natural != 0 makes vfx_resample_each keep its scaled taps in natural order instead of
  * phase-major (the same sums in the same order: every result bit stays; only the memory the tap reads touch changes). */
 int vfx_debug_resample_each_layout(vfx_handle* h, int natural);

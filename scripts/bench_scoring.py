@@ -4,12 +4,14 @@ varlen workload (scripts/bench_varlen.py: the same lengths), timed four ways:
 
   device_ms        vfx_audio_metrics over the 128 pairs as ONE call (sorted by length), HIP events, median of --reps
   stoi_device_ms   with --stoi: vfx_stoi over the same 128 pairs as one call, timed the same way (report only)
+  bsseval_device_ms  with --bsseval: vfx_bsseval (512 taps) over the same 128 pairs as one call, timed the same way (report only), its
+                   share of restore_list_s, and the float64 numpy restatement (tests/bsseval_f64.py) on --threads threads
   restore_list_s   VoiceFixer.restore_list on the same clips (synthetic weights, --precision), wall, median: the bar is
                    device_ms <= 10 % of it
   aggregate_s      aggregate_score end to end: 128 PCM16 est files and 128 targets read, scored, JSON / CSV / result.json written
   numpy_s          the float64 numpy restatement (tests/audio_metrics_f64.py) over the same pairs on --threads threads
 
-    python scripts/bench_scoring.py [--clips=128] [--reps=5] [--precision=2] [--threads=16] [--only-device] [--stoi] > scoring.json
+    python scripts/bench_scoring.py [--clips=128] [--reps=5] [--precision=2] [--threads=16] [--only-device] [--stoi] [--bsseval] > scoring.json
 """
 import json
 import os
@@ -80,6 +82,10 @@ def main():
         ms = device_ms(lambda: eng.stoi(e, t, ls, fs=44100))
         res["stoi_device_ms"] = round(float(np.median(ms)), 3)
         res["stoi_device_ms_all"] = [round(v, 3) for v in ms]
+    if "--bsseval" in sys.argv:
+        ms = device_ms(lambda: eng.bsseval(e, t, ls))
+        res["bsseval_device_ms"] = round(float(np.median(ms)), 3)
+        res["bsseval_device_ms_all"] = [round(v, 3) for v in ms]
     if "--only-device" in sys.argv:                 # (a profiler run: nothing but the scoring call in the trace)
         print(json.dumps(res))
         return
@@ -99,6 +105,8 @@ def main():
         ts.append(time.perf_counter() - t0)
     res["restore_list_s"] = round(float(np.median(ts)), 4)
     res["device_over_restore_list"] = round(res["device_ms"] / 1e3 / res["restore_list_s"], 4)
+    if "--bsseval" in sys.argv:
+        res["bsseval_over_restore_list"] = round(res["bsseval_device_ms"] / 1e3 / res["restore_list_s"], 4)
     print(json.dumps(res), flush=True)
 
     with tempfile.TemporaryDirectory() as d:
@@ -133,6 +141,14 @@ def main():
     got = eng.audio_metrics(e, t, ls).cpu().numpy()
     want = np.stack([host[i] for i in order])
     res["max_abs_diff_vs_numpy"] = [float(v) for v in np.abs(got - want).max(axis=0)]
+    if "--bsseval" in sys.argv:
+        import bsseval_f64 as bref
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(threads) as ex:
+            host = list(ex.map(lambda i: bref.bsseval(ests[i], tgts[i]), range(n)))
+        res["bsseval_numpy_s"] = round(time.perf_counter() - t0, 2)
+        got = eng.bsseval(e, t, ls).cpu().numpy()
+        res["bsseval_max_abs_diff_vs_numpy"] = [float(v) for v in np.abs(got - np.stack([host[i] for i in order])).max(axis=0)]
     print(json.dumps(res))
 
 

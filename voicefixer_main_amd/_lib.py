@@ -24,6 +24,7 @@ FLAG_F16_SATURATED = 2   # precision 2: an activation of the vocoder left the fp
 FLAG_PEAK_NORMALISED = 4  # vfx_restore_gsr divided a clip by its peak (the reference's "Exceed energy limit" warning)
 N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metrics
 N_HANDLER_METRICS = 4     # VFX_N_HANDLER_METRICS: the columns of vfx_restore_*_varlen_scored
+BSSEVAL_SLAB = 8192       # VFX_BSSEVAL_SLAB: samples per partial sum of vfx_bsseval
 
 
 class VfxConfig(ctypes.Structure):
@@ -80,6 +81,7 @@ SIGNATURES = {
     "vfx_audio_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_audio_metrics_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),
     "vfx_stoi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "vfx_bsseval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_chunk_ola": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_void_p, c_void_p]),
@@ -149,6 +151,8 @@ TEST_SIGNATURES = {
     "vfx_op_score_spectrogram": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "vfx_op_stoi_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "vfx_op_bsseval_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_int64,
+                                     c_void_p]),
     "vfx_debug_resample_each_layout": (c_int, [c_void_p, c_int]),
 }
 

@@ -432,6 +432,13 @@ int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lm
   VFX_API_END
 }
 
+int vfx_bsseval(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int flen, double* out,
+                void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  bsseval_scores(h, est, target, B, Lmax, lengths, flen, out, nullptr, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
 int vfx_chunk_gather(vfx_handle* h, const float* x, int B, int L, int win, int hop, int lead, int n_chunks,
                      float* chunks, void* stream) {
   VFX_API_BEGIN_HS(h, stream)

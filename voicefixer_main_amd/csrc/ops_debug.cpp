@@ -1272,3 +1272,21 @@ extern "C" int vfx_op_stoi_stage(vfx_handle* h, const float* est, const float* t
   }
   return 0;
 }
+
+extern "C" int vfx_op_bsseval_stage(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lens, int flen,
+                                    int stage, double* out, int64_t out_n, void* stream) {
+  try {
+    VFX_CHECK(h != nullptr, "vfx_op_bsseval_stage: NULL handle");
+    DeviceGuard device_guard_(h->device);
+    BssStageOut so;
+    so.stage = stage;
+    so.out = out;
+    so.out_n = out_n;
+    Scratch sc;
+    double* scores = static_cast<double*>(sc.blob.alloc((size_t)std::max(B, 1) * 3 * sizeof(double)));
+    bsseval_scores(h, est, target, B, Lmax, lens, flen, scores, &so, static_cast<hipStream_t>(stream));
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
+}

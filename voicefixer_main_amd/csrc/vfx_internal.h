@@ -148,7 +148,8 @@ enum LensRow {
   LENS_LOWPASS_SAMPLES = 12, LENS_LOWPASS_CUT = 13,                    // samples / cut-off bin of the vfx_stft_lowpass sub-batch in flight
   LENS_STOI_SAMPLES = 14, LENS_STOI_OUT = 15, LENS_STOI_FRAMES = 16,   // input samples / 10 kHz samples / frames of the vfx_stoi sub-batch in flight
   LENS_TARGET_SAMPLES = 17,                                            // samples of the targets of a vfx_restore_*_varlen_scored call
-  kLensRows = 18
+  LENS_BSS_SAMPLES = 18,                                               // samples of the vfx_bsseval sub-batch in flight
+  kLensRows = 19
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -546,6 +547,19 @@ struct StoiStageOut {
 // vfx_stoi (checks its arguments before the first launch); stage: null, or the intermediate to copy out (one sub-batch only)
 void stoi_scores(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int up, int down,
                  const double* taps, int ntaps, double* out, const StoiStageOut* stage, hipStream_t s);
+
+// bsseval.hip: BSS Eval v4 "images" SDR, ISR, SAR (Vincent, Gribonval, Fevotte 2006) of the clips of a padded batch, float64 throughout;
+// the slabs of its sums are VFX_BSSEVAL_SLAB samples (include/vfx.h)
+constexpr int kBssMaxFlen = 512;        // taps of the distortion filter: two MFMA accumulators of 256 lags per correlation
+// one intermediate of a vfx_bsseval call, copied out for libvfx_test.so (vfx_op_bsseval_stage; the stages and layouts: include/vfx_test.h)
+struct BssStageOut {
+  int stage = 0;
+  double* out = nullptr;
+  int64_t out_n = 0;
+};
+// vfx_bsseval (checks its arguments before the first launch); stage: null, or the intermediate to copy out (one sub-batch only)
+void bsseval_scores(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int flen, double* out,
+                    const BssStageOut* stage, hipStream_t s);
 void launch_chunk_gather(const float* x, int B, int L, int win, int hop, int lead, int n_chunks, float* chunks,
                          hipStream_t s);
 void launch_chunk_ola(const float* frames, const float* window, float scale, int B, int n_chunks, int win, int hop,

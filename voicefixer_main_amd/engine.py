@@ -370,6 +370,25 @@ class Engine:
                                      _ptr(taps) if taps is not None else None, ntaps, _ptr(out), self._stream()), "vfx_stoi")
         return out
 
+    BSSEVAL_SLAB = _lib.BSSEVAL_SLAB   # samples per partial sum of vfx_bsseval: the slabs are cut from each clip's own extent
+
+    def bsseval(self, est, target, lengths=None, flen=512):
+        """BSS Eval v4 "images" SDR, ISR and SAR (Vincent et al. 2006; one source, one channel, one window over the whole file; restated
+        from the definition in include/vfx.h, not pinned against museval) of waveform pairs: est, target (B, L) or (L,), pair b = the
+        first lengths[b] samples of row b (default: all L) -> (B, 3) float64 on the device: sdr, isr, sar (vfx_bsseval).  flen: the taps
+        of the distortion filter, a multiple of 16 in [16, 512].  A silent est or target scores NaN x 3; a denominator that is exactly
+        zero gives +inf.  A flen or a length the library does not take raises RuntimeError with its text."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        if est.shape != target.shape or est.dim() != 2:
+            raise ValueError("bsseval: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
+        est, _, B, L, lengths = _clip_rows(est, lengths, "bsseval")
+        out = torch.empty(B, 3, device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_bsseval(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * max(B, 1))(*lengths), int(flen),
+                                        _ptr(out), self._stream()), "vfx_bsseval")
+        return out
+
     def chunk_gather(self, x, win, hop, lead, n_chunks):
         """F.unfold with zero padding: x (B, L) -> (B, n_chunks, win), chunk k = x[k*hop - lead : ... + win]."""
         x = _dev_f32(x, self.device)
@@ -1357,3 +1376,23 @@ class Engine:
         if k == 1:
             return out, iout[:B], iout[B:].view(B, Fm)
         return out, iout
+
+    BSSEVAL_STAGES = ("lags", "filter", "energies", "projection")
+
+    def op_bsseval_stage(self, stage, est, target, lengths=None, flen=512):
+        """One intermediate of `bsseval` for the whole batch (vfx_op_bsseval_stage), a float64 tensor on the device:
+          "lags"       -> (B, 2, flen): a and d
+          "filter"     -> (B, flen): c
+          "energies"   -> (B, 5): sum r^2, (e - r)^2, (P - r)^2, P^2, (e - P)^2
+          "projection" -> (B, L + flen - 1): P, zeros past a clip's own lengths[b] + flen - 1"""
+        k = self.BSSEVAL_STAGES.index(stage)
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        est, _, B, L, lengths = _clip_rows(est, lengths, "op_bsseval_stage")
+        flen = int(flen)
+        shape = ((B, 2, flen), (B, flen), (B, 5), (B, L + flen - 1))[k]
+        out = torch.zeros(shape, device=self.device, dtype=torch.float64)
+        _lib.check(_lib.load_test().vfx_op_bsseval_stage(self.h, _ptr(est), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), flen, k,
+                                                         _ptr(out), out.numel(), self._stream()), "vfx_op_bsseval_stage")
+        return out

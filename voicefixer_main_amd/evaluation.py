@@ -129,16 +129,17 @@ def inference(model, save_dir, testsets, metas, limit_number=None, max_batch=128
                 metrics.write_json(scores, output[:-4] + ".json")
 
 
-def evaluation(output_path, model, description, testsets, metas, limit_phrase_number=None, stoi=False):
+def evaluation(output_path, model, description, testsets, metas, limit_phrase_number=None, stoi=False, bsseval=False):
     """evaluation_proc/eval.py:142-221: `inference` into output_path/<date>_<description>_<id>, metrics.aggregate_score per test set
-    (on the model's engine; stoi=True adds STOI), metrics.gather_score.  Returns that directory."""
+    (on the model's engine; stoi=True adds STOI, bsseval=True the BSS Eval sdr, isr, sar), metrics.gather_score.  Returns that
+    directory."""
     run = time.strftime("%Y-%m-%d", time.localtime()) + "_" + description + "_" + str(int(random.random() * 1000))
     output_path = os.path.join(output_path, run)
     inference(model, output_path, testsets, metas, limit_number=limit_phrase_number)
     for testset in testsets:
         try:
             metrics.aggregate_score(output_path, [testset], limit_number=limit_phrase_number, metas=metas,
-                                    engine=getattr(model, "engine", None), stoi=stoi)
+                                    engine=getattr(model, "engine", None), stoi=stoi, bsseval=bsseval)
         except Exception as e:      # (the reference logs a test set that fails to score and goes on to the next)
             logging.exception(e)
     metrics.gather_score(output_path, testsets)

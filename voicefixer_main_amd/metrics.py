@@ -13,9 +13,15 @@ pystoi's stoi(extended=False): 10 kHz by Octave's resample filter, frames at ran
 taken --, 1e-5 for fewer than 30 frames) and, like SI-SDR, held against a float64 restatement (tests/stoi_f64.py: within 1e-9), not
 pinned against the pystoi package.
 
+With `bsseval=True` the keys `sdr`, `isr`, `sar` follow the others: BSS Eval v4 "images" (Vincent, Gribonval, Fevotte 2006; the
+SiSEC 2018 form speechmetrics calls with window = inf) for one source, one channel and one window over the whole file, with a 512-tap
+distortion filter, computed on the GPU by vfx_bsseval (Engine.bsseval) from the same padded batches.  They are restated from the
+definition in include/vfx.h and held against a float64 restatement (tests/bsseval_f64.py: within 1e-9 dB), not pinned against the
+museval package.  A silent est or target scores NaN in all three (museval's rule), which the mean row skips as pandas does.
+
 What differs from the reference, on purpose:
-  * STOI is opt-in (`stoi=True`); PESQ and the bsseval scores are not computed, and their keys are absent (no implementation to pin
-    them against).
+  * STOI and the bsseval scores are opt-in (`stoi=True`, `bsseval=True`) and restated; PESQ is not computed, and its key is absent
+    (no implementation to pin it against).
   * 44.1 kHz and 16 kHz targets (the rates in the engine's `score_rates`; an engine without that attribute scores 44.1 kHz only): any
     other rate raises ValueError, like the reference's "Bad Samplerate" for rates it has no STFT for.  An est file at another rate
     than its target, or of another length, makes that pair an error: speechmetrics would zero-pad the shorter signal and
@@ -36,6 +42,7 @@ from . import handlers
 
 METRIC_KEYS = ("sisdr", "lsd", "non_log_sispec", "sispec", "ssim",
                "final_mel_lsd", "final_non_log_mel_sispec", "final_mel_sispec", "final_mel_ssim")
+BSSEVAL_KEYS = ("sdr", "isr", "sar")
 SAMPLE_RATE = 44100
 MIN_SAMPLES = 6 * 441   # 7 STFT frames: skimage's 7 x 7 SSIM rejects a smaller spectrogram
 # rate -> (hop, fewest samples that give 7 STFT frames): T = n // 441 + 1 at n_fft 2048; T = 1 + (n - 1) // 160 at the odd n_fft 743
@@ -65,11 +72,12 @@ def _wav_info(path):
 
 class AudioMetrics:
     """evaluation_proc/metrics.py:20-106 at 44.1 kHz or 16 kHz.  `engine`: an Engine (or anything with `device` and
-    `audio_metrics(est, target, lengths)` -- and, for `stoi=True`, `stoi(est, target, lengths, fs)`); default: a new Engine on cuda:0.
+    `audio_metrics(est, target, lengths)` -- and, for `stoi=True`, `stoi(est, target, lengths, fs)`, for `bsseval=True`,
+    `bsseval(est, target, lengths)`); default: a new Engine on cuda:0.
     A rate other than 44100 must be in the engine's `score_rates`, and is handed to it as `audio_metrics(..., rate=rate)`.
-    stoi=True adds the key "stoi" after "sisdr"."""
+    stoi=True adds the key "stoi" after "sisdr"; bsseval=True appends BSSEVAL_KEYS."""
 
-    def __init__(self, rate, engine=None, stoi=False):
+    def __init__(self, rate, engine=None, stoi=False, bsseval=False):
         if engine is None and int(rate) in FRONT_ENDS:
             from .engine import Engine
             engine = Engine("cuda:0")
@@ -80,12 +88,15 @@ class AudioMetrics:
         self.hop, self.min_samples = FRONT_ENDS[self.rate]
         self.engine = engine
         self.stoi = bool(stoi)
+        self.bsseval = bool(bsseval)
         self.keys = METRIC_KEYS[:1] + ("stoi",) + METRIC_KEYS[1:] if self.stoi else METRIC_KEYS
+        if self.bsseval:
+            self.keys = self.keys + BSSEVAL_KEYS
 
     # ------------------------------------------------------------------ files
     def evaluation(self, est, target):
-        """est, target: .wav paths -> {key: float} (self.keys: METRIC_KEYS, with "stoi" second when asked for); {} when target is
-        None."""
+        """est, target: .wav paths -> {key: float} (self.keys: METRIC_KEYS, with "stoi" second and BSSEVAL_KEYS last when asked for); {} when
+        target is None."""
         if target is None:
             return {}
         r = self.evaluation_list([(est, target)])[0]
@@ -108,7 +119,7 @@ class AudioMetrics:
     def evaluation_list(self, pairs, max_batch=128):
         """[(est_path, target_path), ...] -> one entry per pair, in order: the {key: float} dict, or the exception that pair
         raised.  The pairs are read and scored sorted by length, up to `max_batch` per padded batch (one vfx_audio_metrics call and,
-        with stoi, one vfx_stoi call on the same device tensors)."""
+        with stoi, one vfx_stoi call, with bsseval, one vfx_bsseval call on the same device tensors)."""
         results = [None] * len(pairs)
         ok = []
         for i, (est, target) in enumerate(pairs):
@@ -146,6 +157,9 @@ class AudioMetrics:
             if self.stoi:
                 st = self.engine.stoi(e_dev, t_dev, lengths, fs=self.rate).cpu().numpy().tolist()
                 scores = [row[:1] + [st[j]] + row[1:] for j, row in enumerate(scores)]
+            if self.bsseval:
+                bs = self.engine.bsseval(e_dev, t_dev, lengths).cpu().numpy().tolist()
+                scores = [row + bs[j] for j, row in enumerate(scores)]
             for j, i in enumerate(idx):
                 results[i] = {key: float(v) for key, v in zip(self.keys, scores[j])}
         return results
@@ -172,14 +186,15 @@ def _parse(line):
 
 
 def _means(rows):
-    """Column means over the rows that hold a number in that column (pandas DataFrame.mean)."""
+    """Column means over the rows that hold a number in that column (pandas DataFrame.mean); a NaN in a BSSEVAL_KEYS column -- a
+    silent est or target -- is skipped like a missing value, as pandas does."""
     cols, sums, counts = [], {}, {}
     for r in rows.values():
         for k, v in r.items():
             if k not in sums:
                 cols.append(k)
                 sums[k], counts[k] = 0.0, 0
-            if isinstance(v, (int, float)) and not isinstance(v, bool):
+            if isinstance(v, (int, float)) and not isinstance(v, bool) and not (k in BSSEVAL_KEYS and v != v):
                 sums[k] += float(v)
                 counts[k] += 1
     return cols, {k: (sums[k] / counts[k] if counts[k] else float("nan")) for k in cols}
@@ -195,13 +210,13 @@ def _write_table(path, rows, cols, mean_row=None):
             w.writerow(["mean"] + [repr(mean_row[c]) for c in cols])
 
 
-def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=None, stoi=False):
+def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=None, stoi=False, bsseval=False):
     """evaluation_proc/eval.py:25-86.  metas[testset] = {"rate": ..., "list": path of the `source [target]` list}; the restored
     file of a line is save_dir/testset/basename(source).  Per pair with a target: the scores, updated with the handler's JSON
     beside the restored file (save_dir/testset/<name>.json, when it exists), are written back to that JSON.  Per test set:
     <testset>.csv (one row per target basename and a `mean` row) and result.json (the means).  A pair that fails is logged and
-    left out.  stoi=True: the scores carry "stoi" (AudioMetrics(stoi=True)), and so do the tables and means.  Returns
-    {testset: {target basename: scores}}."""
+    left out.  stoi=True: the scores carry "stoi" (AudioMetrics(stoi=True)), and so do the tables and means; bsseval=True: likewise
+    "sdr", "isr", "sar" (AudioMetrics(bsseval=True)).  Returns {testset: {target basename: scores}}."""
     if metas is None:
         raise ValueError("aggregate_score: metas ({testset: {'rate', 'list'}}) is required (the reference's Config is not part of "
                          "this package)")
@@ -214,7 +229,7 @@ def aggregate_score(save_dir, testsets, limit_number=None, metas=None, engine=No
         lst = read_list(meta["list"])
         if limit_number is not None:
             lst = lst[:limit_number]
-        judger = AudioMetrics(rate=meta["rate"], engine=engine, stoi=stoi)
+        judger = AudioMetrics(rate=meta["rate"], engine=engine, stoi=stoi, bsseval=bsseval)
         pairs, names = [], []
         for line in lst:
             source, target = _parse(line)
