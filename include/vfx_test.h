@@ -99,6 +99,21 @@ int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, int Cin, cons
  *   path's peak normalisation reads. */
 int vfx_op_voc_final(vfx_handle* h, const float* x, int B, int T, int C, const float* weight, float bias, float slope, int x_f16,
                      const int* lens, float* wav, float* peak, void* stream);
+/* vfx_op_voc_resblock: one fused ResStack launch as the plan adds it (vocoder.cpp: voc_resblock_params, then plan_resblock and
+ *   launch_resblock) on x (B, T, C) -- layer (w1, b1, w2, b2; conv1 of dilation dil) and, dil2 > 0, the layer behind it (w1b .. b2b) in the
+ *   same launch; weights (C, C, 3) and biases (C) on the HOST, w1b .. b2b NULL without a pair.  slope: the layer's LeakyReLU
+ *   (voc_res_slope of this call); act_slope: that of the activated output.  The trunk takes the form the handle's precision and tuning
+ *   give this width, for a stack in front of an upsampler when want_act is set and for the last stage otherwise: fp32 x, fp16(x), or
+ *   -- C = 256 in the 16-bit mode -- xa = fp16(LeakyReLU(x, slope)) beside x or alone; built here from x.  want_raw: the raw output into y;
+ *   want_act: ya = fp16(LeakyReLU(y, act_slope)); both widened to fp32 FROM THE STORED FORM (fp32 or fp16), NaN where the launch stored
+ *   nothing.  lens / lens_mul: clip b ends at lens[b] * lens_mul <= T positions.  A byte written outside the outputs asked for is an
+ *   error, and so is a combination the plan refuses (nothing is launched then): a pair the plan does not form, ya outside the 16-bit
+ *   mode, y of a trunk that keeps none, lens on resblock_rw's fp32 trunk.  info (NULL or 12 ints) receives what plan_resblock chose:
+ *   rw, r128, asrc, fold, tile_m, TWo, TH, tiles_h, tiles_w, x16, W1, patch_rows. */
+int vfx_op_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C, const float* w1, const float* b1, const float* w2,
+                        const float* b2, int dil, const float* w1b, const float* b1b, const float* w2b, const float* b2b, int dil2,
+                        float slope, float act_slope, int want_raw, int want_act, const int* lens, int lens_mul, float* y, float* ya,
+                        int* info, void* stream);
 /* Host-only: the kernel the vocoder plan runs a Cin -> Cout = Cin / 2 upsampler of stride s over T input positions on (a stage behind the
  * first and not the last, in precision mode `precision` with vfx_config.tuning = `tuning`): 1 = k_up16, 0 = the phased k_conv,
  * -1 = bad arguments. */

@@ -129,7 +129,10 @@ TEST_SIGNATURES = {
                                   c_float, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfx_op_voc_final": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
-    "vfx_plan_voc_upsampler_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vfx_op_voc_resblock": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    POINTER(c_int), c_void_p]),
+    "vfx_plan_voc_upsampler_kernel":(c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vfx_op_unet_piece": (c_int, [c_void_p, c_int, c_char_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int64), c_int,
                                   c_void_p, POINTER(c_int64), c_int, c_void_p, c_int64, POINTER(c_int), POINTER(c_int), c_int,
                                   POINTER(c_int), c_void_p]),

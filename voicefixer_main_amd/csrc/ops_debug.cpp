@@ -1,7 +1,8 @@
 // ops_debug.cpp -- libvfx_test.so: kernel-level C entry points used by the parity tests (include/vfx_test.h).
 // They pack PyTorch-layout weights on the fly, run one kernel family of libvfx.so and synchronise; vfx_op_voc_* and vfx_op_unet_piece
 // run single launches of the vocoder and ResUNet plans through the plans' own builder functions (vocoder.cpp, resunet.cpp) -- no
-// launch parameters of those plans are restated here.  Not part of the product library: built into its own shared object that
+// launch parameters of those plans are restated here (vfx_op_resblock / vfx_op_resblock_pair, the older entry points of the fused ResStack
+// layers, fill theirs by hand; vfx_op_voc_resblock is the plan's form).  Not part of the product library: built into its own shared object that
 // resolves the internals it uses from libvfx.so.
 #include <cmath>
 #include <cstring>
@@ -160,8 +161,12 @@ static void from_device_f16(const float* d16, float* dy, size_t n, float slope) 
   VFX_HIP(hipMemcpy(dy, hy.data(), n * sizeof(float), hipMemcpyHostToDevice));
 }
 // Runs a planned layer (or pair) of the raw fp16 trunk twice -- y16 + ya, then ya alone (the last layer in front of an upsampler
-// stores no raw output) -- checks that ya is the same bit pattern both times and that it is LeakyReLU(y16) up to the one rounding
-// that separates fp16(LeakyReLU(s)) from LeakyReLU(fp16(s)), and returns y16 widened in the caller's fp32 tensor.
+// stores no raw output) -- checks that ya is the same bit pattern both times and that it fits y16, and returns y16 widened in the
+// caller's fp32 tensor.  The kernels (resblock_rw.hip, resblock_r128.hip) round BOTH outputs from the same unrounded fp32 sum s:
+// y16 = fp16(s), ya = fp16(fl32(max(s, s * slope))).  So where y16 >= 0, ya is y16 itself (0 < slope <= 1: the maximum is s); where
+// y16 < 0, s lies within half an fp16 ulp hu(y16) of y16 and ya within half an fp16 ulp of slope * s:
+//   |ya - slope * y16| <= slope * hu(y16) + hu(w) + 2^-24 w,  w = slope * (|y16| + hu(y16)),  hu(a) = 2^(max(ilogb(a), -14) - 11)
+// -- at most |slope * y16| / 1024 + 2^-24, half of the 1 / 512 this check allowed before.
 static void run_raw_f16_trunk(ResBlockParams rp, float* y_out, size_t n, float slope, DeviceBlob& blob, hipStream_t s) {
   float* y16 = static_cast<float*>(blob.alloc(n * sizeof(_Float16)));
   float* ya_a = static_cast<float*>(blob.alloc(n * sizeof(_Float16)));
@@ -181,9 +186,15 @@ static void run_raw_f16_trunk(ResBlockParams rp, float* y_out, size_t n, float s
   for (size_t i = 0; i < n; ++i) {
     VFX_CHECK(__builtin_bit_cast(unsigned short, ha[i]) == __builtin_bit_cast(unsigned short, hb[i]),
               "fp16 trunk: ya differs between the launch with and without the raw output at element %zu", i);
-    const float v = (float)hy[i] > 0.f ? (float)hy[i] : (float)hy[i] * slope;
-    VFX_CHECK(std::fabs((float)ha[i] - v) <= std::fabs(v) * (1.f / 512.f) + 1e-7f, "fp16 trunk: ya is not LeakyReLU(y) at element %zu (%g vs %g)", i,
-              (double)(float)ha[i], (double)v);
+    const double yv = (double)(float)hy[i], av = (double)(float)ha[i];
+    if (yv >= 0.0) {
+      VFX_CHECK(av == yv, "fp16 trunk: ya is not y at element %zu, where y >= 0 (%g vs %g)", i, av, yv);
+    } else {
+      auto hu = [](double a) { return std::ldexp(1.0, std::max(std::ilogb(a), -14) - 11); };
+      const double w = (double)slope * (-yv + hu(yv));
+      VFX_CHECK(std::fabs(av - (double)slope * yv) <= (double)slope * hu(yv) + hu(w) + std::ldexp(w, -24),
+                "fp16 trunk: ya is not within half an fp16 ulp of LeakyReLU(s) at element %zu (%g vs y = %g)", i, av, yv);
+    }
   }
   from_device_f16(y16, y_out, n, 1.f);
 }
@@ -671,7 +682,7 @@ extern "C" int vfx_op_conv_transpose(vfx_handle* h, const float* x, int B, int H
   return 0;
 }
 
-// ---- the vocoder's launches as the plan builds them (vocoder.cpp: voc_upsample_params, voc_conv1d_params, launch_voc_final) --------
+// ---- the vocoder's launches as the plan builds them (vocoder.cpp: voc_upsample_params, voc_conv1d_params, voc_resblock_params, launch_voc_final)
 namespace {
 uint16_t bf16_rne_host(float f) {
   uint32_t u;
@@ -879,6 +890,85 @@ extern "C" int vfx_plan_voc_upsampler_kernel(int Cin, int Cout, int s, int T, in
   } catch (const vfx::Error&) {
     return -1;
   }
+}
+
+// One fused ResStack launch (a layer, or a pair: dil2 > 0) the way build_vocoder adds it: voc_resblock_params + plan_resblock +
+// launch_resblock, the trunk in the form the handle gives this width.  Both outputs live in ONE device buffer between guard zones,
+// all of it NaN patterns before the launch: [guard | y | guard | ya | guard]; a guard byte -- or a byte of an output the launch was
+// not given -- that changed is an error of the call.
+extern "C" int vfx_op_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C, const float* w1, const float* b1, const float* w2,
+                                   const float* b2, int dil, const float* w1b, const float* b1b, const float* w2b, const float* b2b,
+                                   int dil2, float slope, float act_slope, int want_raw, int want_act, const int* lens, int lens_mul,
+                                   float* y, float* ya, int* info, void* stream) {
+  try {
+    VFX_CHECK(h && x && w1 && b1 && w2 && b2 && B > 0 && T > 0 && C > 0 && dil >= 1 && dil2 >= 0 && (want_raw || want_act) &&
+                  (!want_raw || y) && (!want_act || ya) && lens_mul >= 1 && (dil2 == 0 || (w1b && b1b && w2b && b2b)),
+              "vfx_op_voc_resblock: bad argument");
+    for (int b = 0; lens && b < B; ++b)
+      VFX_CHECK(lens[b] >= 0 && (int64_t)lens[b] * lens_mul <= T, "vfx_op_voc_resblock: clip %d has %d x %d positions (need 0 .. T = %d)", b,
+                lens[b], lens_mul, T);
+    DeviceGuard device_guard_(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    vfx_config cfg = h->cfg;
+    cfg.voc_res_slope = slope;
+    const int kind = voc_resblock_kind(cfg, C);
+    VFX_CHECK(kind != VOC_RES_TWO_LAUNCHES, "vfx_op_voc_resblock: the plan of this handle runs a %d-channel layer as two k_conv launches", C);
+    const bool wide = kind == VOC_RES_FUSED_WIDE;
+    // want_act: a stack in front of an upsampler; otherwise the last stage's form (the tail reads the raw trunk)
+    const bool last_stage = !want_act;
+    const bool t16 = voc_resblock_trunk_f16(cfg, C, last_stage);
+    const size_t nel = (size_t)B * T * C;
+    const VocResLayer l1{pack_voc_conv1d(cfg, sc.blob, w1, b1, C, C, 3, wide), pack_voc_conv1d(cfg, sc.blob, w2, b2, C, C, 3, wide)};
+    VocResLayer l2;
+    if (dil2 > 0) l2 = {pack_voc_conv1d(cfg, sc.blob, w1b, b1b, C, C, 3, wide), pack_voc_conv1d(cfg, sc.blob, w2b, b2b, C, C, 3, wide)};
+    const float* dx = wide ? (t16 ? nullptr : x) : (t16 ? to_device_f16(sc.blob, x, nel, 1.f) : x);
+    const float* dxa = wide ? to_device_f16(sc.blob, x, nel, slope) : nullptr;
+    const bool y_f16 = t16 && !wide;
+    const size_t guard = 1 << 16, ybytes = (nel * (y_f16 ? 2 : 4) + 255) / 256 * 256, abytes = (nel * 2 + 255) / 256 * 256;
+    const size_t yoff = guard, aoff = yoff + ybytes + guard, total = aoff + abytes + guard;
+    char* buf = static_cast<char*>(sc.blob.alloc(total));
+    VFX_HIP(hipMemset(buf, 0xff, total));
+    float* dy = want_raw ? reinterpret_cast<float*>(buf + yoff) : nullptr;
+    float* dya = want_act ? reinterpret_cast<float*>(buf + aoff) : nullptr;
+    ResBlockParams rp = voc_resblock_params(cfg, C, last_stage, l1, dil2 > 0 ? &l2 : nullptr, B, T, dil, dil2, dx, dxa, dy, dya, act_slope,
+                                            upload_lens(sc.blob, lens, B), lens_mul);
+    rp.flags = h->d_flags;
+    plan_resblock(rp);
+    if (info) {
+      const int v[12] = {rp.rw, rp.r128, rp.asrc, rp.fold, rp.tile_m, rp.TWo, rp.TH, rp.tiles_h, rp.tiles_w, rp.x16, rp.W1, rp.patch_rows};
+      for (int i = 0; i < 12; ++i) info[i] = v[i];
+    }
+    ResBlockParams* d = static_cast<ResBlockParams*>(sc.blob.alloc(sizeof(ResBlockParams)));
+    VFX_HIP(hipMemcpy(d, &rp, sizeof(rp), hipMemcpyHostToDevice));
+    launch_resblock(rp, d, s);
+    VFX_HIP(hipStreamSynchronize(s));
+    std::vector<unsigned char> hb(total);
+    VFX_HIP(hipMemcpy(hb.data(), buf, total, hipMemcpyDeviceToHost));
+    auto untouched = [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i)
+        if (hb[i] != 0xff) return false;
+      return true;
+    };
+    VFX_CHECK(untouched(0, yoff) && untouched(yoff + (want_raw ? nel * (y_f16 ? 2 : 4) : 0), aoff) &&
+                  untouched(aoff + (want_act ? nel * 2 : 0), total),
+              "vfx_op_voc_resblock: the launch wrote outside its outputs");
+    std::vector<float> hy(nel);
+    auto widen = [&](size_t off, bool f16, float* dst) {
+      if (f16) {
+        const _Float16* p16 = reinterpret_cast<const _Float16*>(hb.data() + off);
+        for (size_t i = 0; i < nel; ++i) hy[i] = (float)p16[i];
+      } else {
+        memcpy(hy.data(), hb.data() + off, nel * sizeof(float));
+      }
+      VFX_HIP(hipMemcpy(dst, hy.data(), nel * sizeof(float), hipMemcpyHostToDevice));
+    };
+    if (want_raw) widen(yoff, y_f16, y);
+    if (want_act) widen(aoff, true, ya);
+  } catch (const vfx::Error&) {
+    return 1;
+  }
+  return 0;
 }
 
 // ---- the ResUNet plans' launches, one piece at a time, built by the plan's own builder (resunet.cpp: build_unet_piece) -----------------

@@ -941,6 +941,23 @@ TapConvParams voc_upsample_params(const vfx_config& cfg, const VocConvW& up, int
                                   float* out, float* out_act, float act_slope, const int* lens, int rate, std::vector<TapSeg>& phases);
 // 1 when the plan runs the upsampler of a cin-channel stage (behind the first, not the last) on k_up16, 0 on the phased k_conv
 int voc_plan_upsampler_kernel(const vfx_config& cfg, int cin, int s, int T);
+// One ResStack layer (conv1, conv2) of `channels` channels.  How the plan runs it: two k_conv launches, one fused launch on the raw
+// trunk (resblock.hip, resblock_rw.hip, resblock_r128.hip) or one on the activated fp16 trunk (resblock_w64.hip); whether the tensors
+// between the launches of its stack are fp16 (ResBlockParams::x16; last_stage: the stack feeds the vocoder tail); whether the layers
+// of dilation dil, dil2 run as one launch.
+using VocResLayer = std::pair<VocConvW, VocConvW>;
+enum { VOC_RES_TWO_LAUNCHES = 0, VOC_RES_FUSED = 1, VOC_RES_FUSED_WIDE = 2 };
+int voc_resblock_kind(const vfx_config& cfg, int channels);
+bool voc_resblock_trunk_f16(const vfx_config& cfg, int channels, bool last_stage);
+bool voc_resblock_pair_ok(const vfx_config& cfg, int channels, int dil, int dil2);
+// The fused launch of layer l1 (dilation dil) -- and, l2 != NULL, of the layer behind it (dil2) in the same launch -- on (B, T, channels):
+// the trunk form, slopes, operand mode and the pair fields.  x / y: the raw trunk in and out (fp32, or fp16 where
+// voc_resblock_trunk_f16); xa / ya: the activated fp16 forms (xa: the wide layer's source; ya = fp16(LeakyReLU(y, act_slope)) for the
+// next consumer).  A pointer is NULL where the plan keeps no such tensor: y of the last layer in front of an upsampler on the fp16
+// trunk, x and y of the wide layer on it.  lens: per-clip lengths in units of `rate` positions.  plan_resblock() picks the kernel.
+ResBlockParams voc_resblock_params(const vfx_config& cfg, int channels, bool last_stage, const VocResLayer& l1, const VocResLayer* l2, int B,
+                                   int T, int dil, int dil2, const float* x, const float* xa, float* y, float* ya, float act_slope,
+                                   const int* lens, int rate);
 // The phased launch hp (after finish_params, with tuning set) with the phase segments `phases` runs on k_up16: upsample16_ok, two
 // taps per phase and not VFX_TUNE_NO_FUSED_UPSAMPLERS (upsample16.hip)
 bool upsample16_selected(const TapConvParams& hp, const std::vector<TapSeg>& phases);

@@ -231,6 +231,81 @@ TapConvParams voc_upsample_params(const vfx_config& cfg, const VocConvW& up, int
   return p;
 }
 
+int voc_resblock_kind(const vfx_config& cfg, int channels) {
+  return stack_fused(cfg, channels) ? VOC_RES_FUSED : stack_fused_wide(cfg, channels) ? VOC_RES_FUSED_WIDE : VOC_RES_TWO_LAUNCHES;
+}
+
+bool voc_resblock_trunk_f16(const vfx_config& cfg, int channels, bool last_stage) { return stack_trunk_f16(cfg, channels, last_stage); }
+
+bool voc_resblock_pair_ok(const vfx_config& cfg, int channels, int dil, int dil2) {
+  return cfg.precision == 2 && stack_fused(cfg, channels) &&
+         (resblock_rw_pair_ok(channels, dil, dil2, cfg.tuning) || resblock_r128_pair_ok(channels, dil, dil2, cfg.tuning));
+}
+
+ResBlockParams voc_resblock_params(const vfx_config& cfg, int channels, bool last_stage, const VocResLayer& l1, const VocResLayer* l2, int B,
+                                   int T, int dil, int dil2, const float* x, const float* xa, float* y, float* ya, float act_slope,
+                                   const int* lens, int rate) {
+  const int kind = voc_resblock_kind(cfg, channels);
+  VFX_CHECK(kind != VOC_RES_TWO_LAUNCHES, "vocoder plan: no fused kernel runs a %d-channel ResStack layer of this handle", channels);
+  const bool t16 = stack_trunk_f16(cfg, channels, last_stage);
+  ResBlockParams rp{};
+  rp.w1 = l1.first.w;
+  rp.w2 = l1.second.w;
+  rp.b1 = l1.first.bias;
+  rp.b2 = l1.second.bias;
+  rp.slope = cfg.voc_res_slope;
+  rp.B = B;
+  rp.T = T;
+  rp.C = channels;
+  rp.dil = dil;
+  rp.tuning = cfg.tuning;
+  rp.lens = lens;
+  rp.lens_mul = rate;
+  rp.x16 = t16 ? 1 : 0;
+  if (kind == VOC_RES_FUSED) {
+    // on the raw trunk (fp32, or fp16 with t16): y its next form -- NULL for the last layer in front of an upsampler on the fp16
+    // trunk, which reads ya only -- and ya = fp16(LeakyReLU(y, act_slope)) for that upsampler (16-bit mode)
+    VFX_CHECK(l1.first.mode == l1.second.mode && l1.first.mode == fused_layer_mode(cfg, channels),
+              "vocoder plan: the weights of a fused %d-channel layer are packed for another kernel", channels);
+    VFX_CHECK(x && !xa && (y || (t16 && ya)) && (!ya || cfg.precision == 2),
+              "vocoder plan: a fused %d-channel layer reads the raw trunk and writes it (ya: 16-bit mode; ya alone: fp16 trunk)", channels);
+    rp.x = x;
+    rp.y = y;
+    rp.hionly = cfg.precision == 2;
+    if (ya) {
+      rp.ya = ya;
+      rp.act_slope = act_slope;
+    }
+    if (l2) {
+      // 16-bit mode, C = 64 ((1, 3), (9, 27)) and C = 128 ((1, 3)): two layers of small dilation as one launch -- the tensor
+      // between them is never stored
+      VFX_CHECK(voc_resblock_pair_ok(cfg, channels, dil, dil2), "vocoder plan: layers of dilation %d, %d do not run as a pair", dil, dil2);
+      VFX_CHECK(l2->first.mode == l1.first.mode && l2->second.mode == l1.first.mode,
+                "vocoder plan: the weights of a fused %d-channel layer are packed for another kernel", channels);
+      rp.dil2 = dil2;
+      rp.w1b = l2->first.w;
+      rp.w2b = l2->second.w;
+      rp.b1b = l2->first.bias;
+      rp.b2b = l2->second.bias;
+    }
+  } else {
+    // one launch per layer on the trunk in both forms: conv1 reads the activated fp16 trunk, the residual is the raw one; the
+    // next trunk is written raw and -- unless it only feeds the vocoder tail -- activated for its consumer.  t16: the activated
+    // tensor is the only form of the trunk: no x, no y
+    VFX_CHECK(l1.first.mode == 3 && l1.second.mode == 3, "vocoder plan: the fused wide layer needs fp16 64-channel weights");
+    VFX_CHECK(!l2 && xa && (t16 ? (!x && !y && ya) : (x && y)),
+              "vocoder plan: the fused wide layer runs alone on xa (fp16 trunk: xa -> ya; otherwise x / y beside them)");
+    rp.asrc = 1;
+    rp.x = x;
+    rp.xa = xa;
+    rp.y = y;
+    rp.ya = ya;
+    rp.act_slope = act_slope;
+    rp.hionly = 1;
+  }
+  return rp;
+}
+
 int voc_plan_upsampler_kernel(const vfx_config& cfg, int cin, int s, int T) {
   // a stage behind the first, not the last one: the forms build_vocoder gives such an upsampler
   const bool src_act = up_src_act(cfg, cin, 1);
@@ -419,84 +494,37 @@ void build_vocoder(PlanBuilder& pb, int B, int T, BufRef mel_linear, BufRef wav_
     for (size_t li = 0; li < nlayers; ++li) {
       auto& layer = W->res[st][li];
       if (fuse) {
-        ResBlockParams rp{};
-        rp.x = rel_ptr(cur.raw);
-        rp.x16 = t16 ? 1 : 0;
-        rp.w1 = layer.first.w;
-        rp.w2 = layer.second.w;
-        rp.b1 = layer.first.bias;
-        rp.b2 = layer.second.bias;
-        rp.slope = cfg.voc_res_slope;
-        rp.B = B;
-        rp.T = Tlen;
-        rp.C = up.cout;
-        rp.dil = dil;
-        rp.hionly = cfg.precision == 2;
-        rp.tuning = cfg.tuning;
-        rp.lens = lens_tp;
-        rp.lens_mul = rate;
-        VFX_CHECK(layer.first.mode == layer.second.mode &&
-                      layer.first.mode == fused_layer_mode(cfg, up.cout),
-                  "vocoder plan: the weights of a fused %d-channel layer are packed for another kernel", up.cout);
-        // 16-bit mode, C = 64 ((1, 3), (9, 27)) and C = 128 ((1, 3)): two layers of small dilation as one launch -- the tensor
-        // between them is never stored
-        if (rp.hionly && li + 1 < nlayers && (resblock_rw_pair_ok(up.cout, dil, dil * cfg.voc_dilation_base, cfg.tuning) ||
-                                              resblock_r128_pair_ok(up.cout, dil, dil * cfg.voc_dilation_base, cfg.tuning))) {
-          auto& next = W->res[st][li + 1];
+        // 16-bit mode, C = 64 ((1, 3), (9, 27)) and C = 128 ((1, 3)): two layers of small dilation as one launch
+        const int dil1 = dil;
+        const VocResLayer* next = nullptr;
+        if (li + 1 < nlayers && voc_resblock_pair_ok(cfg, up.cout, dil, dil * cfg.voc_dilation_base)) {
+          next = &W->res[st][li + 1];
           dil *= cfg.voc_dilation_base;
           ++li;
-          rp.dil2 = dil;
-          rp.w1b = next.first.w;
-          rp.w2b = next.second.w;
-          rp.b1b = next.first.bias;
-          rp.b2b = next.second.bias;
         }
         Forms ynew;
         const bool feeds_upsampler = cfg.precision == 2 && li + 1 == nlayers && !last_stage;
-        if (!(t16 && feeds_upsampler)) {  // (fp16 trunk: the upsampler reads ya only -- the raw output is not stored at all)
+        if (!(t16 && feeds_upsampler))  // (fp16 trunk: the upsampler reads ya only -- the raw output is not stored at all)
           ynew.raw = pb.alloc_f(t16 ? act_floats((int64_t)B * Tlen * up.cout) : (int64_t)B * Tlen * up.cout);
-          rp.y = const_cast<float*>(rel_ptr(ynew.raw));
-        }
-        if (feeds_upsampler) {
-          // last layer in front of an upsampler: the activated fp16 form (LeakyReLU(up_slope)) for it
-          ynew.act = pb.alloc_f(act_floats((int64_t)B * Tlen * up.cout));
-          rp.ya = const_cast<float*>(rel_ptr(ynew.act));
-          rp.act_slope = cfg.voc_up_slope;
-        }
-        pb.add_resblock(rp);
+        // last layer in front of an upsampler: the activated fp16 form (LeakyReLU(up_slope)) for it
+        if (feeds_upsampler) ynew.act = pb.alloc_f(act_floats((int64_t)B * Tlen * up.cout));
+        pb.add_resblock(voc_resblock_params(cfg, up.cout, last_stage, layer, next, B, Tlen, dil1, next ? dil : 0, rel_ptr(cur.raw), nullptr,
+                                            ynew.raw != kNone ? const_cast<float*>(rel_ptr(ynew.raw)) : nullptr,
+                                            ynew.act != kNone ? const_cast<float*>(rel_ptr(ynew.act)) : nullptr, cfg.voc_up_slope, lens_tp,
+                                            rate));
         free_forms(cur);
         cur = ynew;
       } else if (fuse_act) {
-        // one launch per layer on the trunk in both forms: conv1 reads the activated fp16 trunk, the residual is the raw
-        // one; the next trunk is written raw and -- unless it only feeds the vocoder tail -- activated for its consumer
-        // (the next layer: LeakyReLU(res_slope); the next upsampler: LeakyReLU(up_slope))
+        // one launch per layer (resblock_w64.hip); the next trunk activated for its consumer (the next layer: LeakyReLU(res_slope);
+        // the next upsampler: LeakyReLU(up_slope)) unless it only feeds the vocoder tail
         const bool last_layer = li + 1 == nlayers;
         Forms y2;
         if (!t16) y2.raw = pb.alloc_f((int64_t)B * Tlen * up.cout);
         if (!(last_layer && last_stage)) y2.act = pb.alloc_f(act_floats((int64_t)B * Tlen * up.cout));
-        VFX_CHECK(layer.first.mode == 3 && layer.second.mode == 3, "vocoder plan: the fused wide layer needs fp16 64-channel weights");
-        ResBlockParams rp{};
-        rp.asrc = 1;
-        rp.x16 = t16 ? 1 : 0;  // the activated tensor is the only form of the trunk: no x, no y
-        rp.tuning = cfg.tuning;
-        rp.lens = lens_tp;
-        rp.lens_mul = rate;
-        rp.x = t16 ? nullptr : rel_ptr(cur.raw);
-        rp.xa = rel_ptr(cur.act);
-        rp.y = t16 ? nullptr : const_cast<float*>(rel_ptr(y2.raw));
-        rp.ya = y2.act != kNone ? const_cast<float*>(rel_ptr(y2.act)) : nullptr;
-        rp.act_slope = last_layer ? cfg.voc_up_slope : cfg.voc_res_slope;
-        rp.w1 = layer.first.w;
-        rp.w2 = layer.second.w;
-        rp.b1 = layer.first.bias;
-        rp.b2 = layer.second.bias;
-        rp.slope = cfg.voc_res_slope;
-        rp.B = B;
-        rp.T = Tlen;
-        rp.C = up.cout;
-        rp.dil = dil;
-        rp.hionly = 1;
-        pb.add_resblock(rp);
+        pb.add_resblock(voc_resblock_params(cfg, up.cout, last_stage, layer, nullptr, B, Tlen, dil, 0, t16 ? nullptr : rel_ptr(cur.raw),
+                                            rel_ptr(cur.act), t16 ? nullptr : const_cast<float*>(rel_ptr(y2.raw)),
+                                            y2.act != kNone ? const_cast<float*>(rel_ptr(y2.act)) : nullptr,
+                                            last_layer ? cfg.voc_up_slope : cfg.voc_res_slope, lens_tp, rate));
         free_forms(cur);
         cur = y2;
       } else if (!act_ok) {

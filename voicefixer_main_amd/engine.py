@@ -1135,6 +1135,29 @@ class Engine:
             self._stream()), "vfx_op_voc_final")
         return (wav, peak) if want_peak else wav
 
+    RESBLOCK_INFO = ("rw", "r128", "asrc", "fold", "tile_m", "TWo", "TH", "tiles_h", "tiles_w", "x16", "W1", "patch_rows")
+
+    def op_voc_resblock(self, x, layer, dil, layer2=None, dil2=0, slope=0.01, act_slope=0.2, want_raw=True, want_act=False, lens=None,
+                        lens_mul=1):
+        """One fused ResStack launch of the vocoder plan on x (B, T, C): layer = (w1, b1, w2, b2) in torch layout, layer2 / dil2 the
+        second layer of a pair.  -> (y raw or None, ya activated or None, info): both widened from the stored form, NaN where the
+        launch stored nothing; info = what plan_resblock chose (RESBLOCK_INFO).  Raises where the plan refuses the combination."""
+        x = _dev_f32(x, self.device)
+        B, T, C = x.shape
+        la = [_host(a) for a in layer]
+        lb = [_host(a) for a in layer2] if layer2 is not None else [None] * 4
+        y = torch.full_like(x, float("nan")) if want_raw else None
+        ya = torch.full_like(x, float("nan")) if want_act else None
+        ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        if ln is not None and ln.shape != (B,):
+            raise ValueError("op_voc_resblock: %d lengths for %d clips" % (ln.size, B))
+        info = (ctypes.c_int * len(self.RESBLOCK_INFO))()
+        _lib.check(_lib.load_test().vfx_op_voc_resblock(
+            self.h, _ptr(x), B, T, C, *[_hptr(a) for a in la], int(dil), *[_hptr(a) for a in lb], int(dil2 if layer2 is not None else 0),
+            float(slope), float(act_slope), int(bool(want_raw)), int(bool(want_act)), _hptr(ln), int(lens_mul), _ptr(y), _ptr(ya), info,
+            self._stream()), "vfx_op_voc_resblock")
+        return y, ya, dict(zip(self.RESBLOCK_INFO, info))
+
     # the STFT / ISTFT front end and the glue launches of a restore call (include/vfx_test.h); every output starts as NaN
     @staticmethod
     def _lens_arg(lens, B, name):
