@@ -84,15 +84,25 @@ def dact(t, e, slope, p):
     return d
 
 
-def _layer(a, da, res, dres, layer, d, slope, p, bounds=True):
+F16_MAX = 65504.0
+
+
+def _layer(a, da, res, dres, layer, d, slope, p, bounds=True, sat=None):
+    """sat: None, or how the 16-bit kernel of the form converts h -- 'packed' (clamp to +-65504, then LeakyReLU: resblock_rw / r128 /
+    w64) or 'after' (LeakyReLU, then clamp: k_resblock) -- so that g is the CLAMPED operand; h stays the value in front of it."""
     w1, b1, w2, b2 = layer
     C = a.shape[1]
     w1q, w2q = _operand(w1, p), _operand(w2, p)
     h = conv64(a, w1q, d) + b1.double()
-    g = _act64(h, 1, slope)
+    if sat == "packed":
+        g = _act64(h.clamp(-F16_MAX, F16_MAX), 1, slope)
+    else:
+        g = _act64(h, 1, slope)
+        if sat == "after":
+            g = g.clamp(-F16_MAX, F16_MAX)
     y = res + conv64(g, w2q, 1) + b2.double()
     if not bounds:
-        return dict(a=a, h=h, g=g, y=y, e2=None)
+        return dict(a=a, h=h, g=g, y=y, e1=None, e2=None)
     S1 = conv64(a.abs() + da, w1q.abs(), d)
     e1 = conv64(da, w1q.abs(), d) + _bar(h, S1, 3 * C, p, INF, extra=b1.double().abs()[None, :])[0]
     dg = dact(h, e1, slope, p)
@@ -104,11 +114,16 @@ def _layer(a, da, res, dres, layer, d, slope, p, bounds=True):
     return dict(a=a, h=h, g=g, y=y, e1=e1, e2=e2)
 
 
-def resstack_ref(x, layers, dils, slope, act_slope, p, tol, *, x16=False, asrc=False, bounds=True):
+def resstack_ref(x, layers, dils, slope, act_slope, p, tol, *, x16=False, asrc=False, bounds=True, sat=None):
     """x (Tb, C) fp32: ONE clip's own positions.  layers: one or two (w1, b1, w2, b2) in torch layout; dils: their dilations.
-    -> dict: y, ya (float64 references), bar_y32 / bar_y16 (y stored as fp32 / fp16), bar_ya, and the intermediates a, g, mid (a2, g2).
-    bounds = False: the references alone (the exact-arithmetic data needs no bar)."""
+    -> dict: y, ya (float64 references), bar_y32 / bar_y16 (y stored as fp32 / fp16), bar_ya, and the intermediates a, g, mid (a2, g2),
+    h and e1 (conv1 + b1 and its bound; h2, e1_2 of a pair's second layer), e_mid (the bound of mid).
+    bounds = False: the references alone (the exact-arithmetic data needs no bar).
+    sat ('packed' / 'after', see _layer): the arithmetic of the 16-bit mode where a value leaves the fp16 range -- every conversion
+    clamps to +-65504 (a NaN source becomes -65504: v_med3), the values in front of the conversions (x_src, h, mid, y) stay unclamped,
+    y16 / ya are the stored (clamped) forms.  Without out-of-range values it changes nothing."""
     x = x.float()
+    x_src = None
     if asrc:
         xa = _act32(x, 1, slope).half()
         a, da = xa.double(), torch.zeros_like(x, dtype=torch.float64)
@@ -125,17 +140,24 @@ def resstack_ref(x, layers, dils, slope, act_slope, p, tol, *, x16=False, asrc=F
     else:
         res = x.double()
         # (p = 0, tests/test_resstack_f64_host.py: nothing rounds, the activation neither -- the oracle's layer)
-        a = _operand(_act32(x, 1, slope), p) if p else _act64(x.double(), 1, slope)
+        if sat:   # the value the kernel converts, then what the conversion makes of it
+            x_src = _act32(x, 1, slope).double()
+            a = torch.nan_to_num(_act32(x, 1, slope), nan=-F16_MAX).clamp(-F16_MAX, F16_MAX).half().double()
+        else:
+            a = _operand(_act32(x, 1, slope), p) if p else _act64(x.double(), 1, slope)
         da = torch.zeros_like(a)
-    L = _layer(a, da, res, torch.zeros_like(res), layers[0], dils[0], slope, p, bounds)
-    out = dict(a=L["a"], g=L["g"], mid=None, slope=slope)
+    L = _layer(a, da, res, torch.zeros_like(res), layers[0], dils[0], slope, p, bounds, sat)
+    out = dict(a=L["a"], g=L["g"], mid=None, slope=slope, x_src=x_src, h=L["h"], e1=L["e1"], h2=None)
     if len(layers) == 2:
         y1, e_y1 = L["y"], L["e2"]
         a2 = _act64(y1, 1, slope)   # unrounded, as g: the kernel's operand lies within dact(y1, e2(1)) of it
-        L2 = _layer(a2, dact(y1, e_y1, slope, p) if bounds else None, y1, e_y1, layers[1], dils[1], slope, p, bounds)
-        out.update(mid=y1, a2=a2, g2=L2["g"])
+        if sat:
+            a2 = a2.clamp(-F16_MAX, F16_MAX)
+        L2 = _layer(a2, dact(y1, e_y1, slope, p) if bounds else None, y1, e_y1, layers[1], dils[1], slope, p, bounds, sat)
+        out.update(mid=y1, e_mid=e_y1, a2=a2, g2=L2["g"], h2=L2["h"], e1_2=L2["e1"])
         L = L2
-    out.update(y=L["y"], e2=L["e2"], cap=(2.0 if len(layers) == 2 else 1.0) * tol * max(1.0, float(L["y"].abs().max())))
+    yf = L["y"][torch.isfinite(L["y"])]
+    out.update(y=L["y"], e2=L["e2"], sat=sat, cap=(2.0 if len(layers) == 2 else 1.0) * tol * max(1.0, float(yf.abs().max()) if yf.numel() else 1.0))
     return with_act_slope(out, act_slope)
 
 
@@ -144,6 +166,9 @@ def with_act_slope(ref, act_slope):
     out = dict(ref)
     y, e2, cap = ref["y"], ref["e2"], ref["cap"]
     out["ya"] = ya = _act64(y, 1, act_slope)
+    if ref.get("sat"):   # the stored forms of out-of-range values
+        out["ya"] = ya = ya.clamp(-F16_MAX, F16_MAX)
+        out["y16"] = y.clamp(-F16_MAX, F16_MAX)
     if e2 is not None:
         capt = torch.full_like(y, cap)
         out.update(bar_y32=torch.minimum(e2, capt), bar_y16=torch.minimum(e2 + r_p(y.abs() + e2, 2), capt),
@@ -240,64 +265,115 @@ def _conv32(a_parts, w_parts, d, drop=None):
     return c(a_parts[0], w_parts[0])
 
 
+def _f16sat(t):
+    """The kernels' conversion (conv_common.h: pack_f16x2): clamp to +-65504 -- a NaN becomes -65504 -- then round."""
+    return torch.nan_to_num(t.float(), nan=-F16_MAX).clamp(-F16_MAX, F16_MAX).half()
+
+
 def _parts(t, p):
     t = t.float()
     if p == 2:
-        return (t.half().float(),)
+        return (_f16sat(t).float(),)
     hi = t.bfloat16().float()
     return (hi, (t - hi).bfloat16().float())
 
 
-def emulate(xrow, Tb, layers, dils, slope, act_slope, p, *, x16=False, asrc=False, packed=False, defect=None, where=None):
+def emulate(xrow, Tb, layers, dils, slope, act_slope, p, *, x16=False, asrc=False, packed=False, defect=None, where=None, record=False,
+            want_raw=True, want_act=True):
     """xrow (T, C) fp32: a clip's row of the batch tensor, whatever lies past Tb included.  -> (y, ya) fp32 (Tb, C): y in its stored form
     (fp16 values on the fp16 trunk), ya = fp16(LeakyReLU32(y unrounded, act_slope)).  packed: the packed fp16 activations of
-    resblock_rw / r128 / w64.  defect: None or one of DEFECTS; drop_tap drops tap 0 of conv2 at output position `where`."""
+    resblock_rw / r128 / w64.  defect: None or one of DEFECTS; drop_tap drops tap 0 of conv2 at output position `where`.
+
+    record = True: -> (y, ya, rec), rec = {site: bool}, the saturation record of every conversion site of the 16-bit mode (X, H, MID, H2,
+    Y, YA: tests/f16_flag_ref.py) by the kernels' rule -- mask the positions that do not count (past the clip's end), then record
+    !(|v| <= 65504) -- with the defects of FLAG_DEFECTS: 'record_before_mask' records every position of the row, computed from
+    whatever the row holds past the clip's end (the outputs are the healthy ones); 'site_silent:<site>' never reports that site;
+    'record_ignores_nan' writes the predicate as |v| > 65504.  want_raw / want_act: the outputs the launch stores (a site of an
+    output that is not stored converts nothing)."""
+    if defect == "record_before_mask":
+        y, ya, _ = _emulate(xrow, Tb, layers, dils, slope, act_slope, p, x16, asrc, packed, None, where, want_raw, want_act)
+        rec = _emulate(xrow, Tb, layers, dils, slope, act_slope, p, x16, asrc, packed, defect, where, want_raw, want_act)[2]
+    else:
+        y, ya, rec = _emulate(xrow, Tb, layers, dils, slope, act_slope, p, x16, asrc, packed, defect, where, want_raw, want_act)
+    return (y, ya, rec) if record else (y, ya)
+
+
+def _emulate(xrow, Tb, layers, dils, slope, act_slope, p, x16, asrc, packed, defect, where, want_raw, want_act):
     T, C = xrow.shape
     src = xrow.float().clone()
-    if defect != "x_past_end":
+    unmasked = defect == "record_before_mask"
+    if defect != "x_past_end" and not unmasked:
         src[Tb:] = 0.0            # positions past the clip's end read as zero
     inside = torch.zeros(T, 1)
     inside[:Tb] = 1.0
     if defect == "swap_pair":
         layers = (layers[1], layers[0])
+    rec = {}
 
-    def act(t):
-        return _parts(lrelu_packed16(t.float().half(), slope) if (p == 2 and packed) else _act32(t, 1, slope), p)
+    def note(site, v):
+        """The record of one site: v (T, C), the fp32 values in front of the conversion."""
+        if p != 2 or defect == "site_silent:" + site:
+            return
+        if not unmasked:
+            v = v[:Tb]
+        bad = (v.abs() > F16_MAX) if defect == "record_ignores_nan" else ~(v.abs() <= F16_MAX)
+        rec[site] = rec.get(site, False) or bool(bad.any())
 
-    def layer(parts, res, lay, d):
+    def act(t, site=None):
+        if p == 2 and packed:
+            if site:
+                note(site, t)
+            return _parts(lrelu_packed16(_f16sat(t), slope), p)
+        t = _act32(t, 1, slope)
+        if site:
+            note(site, t)
+        return _parts(t, p)
+
+    def layer(parts, res, lay, d, site):
         w1, b1, w2, b2 = lay
         h = _conv32(parts, _parts(w1, p), d) + b1
-        g = act(h)
+        g = act(h, site)
         if defect == "h_bf16":
             g = (_act32(h, 1, slope).bfloat16().float(),) + ((torch.zeros_like(h),) if p == 1 else ())
         if defect == "h_past_end":   # left at LeakyReLU(b1) instead of zero
             fill = act(b1[None, :].expand(T, -1).contiguous())
             g = tuple(gp * inside + fp * (1 - inside) for gp, fp in zip(g, fill))
-        else:
+        elif not unmasked:
             g = tuple(gp * inside for gp in g)     # h IS zero past the clip's end
         if defect == "res_shift":
             res = torch.cat([torch.zeros(1, C), res[:-1]])
         return res + _conv32(g, _parts(w2, p), 1, (where, 0) if defect == "drop_tap" else None) + b2
 
     if asrc:
-        xa = _act32(src, 1, slope).half().float()
+        xa = _f16sat(_act32(src, 1, slope)).float()   # (the producer's form: given, not converted by this launch)
         parts = (xa,)
         res = torch.minimum(xa, xa * (np.float32(1.0) / np.float32(slope))) if x16 else src
     elif x16:
-        res = src.half().float()
-        parts = act(res)
+        res = src.clamp(-F16_MAX, F16_MAX).half().float()   # (the producer's clamp)
+        parts = _parts(lrelu_packed16(res, slope), p) if packed else _parts(_act32(res, 1, slope), p)   # fp16 in, nothing to convert
     else:
         res = src
-        parts = act(src)
-    y = layer(parts, res, layers[0], dils[0])
+        t = _act32(src, 1, slope)
+        note("X", t)
+        parts = _parts(t, p)
+    y = layer(parts, res, layers[0], dils[0], "H")
     if len(layers) == 2:
-        y = y * inside               # the second layer's source and residual: the first one's output, zero past the clip's end
-        y = layer(act(y), y, layers[1], dils[1])
+        if not unmasked:
+            y = y * inside           # the second layer's source and residual: the first one's output, zero past the clip's end
+        t = _act32(y, 1, slope)
+        note("MID", t)
+        y = layer(_parts(t, p), y, layers[1], dils[1], "H2")
+    if x16 and not asrc and want_raw:
+        note("Y", y)
+    if want_act:
+        note("YA", _act32(y, 1, act_slope))
     y = y[:Tb]
-    ya = _act32(y, 1, slope if defect == "ya_slope" else act_slope).half().float()
+    ya = _f16sat(_act32(y, 1, slope if defect == "ya_slope" else act_slope)).float()
     if x16 and not asrc:
-        y = y.half().float()
-    return y, ya
+        y = _f16sat(y).float()
+    return y, ya, rec
 
 
 DEFECTS = ("h_past_end", "x_past_end", "ya_slope", "drop_tap", "res_shift", "h_bf16", "swap_pair")
+FLAG_DEFECTS = ("record_before_mask", "site_silent", "record_ignores_nan")
+

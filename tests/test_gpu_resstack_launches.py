@@ -157,7 +157,9 @@ def _run(eng, form, dils, sets, kind):
                 if kind == "exact":
                     assert R.exact_fits(base[T]), (what, "the exact data does not fit fp16")
             ref = R.with_act_slope(base[T], act_slope)
+            eng.take_flags()
             y, ya, info = eng.op_voc_resblock(master[None, :T], l1, dils[0], **kw)
+            assert eng.take_flags() == 0, (what, "a device flag was raised on O(1) data")
             _family(form, info, what)
             one[T] = (y, ya)
             for got, key, bar in ((y, "y", "bar_y16" if (form.x16 and not form.asrc) else "bar_y32"), (ya, "ya", "bar_ya")):
@@ -175,7 +177,10 @@ def _run(eng, form, dils, sets, kind):
             x = torch.full((3, T3, C), float("nan"))
             for b, Tb in enumerate(lens):
                 x[b, :Tb] = master[:Tb]
+            eng.take_flags()
             y, ya, info = eng.op_voc_resblock(x, l1, dils[0], lens=lens, **kw)
+            # (x past each clip's end is NaN: nothing computed from it may raise VFX_FLAG_F16_SATURATED)
+            assert eng.take_flags() == 0, (form.name, dils, kind, lens, "a device flag was raised from positions past a clip's end")
             _family(form, info, (form.name, dils, lens))
             for got, k in ((y, 0), (ya, 1)):
                 if got is None:

@@ -63,8 +63,10 @@ def _run_upsample(eng, p, Cin, s, T, B, seed, src_act, form, lens):
     b = _rand((Cout,), seed + 2, 0.1)
     want_raw = form in ("raw", "act+raw")
     act_slope = {"raw": None, "act": RES_SLOPE, "act+raw": RES_SLOPE, "trunk": 1.0}[form]
+    eng.take_flags()
     y, ya, up16 = eng.op_voc_upsample(x, w.numpy(), b.numpy(), s, UP_SLOPE, src_act=src_act, want_raw=want_raw, act_slope=act_slope,
                                       lens=lens)
+    assert eng.take_flags() == 0, ("a device flag was raised on O(1) data", Cin, s, T, B)
     tol = eng.tol['conv']
     n = 2 * Cin
     for b_ in range(B):
@@ -151,8 +153,10 @@ def _conv_case(eng, p, Cin, Cout, T, B, K, dil, seed, *, reflect=False, src_act=
     res = _rand((B, T, Cout), seed + 3) if residual else None
     if res is not None:
         res[:, ::2, 1::3] = -res[:, ::2, 1::3].abs()   # negative trunk values: the inverted LeakyReLU branch
+    eng.take_flags()
     y, ya = eng.op_voc_conv1d(x, w.numpy(), b.numpy(), dil=dil, reflect=reflect, src_act=src_act, act=act, slope=slope, residual=res,
                               residual_act=residual_act, want_raw=want_raw, next_act=next_act, next_slope=next_slope, lens=lens)
+    assert eng.take_flags() == 0, ("a device flag was raised on O(1) data", Cin, Cout, T, K, dil)
     tol = eng.tol['conv']
     wq = _operand(w, p)
     for b_ in range(B):
@@ -243,7 +247,9 @@ def test_voc_final(engine, x_f16):
         x = _rand((B, T, C), 800 + i)
         w = _rand((1, C, 7), 850 + i, 1.0 / np.sqrt(7 * C))
         bias = 0.05
+        engine.take_flags()
         wav = engine.op_voc_final(x, w.numpy(), bias, UP_SLOPE, x_f16=x_f16, lens=lens).cpu()
+        assert engine.take_flags() == 0, ("a device flag was raised on O(1) data", B, T, C)
         xs = x.half().float() if x_f16 else x
         for b_ in range(B):
             L = T if lens is None else lens[b_]

@@ -77,6 +77,25 @@ __device__ __forceinline__ unsigned pack_f16x2_sat16(float a, float b, bool vali
   return p;
 }
 __device__ __forceinline__ bool f16_sat16_bad(unsigned s) { return (s & 0xffffu) >= 0x7bffu || (s >> 16) >= 0x7bffu; }
+// The same rule for the OUTPUT epilogues: an accumulator of the tile's grid whose store is dropped -- an edge pixel of the grid
+// (computed from clamped h rows), a position past the end of the sequence or of its clip, the overhang of a folded tile -- can hold
+// anything (a bias that only masked positions keep, two taps of one h value) and must not raise the flag.  The conversions of ONE
+// position keep a record of their own, which is folded into the running one only where the position is stored: one v_cndmask + one
+// max per position, the conversions and the stored bits untouched (tests/test_gpu_f16_flag_launches.py: masked_bias, edge_pixel,
+// dropped_output).
+// ... and for the packed record without any instruction per pair: the |.| mask of the record itself is the position's mask
+// (f16_sat16_keep(stored): one v_cndmask per position; the v_and of pack_f16x2_sat16 takes it from a register instead of a literal)
+__device__ __forceinline__ unsigned f16_sat16_keep(bool stored) { return stored ? 0x7fff7fffu : 0u; }
+__device__ __forceinline__ unsigned pack_f16x2_sat16k(float a, float b, unsigned keep, unsigned& sat16) {
+  const unsigned p = pack_f16x2(a, b);
+  const u16x2 m = __builtin_bit_cast(u16x2, p & keep);
+  sat16 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, sat16), m));
+  return p;
+}
+__device__ __forceinline__ void f16_sat_bits_fold(unsigned& sat, unsigned row, bool stored) { sat = max(sat, stored ? row : 0u); }
+__device__ __forceinline__ void f16_sat16_fold(unsigned& sat16, unsigned row16, bool stored) {
+  sat16 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, sat16), __builtin_bit_cast(u16x2, stored ? row16 : 0u)));
+}
 __device__ __forceinline__ unsigned lrelu_f16x2(unsigned p, f16x2 slope2) {
   const f16x2 h = __builtin_bit_cast(f16x2, p);
   return __builtin_bit_cast(unsigned, __builtin_elementwise_max(h, h * slope2));

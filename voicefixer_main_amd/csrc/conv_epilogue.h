@@ -149,8 +149,9 @@ __device__ __forceinline__ void conv_epilogue(const TapConvParams& p, float* sme
             h23 = __builtin_bit_cast(unsigned, __builtin_convertvector(c23, ce_f16x2));
             l01 = l23 = 0u;
             // the predicate of conv_common.h's f16_out_of_range (this header is also used without it)
-            f16_sat = f16_sat | !(__builtin_fabsf(u[0]) <= 65504.f) | !(__builtin_fabsf(u[1]) <= 65504.f) |
-                      !(__builtin_fabsf(u[2]) <= 65504.f) | !(__builtin_fabsf(u[3]) <= 65504.f);
+            // -- counted only where the pixel is stored: a tile's pixels outside the image or past a clip's end hold anything
+            f16_sat = f16_sat | ((opix[q] >= 0) & (!(__builtin_fabsf(u[0]) <= 65504.f) | !(__builtin_fabsf(u[1]) <= 65504.f) |
+                                                   !(__builtin_fabsf(u[2]) <= 65504.f) | !(__builtin_fabsf(u[3]) <= 65504.f)));
           } else {
             h01 = __builtin_bit_cast(unsigned, __builtin_convertvector(ce_f32x2{u[0], u[1]}, ce_bf16x2));
             h23 = __builtin_bit_cast(unsigned, __builtin_convertvector(ce_f32x2{u[2], u[3]}, ce_bf16x2));

@@ -576,6 +576,7 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
         const bool ok = PAIR ? ((m >= 2 + d2) & (m <= MT - 3 - d2))
                              : ((li < TH) & (lj >= 1) & (lj <= W1 - 2) & (!p.fold | (j0 + lj - 1 < d)));
         const unsigned rowoff = ok ? (unsigned)pos * (unsigned)(C * 2) + (unsigned)(ch * 64 + 16 * lhe) : kOob;  // (ok: pos >= 0)
+        const unsigned keep16 = f16_sat16_keep(ok & ((unsigned)pos < (unsigned)Tb));  // the record counts stored positions only (conv_common.h)
 #pragma unroll
         for (int jp = 0; jp < 4; jp += 2) {
           f32x4 v[2];
@@ -585,8 +586,8 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
             for (int e = 0; e < 4; ++e) v[r][e] = acc[n][a][4 * (jp + r) + e] + bv[jp + r][e];
           // lanes 0-31 keep their run jp and receive the partner's run jp; lanes 32-63 receive the partner's run jp + 1 and keep theirs
           if (have_y) {
-            const auto s0 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16(v[0][0], v[0][1], true, sat16), pack_f16x2_sat16(v[1][0], v[1][1], true, sat16), false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16(v[0][2], v[0][3], true, sat16), pack_f16x2_sat16(v[1][2], v[1][3], true, sat16), false, false);
+            const auto s0 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16k(v[0][0], v[0][1], keep16, sat16), pack_f16x2_sat16k(v[1][0], v[1][1], keep16, sat16), false, false);
+            const auto s1 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16k(v[0][2], v[0][3], keep16, sat16), pack_f16x2_sat16k(v[1][2], v[1][3], keep16, sat16), false, false);
             const u32x4 w = {s0[0], s1[0], s0[1], s1[1]};
 #ifdef VFX_ABL_NOSTORE  // timing-only build (wrong results): what the direct stores cost
             asm volatile("" : : "v"(w));
@@ -601,8 +602,8 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
               f32x4 u;
 #pragma unroll
               for (int e = 0; e < 4; ++e) u[e] = fmaxf(v[r][e], v[r][e] * aslope);
-              q2[r][0] = pack_f16x2_sat16(u[0], u[1], true, sat16);
-              q2[r][1] = pack_f16x2_sat16(u[2], u[3], true, sat16);
+              q2[r][0] = pack_f16x2_sat16k(u[0], u[1], keep16, sat16);
+              q2[r][1] = pack_f16x2_sat16k(u[2], u[3], keep16, sat16);
             }
             const auto s0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
             const auto s1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
@@ -659,8 +660,11 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
                            : ((li < TH) & (lj >= 1) & (lj <= W1 - 2) & ((unsigned)pos < (unsigned)Tb) & (!p.fold | (j0 + lj - 1 < d)));
       const f32x4 val = *reinterpret_cast<const f32x4*>(smem + m * LDO + 4 * c4) + bv + keep[q];  // + the residual: this thread's own rows
       const unsigned off = (unsigned)(img * T + pos) * (unsigned)(C * 4) + 16u * c4;
+      unsigned rs = 0;  // this position's record: counted only where it is stored (conv_common.h)
       if constexpr (X16) {
-        const u32x2 w = {pack_f16x2(val[0], val[1], ya_sat), pack_f16x2(val[2], val[3], ya_sat)};
+        const u32x2 w = {pack_f16x2(val[0], val[1], rs), pack_f16x2(val[2], val[3], rs)};
+        f16_sat_bits_fold(ya_sat, rs, ok & (p.y != nullptr));
+        rs = 0;
         __builtin_amdgcn_raw_buffer_store_b64(w, ry, (int)(ok ? off / 2 : kOob), 0, 0);
       } else {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), ry, (int)(ok ? off : kOob), 0, 0);
@@ -670,7 +674,8 @@ __global__ __launch_bounds__(256, 2) void k_resblock_r128(const ResBlockParams* 
         f32x4 u;
 #pragma unroll
         for (int e = 0; e < 4; ++e) u[e] = fmaxf(val[e], val[e] * aslope);
-        const unsigned h01 = pack_f16x2(u[0], u[1], ya_sat), h23 = pack_f16x2(u[2], u[3], ya_sat);
+        const unsigned h01 = pack_f16x2(u[0], u[1], rs), h23 = pack_f16x2(u[2], u[3], rs);
+        f16_sat_bits_fold(ya_sat, rs, ok);
         // quad_perm [1,0,3,2]: the even lane of a pair collects the pair's 8 consecutive channels (16 bytes)
         const unsigned g0 = (unsigned)__builtin_amdgcn_mov_dpp((int)h01, 0xB1, 0xf, 0xf, false);
         const unsigned g1 = (unsigned)__builtin_amdgcn_mov_dpp((int)h23, 0xB1, 0xf, 0xf, false);

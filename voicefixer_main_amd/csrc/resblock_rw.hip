@@ -292,7 +292,9 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw(const ResBlockParams* _
 #pragma unroll
       for (int a = 0; a < WM; ++a) {
         const int m = (wm * WM + a) * 32 + l31_v;
-        const bool hval = (unsigned)(base_h + (SECOND ? m : hrel_of(m))) < (unsigned)T;
+        // (a pair's second h is right for m = 1 + d2 .. MT - 2 - d2 only -- the indices its stored outputs read; outside them it
+        // is computed from the two zeroed y1 rows and clamped rows: discarded, so masked in front of the record like the rest)
+        const bool hval = (!SECOND | ((m >= 1 + d2) & (m <= MT - 2 - d2))) & ((unsigned)(base_h + (SECOND ? m : hrel_of(m))) < (unsigned)T);
         char* rowp = hbuf + m * ROWB + 8 * lh;
         const int key = (m >> 1) & 7;
 #pragma unroll
@@ -438,7 +440,9 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw(const ResBlockParams* _
             f32x4 u;
 #pragma unroll
             for (int e = 0; e < 4; ++e) u[e] = fmaxf(val[e], val[e] * aslope);
-            const unsigned h01 = pack_f16x2(u[0], u[1], sat), h23 = pack_f16x2(u[2], u[3], sat);
+            unsigned rs = 0;  // this position's record: counted only where it is stored (conv_common.h)
+            const unsigned h01 = pack_f16x2(u[0], u[1], rs), h23 = pack_f16x2(u[2], u[3], rs);
+            f16_sat_bits_fold(sat, rs, ok);
             const unsigned g0 = (unsigned)__builtin_amdgcn_mov_dpp((int)h01, 0xB1, 0xf, 0xf, false);
             const unsigned g1 = (unsigned)__builtin_amdgcn_mov_dpp((int)h23, 0xB1, 0xf, 0xf, false);
             const u32x4 w = {h01, h23, g0, g1};
@@ -696,7 +700,8 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw16(const ResBlockParams*
 #pragma unroll
       for (int a = 0; a < WM; ++a) {
         const int m = (wm * WM + a) * 32 + l31;
-        const bool hval = (unsigned)(base_h + (SECOND ? m : hrel[a])) < (unsigned)Tb;
+        // (a pair's second h: right for m = 1 + d2 .. MT - 2 - d2 only, see k_resblock_rw)
+        const bool hval = (!SECOND | ((m >= 1 + d2) & (m <= MT - 2 - d2))) & ((unsigned)(base_h + (SECOND ? m : hrel[a])) < (unsigned)Tb);
         char* rowp = hbuf + m * ROWB + 8 * lh;
         const int key = (m >> 1) & 7;
 #pragma unroll
@@ -821,6 +826,7 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw16(const ResBlockParams*
         // an output pixel of the tile's grid, inside the row of d samples (folded tiles: the last tile column may stick out)
         const bool ok = (orel[a] >= 0) & (PAIR | !p.fold | (j0 + ljt[a] - 1 < d));
         const unsigned rowoff = ok ? (unsigned)(base_h + orel[a]) * (unsigned)(C * 2) + lane_off : kOob;  // (past the clip: out of range)
+        const unsigned keep16 = f16_sat16_keep(ok & ((unsigned)(base_h + orel[a]) < (unsigned)Tb));  // the record counts stored positions only (conv_common.h)
 #pragma unroll
         for (int jp = 0; jp < 4; jp += 2) {
           f32x4 v[2];
@@ -833,8 +839,8 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw16(const ResBlockParams*
             }
           // lanes 0-31 keep their run jp and receive the partner's run jp; lanes 32-63 receive the partner's run jp + 1 and keep theirs
           if (have_y) {
-            const auto s0 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16(v[0][0], v[0][1], true, sat16), pack_f16x2_sat16(v[1][0], v[1][1], true, sat16), false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16(v[0][2], v[0][3], true, sat16), pack_f16x2_sat16(v[1][2], v[1][3], true, sat16), false, false);
+            const auto s0 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16k(v[0][0], v[0][1], keep16, sat16), pack_f16x2_sat16k(v[1][0], v[1][1], keep16, sat16), false, false);
+            const auto s1 = __builtin_amdgcn_permlane32_swap(pack_f16x2_sat16k(v[0][2], v[0][3], keep16, sat16), pack_f16x2_sat16k(v[1][2], v[1][3], keep16, sat16), false, false);
             const u32x4 w = {s0[0], s1[0], s0[1], s1[1]};
 #ifdef VFX_ABL_NOSTORE  // timing-only build (wrong results): what the direct stores cost
             asm volatile("" : : "v"(w));
@@ -849,8 +855,8 @@ __global__ __launch_bounds__(NTHR, 2) void k_resblock_rw16(const ResBlockParams*
               f32x4 u;
 #pragma unroll
               for (int e = 0; e < 4; ++e) u[e] = fmaxf(v[r][e], v[r][e] * aslope);
-              q2[r][0] = pack_f16x2_sat16(u[0], u[1], true, sat16);
-              q2[r][1] = pack_f16x2_sat16(u[2], u[3], true, sat16);
+              q2[r][0] = pack_f16x2_sat16k(u[0], u[1], keep16, sat16);
+              q2[r][1] = pack_f16x2_sat16k(u[2], u[3], keep16, sat16);
             }
             const auto s0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
             const auto s1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);

@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256, 2) void k_resblock_w64(const ResBlockParams* _
         const int pos = base_h + li * rowstride + lj;
         const bool ok = (li < TH) & (lj >= 1) & (lj <= W1 - 2) & ((unsigned)pos < (unsigned)Tb) & (!p.fold | (j0 + lj - 1 < d));
         const unsigned rowoff = ok ? (unsigned)(img * T + pos) * (unsigned)(C * 2) + (unsigned)((2 * we + cb) * 64 + 16 * lhe) : kOob;
+        unsigned rs = 0;  // this position's record: counted only where it is stored (conv_common.h)
 #pragma unroll
         for (int jp = 0; jp < 4; jp += 2) {
           unsigned q[2][2];  // [run jp, jp + 1][channels 0-1, 2-3]
@@ -382,8 +383,8 @@ __global__ __launch_bounds__(256, 2) void k_resblock_w64(const ResBlockParams* _
               const float v = acc[cb][a][4 * (jp + r) + e] + b2v[jp + r][e];
               u[e] = fmaxf(v, v * aslope);
             }
-            q[r][0] = pack_f16x2(u[0], u[1], ya_sat);
-            q[r][1] = pack_f16x2(u[2], u[3], ya_sat);
+            q[r][0] = pack_f16x2(u[0], u[1], rs);
+            q[r][1] = pack_f16x2(u[2], u[3], rs);
           }
           // lanes 0-31 keep their run jp and receive the partner's run jp; lanes 32-63 receive the partner's run jp + 1 and keep theirs
           const auto s0 = __builtin_amdgcn_permlane32_swap(q[0][0], q[1][0], false, false);
@@ -395,6 +396,7 @@ __global__ __launch_bounds__(256, 2) void k_resblock_w64(const ResBlockParams* _
           __builtin_amdgcn_raw_buffer_store_b128(w, rya, (int)(rowoff + (unsigned)(16 * jp)), 0, 0);
 #endif
         }
+        f16_sat_bits_fold(ya_sat, rs, ok);
       }
     }
     VFX_TS(11);
@@ -502,7 +504,9 @@ __global__ __launch_bounds__(256, 2) void k_resblock_w64(const ResBlockParams* _
           f32x4 u;
 #pragma unroll
           for (int e = 0; e < 4; ++e) u[e] = fmaxf(val[q][e], val[q][e] * aslope);
-          const unsigned h01 = pack_f16x2(u[0], u[1], ya_sat), h23 = pack_f16x2(u[2], u[3], ya_sat);
+          unsigned rs = 0;  // this position's record: counted only where it is stored (conv_common.h)
+          const unsigned h01 = pack_f16x2(u[0], u[1], rs), h23 = pack_f16x2(u[2], u[3], rs);
+          f16_sat_bits_fold(ya_sat, rs, ooff[sp][q] != kOob);
           // quad_perm [1,0,3,2]: the even lane of a pair collects the pair's 8 consecutive channels (16 bytes)
           const unsigned g0 = (unsigned)__builtin_amdgcn_mov_dpp((int)h01, 0xB1, 0xf, 0xf, false);
           const unsigned g1 = (unsigned)__builtin_amdgcn_mov_dpp((int)h23, 0xB1, 0xf, 0xf, false);

@@ -148,6 +148,7 @@ __global__ __launch_bounds__(256) void k_up16(const TapConvParams* __restrict__ 
     for (int a = 0; a < WM; ++a) {
       const int q = q0 + mrow + 32 * a;
       const unsigned rowoff = (unsigned)q * (unsigned)(nphase * cph * 2) + (unsigned)(n * 2 + 16 * lh);  // (past the clip: out of range)
+      const unsigned keep16 = f16_sat16_keep(q < Tn);  // the record counts stored positions only (conv_common.h)
 #pragma unroll
       for (int jp = 0; jp < 4; jp += 2) {
         unsigned q2[2][2];
@@ -159,8 +160,8 @@ __global__ __launch_bounds__(256) void k_up16(const TapConvParams* __restrict__ 
             const float v = acc[a][4 * (jp + rr) + e] + bv[jp + rr][e];
             u[e] = fmaxf(v, v * slope);
           }
-          q2[rr][0] = pack_f16x2_sat16(u[0], u[1], true, sat16);
-          q2[rr][1] = pack_f16x2_sat16(u[2], u[3], true, sat16);
+          q2[rr][0] = pack_f16x2_sat16k(u[0], u[1], keep16, sat16);
+          q2[rr][1] = pack_f16x2_sat16k(u[2], u[3], keep16, sat16);
         }
         // lanes 0-31 keep their run jp and receive the partner's run jp; lanes 32-63 receive the partner's run jp + 1 and keep theirs
         const auto s0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
