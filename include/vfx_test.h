@@ -4,7 +4,9 @@
  * NOT part of the drop-in boundary (include/vfx.h, libvfx.so): nothing here corresponds to a call the reference makes.  Each
  * entry point runs ONE kernel family of libvfx.so in isolation -- weights handed over in PyTorch layout on the host, packed on
  * the fly, the launch synchronised -- so that tests/test_gpu_kernels.py can compare it with a float64 torch expression of the
- * same operator; vfx_op_voc_* and vfx_op_unet_piece run single launches exactly as the vocoder and ResUNet plans build them.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
+ * same operator; every launch goes through a throw-away plan of the product's PlanBuilder (csrc/ops_debug.cpp), and vfx_op_voc_*,
+ * vfx_op_resblock(fused), vfx_op_resblock_pair, vfx_op_unet_piece and vfx_op_analysis_piece run single launches exactly as the vocoder,
+ * ResUNet and analysis plans build them.  An error returns 1 (2: an exception of the C++ library) and leaves its text as the library's last error.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
  * handlers.py, dist.py, bench.py's timed path) never loads it.
  */
 #ifndef VFX_TEST_H_
@@ -28,8 +30,9 @@ int vfx_op_conv(vfx_handle* h, const float* x, int B, int H, int W, int Cin, con
                 const float* shift, int act, float slope, const float* bias,
                 const float* residual, float* y, void* stream);
 /* ConvTranspose (stride s, PyTorch layout (Cin, Cout, kh, kw) on the HOST):
- *   2-D: kh=kw=3, s=2, padding 0, output pruned to (2H, 2W+1) or (2H, 2W) when prune_w; without a bias and for H, W >= 2 it runs
- *        the ResUNet plan's form (two phased launches, one per output row class), else four parity launches;
+ *   2-D: kh=kw=3, s=2, padding 0, output pruned to (2H, 2W+1) or (2H, 2W) when prune_w; the launches are those of the ResUNet
+ *        plan's upsampler (resunet.cpp, unet_upsample_launches): without a bias, for H, W >= 2 and Cout % 32 == 0 one phased
+ *        launch (VFX_TUNE_TWO_LAUNCH_UPSAMPLERS: two, one per output row class), else four parity launches;
  *   1-D: kh=1, kw=2s, padding s/2+s%2, output_padding s%2, output (B,1,W*s,Cout). */
 int vfx_op_conv_transpose(vfx_handle* h, const float* x, int B, int H, int W, int Cin,
                           const float* weight, int Cout, int kh, int kw, int stride, int prune_w,

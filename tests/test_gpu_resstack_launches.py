@@ -340,6 +340,37 @@ def test_ya_with_and_without_the_raw_output(engine, form):
             assert torch.equal(_bits(ya_both), _bits(ya_only)), (form.name, dils, lens)
 
 
+@pytest.mark.parametrize("tuning", [0, F32_TRUNK], ids=["f16-trunk", "f32-trunk"])
+def test_older_entry_points_run_the_plans_launch(tuning):
+    """vfx_op_resblock(fused) and vfx_op_resblock_pair take their parameter block from voc_resblock_params like vfx_op_voc_resblock: the
+    same launch, so the same bits.  B = 2, T = 300: one or two tiles per clip at every width, the last one partial; d = 81 folds.  On the
+    raw trunk (fp32, or fp16 widened) y is compared with y; the wide layer's fp16 trunk keeps no y, so the older entry point returns
+    LeakyReLU^-1(ya), formed here as it forms it: v >= 0 ? v : v / slope in float32."""
+    import numpy as np
+    eng = _tuned(tuning)
+    B, T = 2, 300
+    for C in (64, 128, 256):
+        x = R.random_trunk(B, T, C, 7 * C)
+        la, lb = R.random_layer(C, 7 * C + 1), R.random_layer(C, 7 * C + 5)
+        for d in (1, 27, 81):
+            y_old = eng.op_resblock(x, *la, d, SLOPE, True)
+            if C == 256 and tuning == 0:
+                _, ya, info = eng.op_voc_resblock(x, la, d, slope=SLOPE, act_slope=SLOPE, want_raw=False, want_act=True)
+                assert info["asrc"] == 1 and info["x16"] == 1, info
+                v = ya.cpu().numpy()
+                want = torch.from_numpy(np.where(v >= 0, v, v / np.float32(SLOPE)).astype(np.float32))
+            else:
+                want, _, info = eng.op_voc_resblock(x, la, d, slope=SLOPE, act_slope=SLOPE, want_raw=True, want_act=True)
+                assert info["x16"] == int(tuning == 0), info
+            assert torch.isfinite(y_old).all(), (C, d)
+            assert torch.equal(_bits(y_old.cpu()), _bits(want.cpu())), (tuning, C, d, "single layer")
+        for da, db in {64: ((1, 3), (9, 27)), 128: ((1, 3),), 256: ()}[C]:
+            y_old = eng.op_resblock_pair(x, la, da, lb, db, SLOPE)
+            want, _, info = eng.op_voc_resblock(x, la, da, layer2=lb, dil2=db, slope=SLOPE, act_slope=SLOPE, want_raw=True, want_act=True)
+            assert info["x16"] == int(tuning == 0) and torch.isfinite(y_old).all(), (C, da, db, info)
+            assert torch.equal(_bits(y_old.cpu()), _bits(want.cpu())), (tuning, C, da, db, "pair")
+
+
 def test_refusals(engine):
     """Combinations the plan refuses are errors of the call, and nothing is launched."""
     if engine.tol['name'] == 'fp32':

@@ -42,20 +42,6 @@ DeviceTurn& device_turn(int device) {
 // =============================================================================================
 using namespace vfx;
 
-#define VFX_API_BEGIN try {
-// entry points that take a handle: NULL check + run on the handle's device, restore the caller's on exit
-#define VFX_API_BEGIN_H(h) try { VFX_CHECK((h) != nullptr, "NULL handle"); ::vfx::DeviceGuard device_guard_((h)->device);
-// ... and launch on a caller's stream: they take turns with calls on other streams of the device (StreamTurn, vfx_internal.h)
-#define VFX_API_BEGIN_HS(h, stream) VFX_API_BEGIN_H(h) ::vfx::StreamTurn stream_turn_((h)->device, (stream));
-#define VFX_API_END                         \
-  }                                         \
-  catch (const vfx::Error&) { return 1; }   \
-  catch (const std::exception& e) {         \
-    vfx::set_error("exception: %s", e.what()); \
-    return 2;                               \
-  }                                         \
-  return 0;
-
 // body(first clip, clips) over B clips, `step` at a time; stops at the first non-zero return code
 template <class Body>
 static int for_sub_batches(int B, int step, Body body) {

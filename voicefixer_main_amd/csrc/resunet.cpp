@@ -182,6 +182,82 @@ std::shared_ptr<UNetWeights> build_unet_weights(vfx_handle* h, int model) {
 // ---------------------------------------------------------------------------------------------
 // plan construction
 // ---------------------------------------------------------------------------------------------
+// ConvTranspose2d(k3, s2, p0) + prune on (B, H, W, Cin) -> (B, 2H, 2W [+ 1], Cout) as tap convolutions: output parity class
+// (a, b) = (oh & 1, ow & 1) is a convolution with the kernel rows kh == a and columns kw == b (mod 2), weights wT[2 a + b].
+// Three forms, the same stage tables and sums in each (bit-identical):
+//   * ONE launch of four phases r = 2 a + b, for either output width: the output is addressed in units of Cout channels at the TRUE
+//     pixel index (TapConvParams::out_cmul: phase r lands at column 2 j + (r & 1)), phases 2 and 3 write the odd output rows
+//     (TapConvParams::phase_rows), and a block of k_conv covers up to four phases: the patch is staged once and x read from HBM once.
+//   * VFX_TUNE_TWO_LAUNCH_UPSAMPLERS: one launch per output row class, its two column classes the phases.  An even output width makes
+//     (B, 2H, 2W, C) a (B, 2H, W, 2C) tensor whose channel halves are the column parities; an odd one (2 W + 1: the mel ResUNet prunes
+//     the time axis only) has no such view and is addressed through out_cmul, column class 1 one column short.
+//   * four launches, one per parity class: an image of one row or column (plan_conv finds a tile whose all-taps window fits one patch,
+//     which a phased launch needs, from 2 x 2 up), VFX_TUNE_NO_FUSED_UNET, a bias, or couts that are no multiple of 32.
+std::vector<ConvLaunch> unet_upsample_launches(int tuning, int B, int H, int W, int Cin, int Cout, bool prune_w, const float* src, float* out,
+                                               const float* scale, const float* shift, int act, float slope, const float* const wT[4],
+                                               const float* bias) {
+  const int Ho = 2 * H, Wo = prune_w ? 2 * W : 2 * W + 1;
+  const bool phased = H >= 2 && W >= 2 && !(tuning & VFX_TUNE_NO_FUSED_UNET) && !bias && Cout % 32 == 0;
+#ifdef VFX_ABL_NO_ODD_PHASED  // (measurement builds: four launches at an odd width)
+  const bool two_ok = phased && prune_w;
+#else
+  const bool two_ok = phased;
+#endif
+  const bool four = phased && !(tuning & VFX_TUNE_TWO_LAUNCH_UPSAMPLERS);
+  const int na = four ? 2 : 1, nb = (four || two_ok) ? 2 : 1;  // row and column classes per launch
+  std::vector<ConvLaunch> launches;
+  for (int a0 = 0; a0 < 2; a0 += na)
+    for (int b0 = 0; b0 < 2; b0 += nb) {
+      ConvLaunch l{};
+      TapConvParams& p = l.p;
+      p.B = B;
+      p.Hi = H;
+      p.Wi = W;
+      p.Ho = Ho;
+      p.Wo = Wo;
+      p.Cout = na * nb * Cout;
+      p.sh = p.sw = 2;
+      p.oh0 = a0;
+      p.ow0 = b0;
+      p.Hg = (Ho - a0 + 1) / 2;  // (row class 1 has Ho / 2 rows; beside class 0 in one launch: masked, oh < Ho)
+      p.Wg = (Wo - b0 + 1) / 2;  // column class 0: W + 1 columns of an odd width, W of a pruned one; class 1 beside it masked (ow + 1 < Wo)
+      if (nb == 2 && na == 1 && prune_w) {  // the (B, 2H, W, 2C) view
+        p.Wo = W;
+        p.sw = 1;
+      } else if (nb == 2) {
+        p.out_cmul = Cout;
+        p.phase_rows = na == 2;
+      }
+      p.bias = bias;
+      p.out = out;
+      p.act_slope = 1.f;
+      p.nseg = 1;
+      std::vector<TapSeg> phases;
+      for (int a = a0; a < a0 + na; ++a)
+        for (int b = b0; b < b0 + nb; ++b) {
+          TapSeg S{};
+          S.src = src;
+          S.C = Cin;
+          S.scale = scale;
+          S.shift = shift;
+          S.act = act;
+          S.slope = slope;
+          S.wt = wT[a * 2 + b];
+          for (int kh = a; kh < 3; kh += 2)
+            for (int kw = b; kw < 3; kw += 2) {
+              S.dh[S.ntaps] = -(kh / 2);  // oh = 2*ih + kh  ->  ih = i - kh/2 for oh = 2i + a
+              S.dw[S.ntaps] = -(kw / 2);
+              ++S.ntaps;
+            }
+          phases.push_back(S);
+        }
+      p.seg[0] = phases[0];  // the launch's first class reads the kernel rows / columns {0, 2} its others lack: the union of their windows
+      if (phases.size() > 1) l.phases = phases;
+      launches.push_back(l);
+    }
+  return launches;
+}
+
 namespace {
 
 struct Act4 {  // an activation tensor in the arena
@@ -371,167 +447,10 @@ struct TrunkBuilder {
   // BN -> ReLU -> ConvTranspose2d(k3, s2, p0) -> prune (modules.py:205-214)
   Act4 upsample(const DecoderW& D, const Act4& x, bool prune_w) {
     Act4 y = make(2 * x.H, prune_w ? 2 * x.W : 2 * x.W + 1, D.cout);
-    auto parity_taps = [](TapSeg& S, int a, int b) {
-      S.ntaps = 0;
-      for (int kh = a; kh < 3; kh += 2)
-        for (int kw = b; kw < 3; kw += 2) {
-          S.dh[S.ntaps] = -(kh / 2);  // oh = 2*ih + kh  ->  ih = i - kh/2 for oh = 2i + a
-          S.dw[S.ntaps] = -(kw / 2);
-          ++S.ntaps;
-        }
-    };
-    // Round 6: ONE launch of four phases r = 2 a + b for either output width: the output is addressed in units of C channels at the TRUE
-    // pixel index (TapConvParams::out_cmul: phase r lands at column 2 j + (r & 1)), phases 2 and 3 write the odd output rows
-    // (TapConvParams::phase_rows), and a block of k_conv covers up to four phases (BN = 128 for 32 couts per phase): the patch is
-    // staged once for all of them and x is read from HBM once.  VFX_TUNE_TWO_LAUNCH_UPSAMPLERS keeps the forms of rounds 3-4 below (one
-    // launch per output row class, one phase per block); same stage tables, same sums: bit-identical.
-    if (x.H >= 2 && x.W >= 2 && !(pb.h->cfg.tuning & (VFX_TUNE_NO_FUSED_UNET | VFX_TUNE_TWO_LAUNCH_UPSAMPLERS))) {
-      TapConvParams p{};
-      p.B = B;
-      p.Hi = x.H;
-      p.Wi = x.W;
-      p.Ho = y.H;
-      p.Wo = y.W;
-      p.Cout = 4 * D.cout;
-      p.out_cmul = D.cout;
-      p.phase_rows = 1;
-      p.sh = 2;
-      p.sw = 2;
-      p.oh0 = 0;
-      p.ow0 = 0;
-      p.Hg = (y.H + 1) / 2;            // (row class 1 has y.H / 2 rows: masked, oh < Ho)
-      p.Wg = (y.W + 1) / 2;            // column class 0: W + 1 columns of an odd width 2 W + 1, W of a pruned one; class 1 masked (ow + 1 < Wo)
-      p.out = const_cast<float*>(rel_ptr(y.off));
-      p.act_slope = 1.f;
-      p.nseg = 1;
-      std::vector<TapSeg> phases(4);
-      for (int r = 0; r < 4; ++r) {
-        TapSeg& S = phases[r];
-        S = TapSeg{};
-        S.src = rel_ptr(x.off);
-        S.C = x.C;
-        S.scale = D.bn_scale;
-        S.shift = D.bn_shift;
-        S.act = ACT_LEAKY;
-        S.slope = 0.f;  // ReLU
-        S.wt = D.wT[r];
-        parity_taps(S, r >> 1, r & 1);
-      }
-      p.seg[0] = phases[0];  // phase (0, 0) reads kh, kw in {0, 2}: the union of all four windows
-      pb.add_conv_phased(p, phases);
-      return y;
-    }
-    // (x.H, x.W >= 2: plan_conv then always finds a tile whose all-taps window fits one patch, which a phased launch needs;
-    // an odd output width -- the mel ResUNet prunes the time axis only -- has no such view: addressed in units of C instead, below)
-    if (prune_w && x.H >= 2 && x.W >= 2 && !(pb.h->cfg.tuning & VFX_TUNE_NO_FUSED_UNET)) {
-      // An even output width makes (B, 2H, 2W, C) a (B, 2H, W, 2C) tensor whose channel halves are the two column parities:
-      // the column classes of one row class are the PHASES of one launch (own taps, own weight tensor, one patch) -- two
-      // launches per upsampler instead of four.  In the deep levels a launch is a chain of patch round trips, one per 32-channel
-      // stage, whatever it computes (25-45 us each, profiles/r03_c10_ring4_ab.jsonl): half the launches, half that time.
-      for (int a = 0; a < 2; ++a) {
-        TapConvParams p{};
-        p.B = B;
-        p.Hi = x.H;
-        p.Wi = x.W;
-        p.Ho = y.H;
-        p.Wo = x.W;
-        p.Cout = 2 * D.cout;
-        p.sh = 2;
-        p.sw = 1;
-        p.oh0 = a;
-        p.ow0 = 0;
-        p.Hg = (y.H - a + 1) / 2;
-        p.Wg = x.W;
-        p.out = const_cast<float*>(rel_ptr(y.off));
-        p.act_slope = 1.f;
-        p.nseg = 1;
-        std::vector<TapSeg> phases(2);
-        for (int b = 0; b < 2; ++b) {
-          TapSeg& S = phases[b];
-          S = TapSeg{};
-          S.src = rel_ptr(x.off);
-          S.C = x.C;
-          S.scale = D.bn_scale;
-          S.shift = D.bn_shift;
-          S.act = ACT_LEAKY;
-          S.slope = 0.f;  // ReLU
-          S.wt = D.wT[a * 2 + b];
-          parity_taps(S, a, b);
-        }
-        p.seg[0] = phases[0];  // column class 0 reads kw = 0, 2: its taps are the union of both classes' windows
-        pb.add_conv_phased(p, phases);
-      }
-      return y;
-    }
-#ifndef VFX_ABL_NO_ODD_PHASED
-    if (!prune_w && x.H >= 2 && x.W >= 2 && !(pb.h->cfg.tuning & VFX_TUNE_NO_FUSED_UNET)) {
-      // An odd output width (2 W + 1: the mel ResUNet) has no such view, but the same two launches: the output is addressed in
-      // units of C channels at the TRUE pixel index (TapConvParams::out_cmul), column class 1 one column short.
-      for (int a = 0; a < 2; ++a) {
-        TapConvParams p{};
-        p.B = B;
-        p.Hi = x.H;
-        p.Wi = x.W;
-        p.Ho = y.H;
-        p.Wo = y.W;
-        p.Cout = 2 * D.cout;
-        p.out_cmul = D.cout;
-        p.sh = 2;
-        p.sw = 2;
-        p.oh0 = a;
-        p.ow0 = 0;
-        p.Hg = (y.H - a + 1) / 2;
-        p.Wg = x.W + 1;  // column class 0 has W + 1 columns, class 1 W
-        p.out = const_cast<float*>(rel_ptr(y.off));
-        p.act_slope = 1.f;
-        p.nseg = 1;
-        std::vector<TapSeg> phases(2);
-        for (int b = 0; b < 2; ++b) {
-          TapSeg& S = phases[b];
-          S = TapSeg{};
-          S.src = rel_ptr(x.off);
-          S.C = x.C;
-          S.scale = D.bn_scale;
-          S.shift = D.bn_shift;
-          S.act = ACT_LEAKY;
-          S.slope = 0.f;  // ReLU
-          S.wt = D.wT[a * 2 + b];
-          parity_taps(S, a, b);
-        }
-        p.seg[0] = phases[0];
-        pb.add_conv_phased(p, phases);
-      }
-      return y;
-    }
-#endif
-    for (int a = 0; a < 2; ++a)
-      for (int b = 0; b < 2; ++b) {
-        TapConvParams p{};
-        p.B = B;
-        p.Hi = x.H;
-        p.Wi = x.W;
-        p.Ho = y.H;
-        p.Wo = y.W;
-        p.Cout = D.cout;
-        p.sh = p.sw = 2;
-        p.oh0 = a;
-        p.ow0 = b;
-        p.Hg = (y.H - a + 1) / 2;
-        p.Wg = (y.W - b + 1) / 2;
-        p.out = const_cast<float*>(rel_ptr(y.off));
-        p.act_slope = 1.f;
-        p.nseg = 1;
-        TapSeg& S = p.seg[0];
-        S.src = rel_ptr(x.off);
-        S.C = x.C;
-        S.scale = D.bn_scale;
-        S.shift = D.bn_shift;
-        S.act = ACT_LEAKY;
-        S.slope = 0.f;  // ReLU
-        S.wt = D.wT[a * 2 + b];
-        parity_taps(S, a, b);
-        pb.add_conv(p);
-      }
+    for (const ConvLaunch& l : unet_upsample_launches(pb.h->cfg.tuning, B, x.H, x.W, x.C, D.cout, prune_w, rel_ptr(x.off),
+                                                      const_cast<float*>(rel_ptr(y.off)), D.bn_scale, D.bn_shift, ACT_LEAKY, 0.f /* ReLU */,
+                                                      D.wT, nullptr))
+      pb.add_conv(l);
     return y;
   }
 

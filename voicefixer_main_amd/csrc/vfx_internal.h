@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <exception>
 #include <functional>
 #include <initializer_list>
 #include <map>
@@ -40,6 +41,22 @@ struct Error {};  // thrown after set_error(); caught at the C boundary
       throw ::vfx::Error();          \
     }                                \
   } while (0)
+
+// The guards of an extern "C" entry point (libvfx.so and libvfx_test.so): nothing is thrown across the C boundary.  An Error is return
+// code 1 (its message already set), any other std::exception return code 2 with its what() as vfx_last_error().
+#define VFX_API_BEGIN try {
+// entry points that take a handle: NULL check + run on the handle's device, restore the caller's on exit
+#define VFX_API_BEGIN_H(h) try { VFX_CHECK((h) != nullptr, "NULL handle"); ::vfx::DeviceGuard device_guard_((h)->device);
+// ... and launch on a caller's stream: they take turns with calls on other streams of the device (StreamTurn, below)
+#define VFX_API_BEGIN_HS(h, stream) VFX_API_BEGIN_H(h) ::vfx::StreamTurn stream_turn_((h)->device, (stream));
+#define VFX_API_END                              \
+  }                                              \
+  catch (const ::vfx::Error&) { return 1; }      \
+  catch (const std::exception& e) {              \
+    ::vfx::set_error("exception: %s", e.what()); \
+    return 2;                                    \
+  }                                              \
+  return 0;
 
 // Every entry point that takes a handle works on the handle's device whatever the caller's current device is, and
 // leaves the caller's current device as it found it (two handles on two GPUs in one process, torch.cuda.set_device
@@ -835,6 +852,12 @@ struct Plan {
 // (so that offset 0 is distinguishable from nullptr).
 inline const float* rel_ptr(size_t off) { return reinterpret_cast<const float*>(off + 1); }
 
+// A tap convolution as a builder function hands it to the plan: phases empty = PlanBuilder::add_conv, otherwise add_conv_phased
+struct ConvLaunch {
+  TapConvParams p;
+  std::vector<TapSeg> phases;
+};
+
 struct PlanBuilder {
   vfx_handle* h;
   Plan* plan;
@@ -856,6 +879,7 @@ struct PlanBuilder {
   void add_conv(TapConvParams p);
   // p.seg[0] carries the UNION of the phases' taps (geometry only); phases[r] = source / prologue / taps / weights of phase r
   void add_conv_phased(TapConvParams p, const std::vector<TapSeg>& phases);
+  void add_conv(const ConvLaunch& l) { l.phases.empty() ? add_conv(l.p) : add_conv_phased(l.p, l.phases); }
   void add_resblock(ResBlockParams p);  // x / y are arena offsets encoded with rel_ptr()
 };
 
@@ -1063,6 +1087,13 @@ struct UNetPiece {
   int h_form;
 };
 void build_unet_piece(PlanBuilder& pb, const UNetWeights& Wt, UNetPiece& piece);
+// The launches of a ResUNet upsampler (resunet.cpp: the one-launch, two-launch and four-launch forms), for the plans (no bias, BN + ReLU
+// prologue) and for vfx_op_conv_transpose: prologue scale / shift [Cin] (NULL: identity) + act (slope) on src (B, H, W, Cin), weights
+// wT[2 a + b] packed per output parity class, bias [Cout] or NULL -> out (B, 2H, prune_w ? 2W : 2W + 1, Cout).  src / out as the plan
+// wants them (rel_ptr offsets); every launch goes to PlanBuilder::add_conv.
+std::vector<ConvLaunch> unet_upsample_launches(int tuning, int B, int H, int W, int Cin, int Cout, bool prune_w, const float* src, float* out,
+                                               const float* scale, const float* shift, int act, float slope, const float* const wT[4],
+                                               const float* bias);
 UNetWeights unet_weight_shapes();  // the channel counts of every block, no tensors: what build_unet_weights fills (host-only planning)
 // What a piece's plan launches, in order: kUNetLaunchInts ints per launch = family (UNetLaunchFamily), ksplit (1 = none), activated
 // output, bias, K segments, output channels.  Returns the number of launches; writes those that fit `cap` ints.
