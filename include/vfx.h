@@ -562,6 +562,50 @@ int vfx_stoi(vfx_handle* h, const float* est, const float* target, int B, int Lm
 int vfx_bsseval(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, int flen, double* out,
                 void* stream);
 
+/*
+ * The validation losses of the training scripts, forward values only (no gradient), for a padded batch of (est, target) waveform pairs
+ * at 44.1 kHz: est, target (B, Lmax) device floats, pair b = the first L_b = lengths[b] samples of row b; lengths is a HOST array int[B]
+ * with n_fft/2 < lengths[b] <= Lmax, or NULL: every clip has Lmax samples.  out: (B, VFX_N_SPEC_LOSSES) device doubles, per clip over its
+ * own L_b samples and T_b = L_b / hop + 1 frames:
+ *   0 l1_wav     mean |e - t|                                 (nn.L1Loss of the waveforms)
+ *   1 l1_sp      mean over T_b x 1025 of | |STFT e| - |STFT t| |          (tools/pytorch/losses.py:192-204 L1_Sp, eps 1e-8)
+ *   2 l1_log_sp  the same mean of | log10 |STFT e| - log10 |STFT t| |     (losses.py L1_Log_Sp)
+ * |STFT .| = sqrt(max(re^2 + im^2, 1e-8)) is bit for bit vfx_stft_phase(eps = 1e-8)'s magnitude of the clip alone (frames and
+ * reflection of its own length).  A difference of columns 0 and 1 is ONE float32 subtraction, its absolute value widened to double; the
+ * logarithms of column 2 are taken in float64.  Every sum is in float64 in an order fixed by the clip alone (per frame, per chunk of
+ * 4096 samples, then by index): a clip's three numbers do not depend on the batch it is in nor on Lmax, est == target gives exactly 0,
+ * and nothing at or past a clip's length is read.  No spectrogram is written to memory (one fused launch transforms both clips).  More
+ * than 128 clips run as consecutive sub-batches.  The partial sums live in the handle's grow-only varlen scratch: while a hipGraph
+ * captured from a plan is alive, a call that would have to grow it fails with a message that says so.
+ * Fails, naming the clip and launching nothing, for a NULL pointer, B <= 0, or a length out of range.
+ */
+#define VFX_N_SPEC_LOSSES 3   /* 0 l1_wav  1 l1_sp  2 l1_log_sp */
+int vfx_spec_losses(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths,
+                    double* out /* (B, 3) device */, void* stream);
+
+/*
+ * Column 0 of vfx_spec_losses for tensors that are not waveforms (nn.L1Loss of two log-mel images): a, b (B, ld) device floats, row r =
+ * its first counts[r] elements (HOST int[B], 1 <= counts[r] <= ld; NULL: all ld) -> out[r] = mean |float32(a_i - b_i)|, B device
+ * doubles, by the same chunked float64 sums (a row's number depends on the row alone).  Fails, launching nothing, for a NULL pointer,
+ * B <= 0, ld outside (0, 2^31) or a count out of range.
+ */
+int vfx_l1_rows(vfx_handle* h, const float* a, const float* b, int B, int64_t ld, const int* counts, double* out, void* stream);
+
+/*
+ * val_l of VoiceFixer's validation_step (models/gsr_voicefixer.py:264-277) per clip of a padded batch, without the vocoder:
+ *   val_l[b] = mean over T_b x 128 of | float32(lg - tlog) |,  lg = the selected analysis module's log10 estimate of clip b -- the
+ *   first half of vfx_restore_gsr_varlen: the same launches, plans and scratch --, tlog = to_log(mel(target b)) at the target's own
+ *   length (vfx_stft_mel(log10_mel = 1)).
+ * wav, target (B, Lmax) device floats; lengths HOST int[B]; target_lengths HOST int[B] or NULL (= lengths); logmel_out (B, T, 128)
+ * device or NULL: bit for bit vfx_restore_gsr_varlen's; val_l: B device doubles.  The sum is in float64 over chunks of 4096 values cut
+ * from the clip's own first row, then by index: a clip's val_l does not depend on the batch.  Any mix of lengths; more than 128 clips
+ * run as consecutive sub-batches.  Only the analysis module's weights have to be finalized.
+ * Fails, naming the clip and launching nothing, for a NULL wav, target, lengths or val_l, B <= 0, a length of a clip or of a target
+ * outside (n_fft/2, Lmax], or a target whose frame count differs from its clip's.
+ */
+int vfx_validate_gsr_varlen(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                            const int* target_lengths, float* logmel_out /* optional */, double* val_l /* (B) device */, void* stream);
+
 /* Read-and-clear the sticky device flags (synchronises `stream`). */
 int vfx_take_flags(vfx_handle* h, void* stream, int* flags_out);
 /* ... only the bits in `mask` (VFX_FLAG_*): the others stay raised for a later check. */

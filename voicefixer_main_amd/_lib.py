@@ -25,6 +25,7 @@ FLAG_PEAK_NORMALISED = 4  # vfx_restore_gsr divided a clip by its peak (the refe
 N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metrics
 N_HANDLER_METRICS = 4     # VFX_N_HANDLER_METRICS: the columns of vfx_restore_*_varlen_scored
 BSSEVAL_SLAB = 8192       # VFX_BSSEVAL_SLAB: samples per partial sum of vfx_bsseval
+N_SPEC_LOSSES = 3         # VFX_N_SPEC_LOSSES: the columns of vfx_spec_losses (l1_wav, l1_sp, l1_log_sp)
 
 
 class VfxConfig(ctypes.Structure):
@@ -98,6 +99,10 @@ SIGNATURES = {
                                               c_void_p, c_int, c_void_p]),
     "vfx_restore_ssr_varlen_scored": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
                                               c_void_p]),
+    "vfx_spec_losses": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_l1_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_validate_gsr_varlen": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p,
+                                        c_void_p]),
     "vfx_take_flags": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "vfx_take_flags_masked": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int)]),
     "vfx_turn_begin": (c_int, [c_int, c_void_p]),

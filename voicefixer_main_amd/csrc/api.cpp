@@ -425,6 +425,72 @@ int vfx_bsseval(vfx_handle* h, const float* est, const float* target, int B, int
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// validation losses (tools/pytorch/losses.py L1, L1_Sp, L1_Log_Sp on the device: losses.hip)
+// ---------------------------------------------------------------------------------------------
+int vfx_spec_losses(vfx_handle* h, const float* est, const float* target, int B, int Lmax, const int* lengths, double* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(est && target && out, "vfx_spec_losses: NULL argument");
+  VFX_CHECK(B > 0 && Lmax > 0, "vfx_spec_losses: need B > 0 and Lmax > 0, got B=%d Lmax=%d", B, Lmax);
+  VFX_CHECK(h->cfg.n_fft == 2048, "vfx_spec_losses: needs the 44.1 kHz front end (n_fft 2048)");
+  const int hop = h->cfg.hop, half = h->cfg.n_fft / 2, nbins = half + 1;
+  std::vector<int> host(2 * (size_t)B);  // samples | frames
+  for (int b = 0; b < B; ++b) {
+    const int Lb = lengths ? lengths[b] : Lmax;
+    VFX_CHECK(Lb > half && Lb <= Lmax, "vfx_spec_losses: clip %d has %d samples (need %d < length <= Lmax = %d: reflect padding)", b, Lb, half,
+              Lmax);
+    host[b] = Lb;
+    host[(size_t)B + b] = Lb / hop + 1;
+  }
+  const int T = frames_of(h, Lmax), nchunk = l1_chunks(Lmax);
+  const int step = std::min(B, kLossMaxClips);
+  const size_t frame_bytes = (size_t)step * T * 2 * sizeof(double);
+  char* const sc = h->scratch.ensure(h, frame_bytes + (size_t)step * nchunk * sizeof(double), 8,
+                                     "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured from plan "
+                                     "'%s': run the largest vfx_spec_losses batch once BEFORE capturing");
+  double* const frame_ws = reinterpret_cast<double*>(sc);
+  double* const chunk_ws = reinterpret_cast<double*>(sc + frame_bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_n = h->lens_row(LENS_LOSS_COUNT);
+  int* const d_f = h->lens_row(LENS_LOSS_FRAMES);
+  for (int b0 = 0; b0 < B; b0 += step) {  // (a clip's numbers do not depend on the launch it is in)
+    const int n = std::min(step, B - b0);
+    const float* const e = est + (int64_t)b0 * Lmax;
+    const float* const t = target + (int64_t)b0 * Lmax;
+    launch_set_frames(d_n, host.data() + b0, n, s);
+    launch_set_frames(d_f, host.data() + B + b0, n, s);
+    launch_l1_rows(e, t, n, Lmax, d_n, nchunk, chunk_ws, s);
+    launch_pair_stft_l1(h->fe, e, t, n, Lmax, T, d_n, hop, 1e-8f, frame_ws, s);
+    launch_loss_final(chunk_ws, nchunk, d_n, frame_ws, T, d_f, nbins, 1, out + (int64_t)b0 * VFX_N_SPEC_LOSSES, VFX_N_SPEC_LOSSES, n, s);
+  }
+  VFX_API_END
+}
+
+int vfx_l1_rows(vfx_handle* h, const float* a, const float* b, int B, int64_t ld, const int* counts, double* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(a && b && out, "vfx_l1_rows: NULL argument");
+  VFX_CHECK(B > 0 && ld > 0 && ld <= 0x7fffffff, "vfx_l1_rows: need B > 0 and 0 < ld < 2^31, got B=%d ld=%lld", B, (long long)ld);
+  std::vector<int> host(B);
+  for (int r = 0; r < B; ++r) {
+    host[r] = counts ? counts[r] : (int)ld;
+    VFX_CHECK(host[r] >= 1 && host[r] <= ld, "vfx_l1_rows: row %d has %d elements (need 1 <= count <= ld = %lld)", r, host[r], (long long)ld);
+  }
+  const int nchunk = l1_chunks(ld);
+  const int step = std::min(B, kLossMaxClips);
+  double* const chunk_ws = reinterpret_cast<double*>(h->scratch.ensure(
+      h, (size_t)step * nchunk * sizeof(double), 8, "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured "
+      "from plan '%s': run the largest vfx_l1_rows batch once BEFORE capturing"));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_n = h->lens_row(LENS_LOSS_COUNT);
+  for (int r0 = 0; r0 < B; r0 += step) {
+    const int n = std::min(step, B - r0);
+    launch_set_frames(d_n, host.data() + r0, n, s);
+    launch_l1_rows(a + (int64_t)r0 * ld, b + (int64_t)r0 * ld, n, ld, d_n, nchunk, chunk_ws, s);
+    launch_loss_final(chunk_ws, nchunk, d_n, nullptr, 0, nullptr, 0, 0, out + r0, 1, n, s);
+  }
+  VFX_API_END
+}
+
 int vfx_chunk_gather(vfx_handle* h, const float* x, int B, int L, int win, int hop, int lead, int n_chunks,
                      float* chunks, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
@@ -978,21 +1044,33 @@ static int padded_group(int n) { return n <= 2 ? n : (n <= 8 ? (n + 1) / 2 * 2 :
 // With a target (vfx_restore_gsr_varlen_scored, which has checked the lengths): target (B, Lmax), clip b = its first target_lengths[b]
 // samples, metrics_out (B, VFX_N_HANDLER_METRICS) -- the handler's four mel scores (eval_gsr_voicefixer.py:56-64), scored where the
 // log10 estimate and what the vocoder receives both exist.  Without one (all three NULL) the launches and the scratch are the same as ever.
-static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out,
-                                    float* logmel_out, int flags, void* stream, const float* target = nullptr,
-                                    const int* target_lengths = nullptr, double* metrics_out = nullptr) {
-  VFX_API_BEGIN_HS(h, stream)
-  VFX_CHECK(wav && wav_out && lengths && B > 0 && B <= kMaxVarlenClips, "bad argument");
+//
+// The first half -- pre() at the clips' own lengths, then the selected analysis module -- is varlen_analysis: vfx_restore_gsr_varlen goes
+// on to the vocoder from it, vfx_validate_gsr_varlen to the log-mel L1 against the targets.  It places every tensor between the stages
+// of the call in the handle's scratch (the vocoder's only when `vocoder`), `tail_bytes` more behind them for the caller's own, and
+// leaves the log10 estimate in `lg`, copied to logmel_out (rows past a clip's last frame: zeros) when that is given.
+struct VarlenAnalysis {
+  int T = 0;
+  std::vector<int> host;  // samples | frames | vocoder frames of the B clips
+  struct Run { int b0, n, Tv; };
+  std::vector<Run> runs;  // the vocoder's runs of consecutive clips (none without a vocoder)
+  char* sc = nullptr;     // the scratch
+  size_t o_den = 0, o_vmel = 0, o_long = 0, o_ws = 0, o_pk = 0, o_tail = 0;
+  float *mel = nullptr, *lg = nullptr;
+};
+static size_t up_floats(int64_t n) { return (size_t)((n + 63) / 64 * 64) * sizeof(float); }
+
+static void varlen_analysis(vfx_handle* h, const char* who, const float* wav, int B, int Lmax, const int* lengths, bool vocoder,
+                            size_t tail_bytes, float* logmel_out, void* stream, VarlenAnalysis& va) {
   const int am = h->analysis_model;
-  VFX_CHECK((am == VFX_MODEL_UNET_MEL ? (bool)h->unet[am] : (bool)h->analysis[am - VFX_MODEL_GRU_MEL]) && h->voc,
-            "vfx_restore_gsr_varlen: weights are not finalized");
   const int hop = h->cfg.hop;
-  const int T = frames_of(h, Lmax);
-  std::vector<int> host(3 * (size_t)B);
+  const int T = va.T = frames_of(h, Lmax);
+  std::vector<int>& host = va.host;
+  host.assign(3 * (size_t)B, 0);
   std::map<int, std::vector<int>, std::greater<int>> groups;  // padded frame count -> clips (longest group first)
   for (int b = 0; b < B; ++b) {
     const int Lb = lengths[b];
-    VFX_CHECK(Lb > h->cfg.n_fft / 2 && Lb <= Lmax, "vfx_restore_gsr_varlen: clip %d has %d samples (need %d < length <= Lmax = %d)", b, Lb,
+    VFX_CHECK(Lb > h->cfg.n_fft / 2 && Lb <= Lmax, "%s: clip %d has %d samples (need %d < length <= Lmax = %d)", who, b, Lb,
               h->cfg.n_fft / 2, Lmax);
     const int Tb = Lb / hop + 1;
     host[b] = Lb;
@@ -1007,16 +1085,13 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
   int* const d_t = h->lens_row(LENS_FRAMES);
   int* const d_gt = h->lens_row(LENS_GROUP_FRAMES);
   int* const d_gi = h->lens_row(LENS_GROUP_INDEX);
-  int* const d_vl = h->lens_row(LENS_RUN_SAMPLES);
-  int* const d_vt = h->lens_row(LENS_RUN_FRAMES);
-  int* const d_vtp = h->lens_row(LENS_RUN_VOC_FRAMES);
   launch_set_lens(d_l, cap, host.data(), B, s);
-  const int unify = flags & 1;
   // ---- vocoder runs: consecutive clips (the callers hand them over sorted by length), each run on a compact (n, Tv, 128) tensor whose
   // frame count Tv is the run's own longest clip, rounded up to a multiple of 64 frames (a handful of plan shapes per test set)
-  struct Run { int b0, n, Tv; };
-  std::vector<Run> runs;
-  for (int b0 = 0; b0 < B;) {
+  using Run = VarlenAnalysis::Run;
+  std::vector<Run>& runs = va.runs;
+  runs.clear();
+  for (int b0 = 0; vocoder && b0 < B;) {
     int n = 0, tmax = 0;
     while (b0 + n < B) {
       const int tb = host[B + b0 + n];
@@ -1045,24 +1120,22 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
     vlong = std::max<int64_t>(vlong, (int64_t)r.n * vocoder_out_len(h->cfg, r.Tv));
     nmax = std::max(nmax, r.n);
   }
-  auto up = [](int64_t n) { return (size_t)((n + 63) / 64 * 64) * sizeof(float); };
+  auto up = up_floats;
   const size_t o_mel = 0, o_log = o_mel + up(nmel), o_den = o_log + up(nmel), o_gin = o_den + up(nmel), o_gout = o_gin + up(gmax),
                o_vmel = o_gout + up(gmax), o_long = o_vmel + up(vmel), o_ws = o_long + up(vlong), o_pk = o_ws + up(2 * B + 64),
-               o_tmel = o_pk + up(nmax + 64), o_score = o_tmel + (target ? up(nmel) : 0),
-               o_end = o_score + (target ? handler_metrics_ws_bytes(B, T) : 0);  // (the last two: only a call with a target has them)
+               o_tail = o_pk + up(nmax + 64), o_end = o_tail + tail_bytes;  // (the tail: only a call with a target has one)
   // Handle-owned scratch beside the arena (grow-only): the tensors that travel BETWEEN the plans of one varlen call (every plan
   // places its own buffers from offset 0 of the arena).  Growing frees and re-allocates: the device is idle then (hipFree waits).
   char* const sc = h->scratch.ensure(h, o_end, 8, "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured "
                                      "from plan '%s': run the largest varlen batch once BEFORE capturing");
   float* const mel = reinterpret_cast<float*>(sc + o_mel);
   float* const lg = reinterpret_cast<float*>(sc + o_log);
-  float* const den = reinterpret_cast<float*>(sc + o_den);
   float* const gin = reinterpret_cast<float*>(sc + o_gin);
   float* const gout = reinterpret_cast<float*>(sc + o_gout);
-  float* const vm = reinterpret_cast<float*>(sc + o_vmel);
-  float* const wlong = reinterpret_cast<float*>(sc + o_long);
-  float* const ws = reinterpret_cast<float*>(sc + o_ws);
-  float* const pk = reinterpret_cast<float*>(sc + o_pk);
+  va.sc = sc;
+  va.o_den = o_den, va.o_vmel = o_vmel, va.o_long = o_long, va.o_ws = o_ws, va.o_pk = o_pk, va.o_tail = o_tail;
+  va.mel = mel;
+  va.lg = lg;
   // ---- pre(): STFT -> magnitude -> mel, every clip framed and reflected at its own length (eval_gsr_voicefixer.py:19-25)
   launch_stft_mel(h->fe, wav, B, Lmax, T, mel, nullptr, nullptr, nullptr, 0, hop, 1e-8f, s, d_l);
   // ---- the mel ResUNet, one launch set per padded frame count (unet.py:75-77 pads every clip to ITS multiple of 64 frames): the
@@ -1097,9 +1170,46 @@ static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int 
     }
   }
   if (logmel_out) launch_copy_rows_masked(lg, logmel_out, B, T, 128, d_t, s);
+}
+
+// vfx_restore_gsr_varlen for at most kMaxVarlenClips clips; with a target, vfx_restore_gsr_varlen_scored
+static int vfx_restore_gsr_varlen_1(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, float* wav_out,
+                                    float* logmel_out, int flags, void* stream, const float* target = nullptr,
+                                    const int* target_lengths = nullptr, double* metrics_out = nullptr) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(wav && wav_out && lengths && B > 0 && B <= kMaxVarlenClips, "bad argument");
+  const int am = h->analysis_model;
+  VFX_CHECK((am == VFX_MODEL_UNET_MEL ? (bool)h->unet[am] : (bool)h->analysis[am - VFX_MODEL_GRU_MEL]) && h->voc,
+            "vfx_restore_gsr_varlen: weights are not finalized");
+  const int hop = h->cfg.hop;
+  const int T = frames_of(h, Lmax);
+  const int64_t nmel = (int64_t)B * T * 128;
+  VarlenAnalysis va;
+  varlen_analysis(h, "vfx_restore_gsr_varlen", wav, B, Lmax, lengths, true, target ? up_floats(nmel) + handler_metrics_ws_bytes(B, T) : 0,
+                  logmel_out, stream, va);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  constexpr int cap = kMaxVarlenClips;
+  int* const d_t = h->lens_row(LENS_FRAMES);
+  int* const d_gt = h->lens_row(LENS_GROUP_FRAMES);
+  int* const d_gi = h->lens_row(LENS_GROUP_INDEX);
+  int* const d_vl = h->lens_row(LENS_RUN_SAMPLES);
+  int* const d_vt = h->lens_row(LENS_RUN_FRAMES);
+  int* const d_vtp = h->lens_row(LENS_RUN_VOC_FRAMES);
+  const int unify = flags & 1;
+  const std::vector<int>& host = va.host;
+  const std::vector<VarlenAnalysis::Run>& runs = va.runs;
+  char* const sc = va.sc;
+  float* const mel = va.mel;
+  float* const lg = va.lg;
+  float* const den = reinterpret_cast<float*>(sc + va.o_den);
+  float* const vm = reinterpret_cast<float*>(sc + va.o_vmel);
+  float* const wlong = reinterpret_cast<float*>(sc + va.o_long);
+  float* const ws = reinterpret_cast<float*>(sc + va.o_ws);
+  float* const pk = reinterpret_cast<float*>(sc + va.o_pk);
   launch_from_log(lg, mel, B, T, unify, ws, den, s, d_t);
   // ---- the handler's scores against the target: its mel by pre() at its own length, then the clip's four numbers over its own frames
   if (target) {
+    const size_t o_tmel = va.o_tail, o_score = o_tmel + up_floats(nmel);
     int* const d_tl = h->lens_row(LENS_TARGET_SAMPLES);
     launch_set_frames(d_tl, target_lengths, B, s);
     float* const tmel = reinterpret_cast<float*>(sc + o_tmel);
@@ -1177,6 +1287,68 @@ int vfx_restore_gsr_varlen_scored(vfx_handle* h, const float* wav, const float* 
     return vfx_restore_gsr_varlen_1(h, wav + (int64_t)b * Lmax, n, Lmax, lengths + b, wav_out + (int64_t)b * Lmax,
                                     logmel_out ? logmel_out + (int64_t)b * T * 128 : nullptr, flags, stream, target + (int64_t)b * Lmax,
                                     target_lengths + b, metrics_out + (int64_t)b * VFX_N_HANDLER_METRICS);
+  });
+}
+
+// val_l of models/gsr_voicefixer.py:264-277 per clip: the first half of vfx_restore_gsr_varlen (varlen_analysis), then to_log(mel(target))
+// at the target's own length and the L1 over the clip's own T_b x 128 values.  No vocoder runs and none has to be loaded.
+static int vfx_validate_gsr_varlen_1(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                     const int* target_lengths, float* logmel_out, double* val_l, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  const int am = h->analysis_model;
+  VFX_CHECK(am == VFX_MODEL_UNET_MEL ? (bool)h->unet[am] : (bool)h->analysis[am - VFX_MODEL_GRU_MEL],
+            "vfx_validate_gsr_varlen: weights of the analysis module are not finalized");
+  const int hop = h->cfg.hop;
+  const int T = frames_of(h, Lmax);
+  const int64_t nmel = (int64_t)B * T * 128;
+  const int nchunk = l1_chunks((int64_t)T * 128);
+  VarlenAnalysis va;
+  varlen_analysis(h, "vfx_validate_gsr_varlen", wav, B, Lmax, lengths, false, up_floats(nmel) + (size_t)B * nchunk * sizeof(double), logmel_out,
+                  stream, va);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* const tlog = reinterpret_cast<float*>(va.sc + va.o_tail);
+  double* const chunk_ws = reinterpret_cast<double*>(va.sc + va.o_tail + up_floats(nmel));
+  int* const d_tl = h->lens_row(LENS_TARGET_SAMPLES);
+  int* const d_n = h->lens_row(LENS_LOSS_COUNT);
+  std::vector<int> count(B);
+  for (int b = 0; b < B; ++b) count[b] = 128 * va.host[(size_t)B + b];  // the first T_b rows of a clip are contiguous
+  launch_set_frames(d_tl, target_lengths, B, s);
+  launch_set_frames(d_n, count.data(), B, s);
+  launch_stft_mel(h->fe, target, B, Lmax, T, tlog, nullptr, nullptr, nullptr, 1, hop, 1e-8f, s, d_tl);
+  launch_l1_rows(va.lg, tlog, B, (int64_t)T * 128, d_n, nchunk, chunk_ws, s);
+  launch_loss_final(chunk_ws, nchunk, d_n, nullptr, 0, nullptr, 0, 0, val_l, 1, B, s);
+  VFX_API_END
+}
+
+// What vfx_validate_gsr_varlen checks of a whole batch before any sub-batch launches: check_scored_batch's rules without the 7-frame
+// minimum (no SSIM is computed here)
+static int check_validate_batch(vfx_handle* h, const char* who, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                                const int* target_lengths, const double* val_l) {
+  VFX_API_BEGIN
+  VFX_CHECK(h != nullptr, "NULL handle");
+  VFX_CHECK(wav && lengths && B > 0 && Lmax > 0, "%s: bad argument", who);
+  VFX_CHECK(target, "%s: target is NULL", who);
+  VFX_CHECK(val_l, "%s: val_l is NULL", who);
+  VFX_CHECK(h->cfg.n_mels == 128, "%s: needs 128 mel bands", who);
+  const int hop = h->cfg.hop, half = h->cfg.n_fft / 2;
+  for (int b = 0; b < B; ++b) {
+    const int Lb = lengths[b], Lt = target_lengths ? target_lengths[b] : Lb;
+    VFX_CHECK(Lb > half && Lb <= Lmax, "%s: clip %d has %d samples (need %d < length <= Lmax = %d)", who, b, Lb, half, Lmax);
+    VFX_CHECK(Lt > half && Lt <= Lmax, "%s: the target of clip %d has %d samples (need %d < length <= Lmax = %d)", who, b, Lt, half, Lmax);
+    VFX_CHECK(Lt / hop == Lb / hop, "%s: clip %d has %d frames (%d samples) but its target has %d (%d samples)", who, b, Lb / hop + 1, Lb,
+              Lt / hop + 1, Lt);
+  }
+  VFX_API_END
+}
+
+int vfx_validate_gsr_varlen(vfx_handle* h, const float* wav, const float* target, int B, int Lmax, const int* lengths,
+                            const int* target_lengths, float* logmel_out, double* val_l, void* stream) {
+  if (const int rc = check_validate_batch(h, "vfx_validate_gsr_varlen", wav, target, B, Lmax, lengths, target_lengths, val_l)) return rc;
+  if (!target_lengths) target_lengths = lengths;
+  const int T = Lmax / h->cfg.hop + 1;
+  return for_sub_batches(B, kLossMaxClips, [&](int b, int n) {
+    return vfx_validate_gsr_varlen_1(h, wav + (int64_t)b * Lmax, target + (int64_t)b * Lmax, n, Lmax, lengths + b, target_lengths + b,
+                                     logmel_out ? logmel_out + (int64_t)b * T * 128 : nullptr, val_l + b, stream);
   });
 }
 

@@ -166,7 +166,8 @@ enum LensRow {
   LENS_STOI_SAMPLES = 14, LENS_STOI_OUT = 15, LENS_STOI_FRAMES = 16,   // input samples / 10 kHz samples / frames of the vfx_stoi sub-batch in flight
   LENS_TARGET_SAMPLES = 17,                                            // samples of the targets of a vfx_restore_*_varlen_scored call
   LENS_BSS_SAMPLES = 18,                                               // samples of the vfx_bsseval sub-batch in flight
-  kLensRows = 19
+  LENS_LOSS_COUNT = 19, LENS_LOSS_FRAMES = 20,                         // elements per row / frames of the vfx_spec_losses or vfx_validate_gsr_varlen sub-batch in flight
+  kLensRows = 21
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -516,6 +517,22 @@ void launch_handler_metrics(const float* lg, const float* den, const float* tgt,
                             hipStream_t s);
 void launch_mel_metrics(const float* est, const float* tgt, int B, int T, const int* frames, char* ws, double* out, hipStream_t s);
 int64_t count_nonfinite(const float* p, int64_t n, hipStream_t s);  // debug aid, synchronises
+
+// losses.hip: the validation losses (vfx_spec_losses, vfx_validate_gsr_varlen).  Per-clip partial sums (float64) in ws; lens, n, counts,
+// frames: device, [B]
+constexpr int kL1Chunk = 4096;  // elements of a row per partial sum of k_l1_rows, cut from the row's own start
+constexpr int kLossMaxClips = 128;  // clips per launch set of the two entries: what bounds their scratch (a clip's numbers do not depend on it)
+inline int l1_chunks(int64_t n) { return (int)((n + kL1Chunk - 1) / kL1Chunk); }
+// est, tgt (B, L), pair b = the first lens[b] samples -> ws (B, T, 2): per frame t < lens[b] / hop + 1 the sums over the 1025 bins of
+// |se - st| and |log10 se - log10 st|, se / st = launch_stft_mel's magnitudes (eps) of the two clips, bit for bit; no spectrum is stored
+void launch_pair_stft_l1(const FrontEndTables& t, const float* est, const float* tgt, int B, int L, int T, const int* lens, int hop,
+                         float eps, double* ws, hipStream_t s);
+// a, b (B, ld), row r = its first n[r] elements -> ws (B, nchunk): sum |float32(a_i - b_i)| per chunk of kL1Chunk elements
+void launch_l1_rows(const float* a, const float* b, int B, int64_t ld, const int* n, int nchunk, double* ws, hipStream_t s);
+// out[b * stride] = clip b's chunk sums / counts[b] (chunk_ws given); out[b * stride + col + {0, 1}] = its frame sums / (frames[b] * nbins)
+// (frame_ws given)
+void launch_loss_final(const double* chunk_ws, int nchunk, const int* counts, const double* frame_ws, int T, const int* frames, int nbins,
+                       int col, double* out, int stride, int B, hipStream_t s);
 
 // stft_dft.hip: the front end of the scores at 16 kHz (vfx_audio_metrics_rate): |STFT| with n_fft 743, hop 160 as a DFT-matrix GEMM on
 // the f32-input MFMA, and the 80-band mel image.  An odd n_fft pads 371 samples on each side: 1 + (len - 1) / 160 frames.

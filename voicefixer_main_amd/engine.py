@@ -960,6 +960,48 @@ class Engine:
                                                           self._stream()), "vfx_restore_ssr_varlen_scored")
         return out, scores
 
+    def spec_losses(self, est, target, lengths=None):
+        """The three validation losses of waveform pairs, forward values only (vfx_spec_losses): est, target (B, L) or (L,), pair b =
+        the first lengths[b] samples of row b (default: all L; 1024 < lengths[b] <= L) -> (B, 3) float64 on the device, the columns
+        l1_wav, l1_sp, l1_log_sp (tools/pytorch/losses.py L1, L1_Sp, L1_Log_Sp) of each clip over its own samples and frames."""
+        est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)
+        if est.dim() == 1:
+            est, target = est[None], target[None]
+        if est.shape != target.shape or est.dim() != 2:
+            raise ValueError("spec_losses: est %s and target %s must be equal (B, L) tensors" % (tuple(est.shape), tuple(target.shape)))
+        B, L = est.shape
+        out = torch.empty((B, _lib.N_SPEC_LOSSES), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_spec_losses(self.h, _ptr(est), _ptr(target), B, L, self._lens_arg(lengths, B, "spec_losses"), _ptr(out),
+                                            self._stream()), "vfx_spec_losses")
+        return out
+
+    def l1_rows(self, a, b, counts=None):
+        """mean |a - b| over the first counts[r] elements (default: all) of every row of two equal (B, ...) float32 tensors, the rows
+        flattened -> (B,) float64 on the device (vfx_l1_rows): the L1 of tensors that are not waveforms -- the log-mel case of
+        losses.get_loss_function("l1") -- by the chunked float64 sums of spec_losses' column 0."""
+        a, b = _dev_f32(a, self.device), _dev_f32(b, self.device)
+        if a.shape != b.shape or a.dim() < 1:
+            raise ValueError("l1_rows: a %s and b %s must have one shape" % (tuple(a.shape), tuple(b.shape)))
+        B = a.shape[0] if a.dim() > 1 else 1
+        a, b = a.reshape(B, -1), b.reshape(B, -1)
+        out = torch.empty((B,), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_l1_rows(self.h, _ptr(a), _ptr(b), B, a.shape[1], self._lens_arg(counts, B, "l1_rows"), _ptr(out),
+                                        self._stream()), "vfx_l1_rows")
+        return out
+
+    def validate_gsr_varlen(self, wav, lengths, target, target_lengths=None, want_logmel=False):
+        """val_l of VoiceFixer's validation_step per clip, without the vocoder (vfx_validate_gsr_varlen): wav, target (B, Lmax), clip b =
+        wav[b, :lengths[b]], its target target[b, :target_lengths[b]] (default: lengths) -> val_l (B,) float64 on the device = the
+        mean over the clip's own T_b x 128 values of |log-mel estimate - to_log(mel(target))| [, logmel (B, T, 128): bit for bit
+        restore_gsr_varlen's].  Any mix of lengths; only the analysis module has to be loaded."""
+        wav, _, B, L, lengths = _clip_rows(_dev_f32(wav, self.device), lengths, "validate_gsr_varlen")
+        target, tarr = self._scored_args(target, target_lengths, B, L, "validate_gsr_varlen")
+        logmel = torch.empty((B, self.frames(L), N_MELS), device=self.device, dtype=torch.float32) if want_logmel else None
+        val_l = torch.empty((B,), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_validate_gsr_varlen(self.h, _ptr(wav), _ptr(target), B, L, (ctypes.c_int * B)(*lengths), tarr, _ptr(logmel),
+                                                    _ptr(val_l), self._stream()), "vfx_validate_gsr_varlen")
+        return (val_l, logmel) if want_logmel else val_l
+
     def check_negative_input(self):
         """`to_log`'s assert alone (pytorch_util.py:158): reads and clears ONLY the negative-input bit -- a saturation bit a
         deferred vocoder check still has to see stays raised."""

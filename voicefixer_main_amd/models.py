@@ -321,29 +321,31 @@ HANDLER_METRIC_KEYS = ("mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"
 MIN_SCORED_SAMPLES = 6 * 441   # 7 STFT frames: skimage's 7 x 7 SSIM refuses a smaller mel image
 
 
-def _restore_scored_list(engine, call, wavs, targets, max_batch, bucket_key, bucket_len, name):
-    """The list layer of the two restore_scored_list methods: clips and their targets sorted by length (longest first, as
-    dist.restore_sharded_lengths orders restore_list's), up to `max_batch` of one `bucket_key` per call, both padded to
-    `bucket_len(longest)`; `call(x, lengths, t, target_lengths)` -> (restored (B, Lmax), scores (B, 4) on the device).  ONE
-    device-to-host copy of the (B, 4) block per batch.  -> (restored clips, [{key: score}]) in input order."""
+MIN_VALIDATED_SAMPLES = 1025   # more than n_fft / 2 samples: the STFT's reflect padding
+
+
+def _paired_batches(engine, wavs, targets, max_batch, bucket_key, bucket_len, name, min_samples, min_why, what="scored", how="restored"):
+    """The list layer under restore_scored_list and validate_list: checks a list of clips and their targets, then yields the padded
+    batches to run -- clips sorted by length (longest first, as dist.restore_sharded_lengths orders restore_list's), up to
+    `max_batch` of one `bucket_key` per batch, both padded to `bucket_len(longest)` -- as (chunk = the clips' indices in the input
+    list, x (B, Lmax), lengths, t (B, Lmax), target_lengths)."""
     from . import dist as vdist
     if vdist.world_rank()[0] > 1:
-        raise RuntimeError("%s: scored sets are restored by one process (a process group of %d ranks is initialised)"
-                           % (name, vdist.world_rank()[0]))
+        raise RuntimeError("%s: %s sets are %s by one process (a process group of %d ranks is initialised)"
+                           % (name, what, how, vdist.world_rank()[0]))
     if len(wavs) != len(targets):
         raise ValueError("%s: %d clips and %d targets" % (name, len(wavs), len(targets)))
     hop = engine.hop
     lengths = [int(w.shape[-1]) for w in wavs]
     tlens = [int(t.shape[-1]) for t in targets]
     for i, (n, m) in enumerate(zip(lengths, tlens)):
-        if n < MIN_SCORED_SAMPLES:
-            raise ValueError("%s: clip %d has %d samples: the scores need at least %d (7 STFT frames)" % (name, i, n, MIN_SCORED_SAMPLES))
+        if n < min_samples:
+            raise ValueError("%s: clip %d has %d samples: %s at least %d (%s)" % (name, i, n, min_why[0], min_samples, min_why[1]))
         if n // hop != m // hop:
             raise ValueError("%s: clip %d has %d frames but its target has %d" % (name, i, n // hop + 1, m // hop + 1))
     buckets = {}
     for i, n in enumerate(lengths):
         buckets.setdefault(bucket_key(n), []).append(i)
-    restored, scores = [None] * len(wavs), [None] * len(wavs)
     for k in sorted(buckets, reverse=True):
         idx = sorted(buckets[k], key=lambda i: (-lengths[i], i))
         for a in range(0, len(idx), max_batch):
@@ -352,12 +354,52 @@ def _restore_scored_list(engine, call, wavs, targets, max_batch, bucket_key, buc
             width = bucket_len(max(lens))
             x = clips.pad([wavs[i].reshape(-1) for i in chunk], engine.device, torch.float32, width=width)
             t = clips.pad([targets[i].reshape(-1) for i in chunk], engine.device, torch.float32, width=width)
-            out, block = call(x, lens, t, tl)
-            block = block.cpu().tolist()     # the batch's one device-to-host copy of scores
-            for j, i in enumerate(chunk):
-                restored[i] = out[j, :lengths[i]]
-                scores[i] = {key: float(v) for key, v in zip(HANDLER_METRIC_KEYS, block[j])}
+            yield chunk, x, lens, t, tl
+
+
+def _restore_scored_list(engine, call, wavs, targets, max_batch, bucket_key, bucket_len, name):
+    """The two restore_scored_list methods over _paired_batches: `call(x, lengths, t, target_lengths)` -> (restored (B, Lmax),
+    scores (B, 4) on the device).  ONE device-to-host copy of the (B, 4) block per batch.  -> (restored clips, [{key: score}]) in
+    input order."""
+    restored, scores = [None] * len(wavs), [None] * len(wavs)
+    for chunk, x, lens, t, tl in _paired_batches(engine, wavs, targets, max_batch, bucket_key, bucket_len, name, MIN_SCORED_SAMPLES,
+                                                 ("the scores need", "7 STFT frames")):
+        out, block = call(x, lens, t, tl)
+        block = block.cpu().tolist()     # the batch's one device-to-host copy of scores
+        for j, i in enumerate(chunk):
+            restored[i] = out[j, :lens[j]]
+            scores[i] = {key: float(v) for key, v in zip(HANDLER_METRIC_KEYS, block[j])}
     return restored, scores
+
+
+def _validate_list(engine, call, wavs, targets, max_batch, bucket_key, bucket_len, name, equal_lengths=False):
+    """The two validate_list methods over _paired_batches: `call(x, lengths, t, target_lengths)` -> the loss per clip, (B,) float64 on
+    the device.  ONE device-to-host copy per batch.  -> ([loss per file] in input order, their mean: what Lightning logs as val_l
+    for an epoch of the reference's batch_size = 1 validation loader)."""
+    if equal_lengths:
+        for i, (w, t) in enumerate(zip(wavs, targets)):
+            if int(w.shape[-1]) != int(t.shape[-1]):
+                raise ValueError("%s: clip %d has %d samples but its target has %d: the spectrogram losses compare equal lengths"
+                                 % (name, i, int(w.shape[-1]), int(t.shape[-1])))
+    if len(wavs) == 0 and len(targets) == 0:
+        raise ValueError("%s: no clips" % name)
+    losses = [None] * len(wavs)
+    for chunk, x, lens, t, tl in _paired_batches(engine, wavs, targets, max_batch, bucket_key, bucket_len, name, MIN_VALIDATED_SAMPLES,
+                                                 ("the STFT needs", "more than n_fft / 2: reflect padding"), "validation", "scored"):
+        block = call(x, lens, t, tl).cpu().tolist()     # the batch's one device-to-host copy
+        for j, i in enumerate(chunk):
+            losses[i] = float(block[j])
+    return losses, math.fsum(losses) / len(losses)
+
+
+def _wave_batch(batch, key, name):
+    """batch[key] of the reference's validation loader, (B, L, 1) or (B, L) -> (B, L)."""
+    x = batch[key]
+    if x.dim() == 3 and x.shape[-1] == 1:
+        x = x[..., 0]
+    if x.dim() != 2:
+        raise ValueError("%s: batch['%s'] must be (B, L, 1) or (B, L), got %s" % (name, key, tuple(batch[key].shape)))
+    return x
 
 
 class _Base:
@@ -561,6 +603,28 @@ class VoiceFixer(_Base):
         return _restore_scored_list(eng, call, wavs, targets, max_batch, lambda L: 0, lambda L: eng.padded_frames(L) * eng.hop - 1,
                                     "VoiceFixer.restore_scored_list")
 
+    def validation_step(self, batch, batch_idx=0):
+        """models/gsr_voicefixer.py:264-277, forward value only: batch["noisy"], batch["vocals"] (B, L, 1) or (B, L) ->
+        {"loss": val_l}, the 0-dim float64 tensor L1(model(mel(noisy))['mel'], to_log(mel(vocals))) -- the number the training
+        script logs as val_l and writes into the checkpoint's file name.  The library computes it per clip, without the vocoder
+        (Engine.validate_gsr_varlen); the batch's value is the mean of the clips', which for the equal lengths of a batch is the
+        reference's batch mean."""
+        x, t = _wave_batch(batch, "noisy", "VoiceFixer.validation_step"), _wave_batch(batch, "vocals", "VoiceFixer.validation_step")
+        if x.shape != t.shape:
+            raise ValueError("VoiceFixer.validation_step: noisy %s and vocals %s differ in shape" % (tuple(x.shape), tuple(t.shape)))
+        return {"loss": self.engine.validate_gsr_varlen(x, [int(x.shape[1])] * int(x.shape[0]), t).mean()}
+
+    def validate_list(self, wavs, targets, max_batch=128):
+        """val_l of a validation set of (noisy, vocals) pairs of ARBITRARY lengths: lists of 1-D clips at 44.1 kHz -> ([val_l per
+        file] in input order, their mean).  The mean is what Lightning logs for an epoch of the reference's validation loader
+        (batch_size = 1).  The files go through the library as restore_scored_list's do (sorted by length, up to `max_batch` per
+        call, padded with their lengths), one device-to-host copy per batch, and never reach the vocoder.  A target must have its
+        clip's frame count (len // 441) and a clip more than 1024 samples.  Single process."""
+        eng = self.engine
+        call = lambda x, lens, t, tl: eng.validate_gsr_varlen(x, lens, t, tl)
+        return _validate_list(eng, call, wavs, targets, max_batch, lambda L: 0, lambda L: eng.padded_frames(L) * eng.hop - 1,
+                              "VoiceFixer.validate_list")
+
 
 class SSR_UNet(_Base):
     """models/ssr_unet.py:56-155 / models/gsr_unet.py (identical inference surface): the
@@ -612,6 +676,41 @@ class SSR_UNet(_Base):
         eng = self.engine
         return _restore_scored_list(eng, eng.restore_ssr_varlen_scored, wavs, targets, max_batch, eng.padded_frames,
                                     lambda L: eng.padded_frames(L) * eng.hop - 1, "SSR_UNet.restore_scored_list")
+
+    VALIDATE_AGAINST = ("target", "input")
+
+    def _l1_sp_call(self, against, name):
+        """(x, lengths, t, target_lengths) -> l1_sp per clip (B,) float64 on the device, of the restored clips against `against`;
+        restored and compared on the device, no host copy in between."""
+        if against not in self.VALIDATE_AGAINST:
+            raise ValueError("%s: against must be one of %s, got %r" % (name, self.VALIDATE_AGAINST, against))
+        eng = self.engine
+        return lambda x, lens, t, tl: eng.spec_losses(eng.restore_ssr_varlen(x, lens), t if against == "target" else x, lens)[:, 1]
+
+    def validation_step(self, batch, batch_idx=0, against="target"):
+        """validation_step of models/ssr_unet.py:227-234 and models/gsr_unet.py:225-232, forward value only: batch["noisy"],
+        batch["vocals"] (B, L, 1) or (B, L) -> {"loss": the 0-dim float64 tensor get_loss_function("l1_sp")(estimate, reference)},
+        the mean of the clips' own values (for the equal lengths of a batch: the reference's batch mean).
+          against="target" (default)  l1_sp(estimate, vocals): the training objective (ssr_unet.py:220, gsr_unet.py:218)
+          against="input"             l1_sp(estimate, noisy): what gsr_unet.py:230 logs as val_l -- it compares with the degraded input
+        ssr_unet.py:232 hands L1_Sp the target's SPECTROGRAM (sp_target) where it expects a waveform; that line is not reproduced."""
+        name = "SSR_UNet.validation_step"
+        x, t = _wave_batch(batch, "noisy", name), _wave_batch(batch, "vocals", name)
+        if x.shape != t.shape:
+            raise ValueError("%s: noisy %s and vocals %s differ in shape" % (name, tuple(x.shape), tuple(t.shape)))
+        x, t = x.to(self.device, torch.float32).contiguous(), t.to(self.device, torch.float32).contiguous()
+        lens = [int(x.shape[1])] * int(x.shape[0])
+        return {"loss": self._l1_sp_call(against, name)(x, lens, t, lens).mean()}
+
+    def validate_list(self, wavs, targets, max_batch=16, against="target"):
+        """validation_step over a validation set of (noisy, vocals) pairs of ARBITRARY lengths: lists of 1-D clips at 44.1 kHz ->
+        ([l1_sp per file] in input order, their mean: what Lightning logs for an epoch at the reference's batch_size = 1).
+        `against` as in validation_step.  A clip and its target must have EQUAL length (L1_Sp compares equal shapes) of more than
+        1024 samples.  The files are bucketed as restore_list's, restored by Engine.restore_ssr_varlen and compared by
+        Engine.spec_losses on the device; one device-to-host copy per batch.  Single process."""
+        eng = self.engine
+        return _validate_list(eng, self._l1_sp_call(against, "SSR_UNet.validate_list"), wavs, targets, max_batch, eng.padded_frames,
+                              lambda L: eng.padded_frames(L) * eng.hop - 1, "SSR_UNet.validate_list", equal_lengths=True)
 
 
 GSR_UNet = SSR_UNet
