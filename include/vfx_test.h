@@ -6,7 +6,9 @@
  * the fly, the launch synchronised -- so that tests/test_gpu_kernels.py can compare it with a float64 torch expression of the
  * same operator; every launch goes through a throw-away plan of the product's PlanBuilder (csrc/ops_debug.cpp), and vfx_op_voc_*,
  * vfx_op_resblock(fused), vfx_op_resblock_pair, vfx_op_unet_piece and vfx_op_analysis_piece run single launches exactly as the vocoder,
- * ResUNet and analysis plans build them.  An error returns 1 (2: an exception of the C++ library) and leaves its text as the library's last error.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
+ * ResUNet and analysis plans build them; tests/test_gpu_plan_chains.py chains them into the whole networks and holds vfx_resunet_mel,
+ * vfx_resunet_spec, vfx_vocoder and vfx_restore_gsr to those chains bit for bit (vfx_plan_unet, vfx_plan_voc_stack,
+ * vfx_op_voc_resblock_at and VFX_OP_STORED exist for that).  An error returns 1 (2: an exception of the C++ library) and leaves its text as the library's last error.  libvfx_test.so is linked against libvfx.so and uses its internals; the product (voicefixer_main_amd/models.py,
  * handlers.py, dist.py, bench.py's timed path) never loads it.
  */
 #ifndef VFX_TEST_H_
@@ -84,7 +86,13 @@ int vfx_op_block2d(vfx_handle* h, const float* x, int B, int H, int W, int C, co
  *   the plan picks it (*used_up16 = 1), else on the phased k_conv.  src_act = 0: the launch reads x through its LeakyReLU(up_slope)
  *   prologue; 1: it reads the ACTIVATED form of LeakyReLU(x, up_slope), built here in the handle's operand form (16-bit mode: fp16).
  *   want_raw: the raw fp32 output into y; want_act: the activated output LeakyReLU(., act_slope) (act_slope = 1: the fp16 trunk of the
- *   16-bit mode) into ya, widened to fp32 from the stored form.  ya starts as NaN patterns; y is the caller's (fill it first). */
+ *   16-bit mode) into ya, widened to fp32 from the stored form.  ya starts as NaN patterns; y is the caller's (fill it first).
+ *
+ * VFX_OP_STORED, or-ed into src_act / want_act of vfx_op_voc_upsample and into src_act / residual_act / next_act of vfx_op_voc_conv1d: that
+ *   activated tensor crosses the call in its STORED form, byte for byte -- fp32 (precision 0), [32 hi bf16 | 32 lo bf16] per pixel and
+ *   32-channel chunk (precision 1, 4 bytes per element), fp16 (precision 2) -- a device buffer of the caller instead of fp32 values this
+ *   library converts: what one launch stored is what the next one reads, as in the plan (tests/plan_chains.py). */
+#define VFX_OP_STORED 0x100
 int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, int Cin, const float* weight, const float* bias, int stride,
                         float up_slope, int src_act, int want_raw, int want_act, float act_slope, const int* lens, float* y, float* ya,
                         int* used_up16, void* stream);
@@ -117,6 +125,19 @@ int vfx_op_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C, cons
                         const float* b2, int dil, const float* w1b, const float* b1b, const float* w2b, const float* b2b, int dil2,
                         float slope, float act_slope, int want_raw, int want_act, const int* lens, int lens_mul, float* y, float* ya,
                         int* info, void* stream);
+/* vfx_op_voc_resblock at a stated place of the plan, without lens: last_stage != 0 -- the stack in front of the tail -- instead of
+ *   !want_act, and xa = the activated fp16 trunk fp16(LeakyReLU(., slope)) of a wide layer (C = 256 in the 16-bit mode) as the launch in
+ *   front of it stored it, a device buffer of B * T * C halves, instead of one built from x; x is NULL where xa is the trunk's only form,
+ *   xa is NULL for the other widths. */
+int vfx_op_voc_resblock_at(vfx_handle* h, const float* x, const void* xa, int B, int T, int C, const float* w1, const float* b1,
+                           const float* w2, const float* b2, int dil, const float* w1b, const float* b1b, const float* w2b,
+                           const float* b2b, int dil2, float slope, float act_slope, int last_stage, int want_raw, int want_act, float* y,
+                           float* ya, int* info, void* stream);
+/* No launch, the handle's configuration only: how its vocoder plan runs the ResStack of C channels.  out[3] = kind (0: two k_conv launches
+ * per layer, 1: one fused launch per layer or pair on the raw trunk, 2: one fused launch per layer on the activated trunk), the trunk
+ * between the stack's launches is fp16 (last_stage != 0: of the stack in front of the tail), the layers of dilation dil and dil2 > 0 run
+ * as ONE launch. */
+int vfx_plan_voc_stack(vfx_handle* h, int C, int last_stage, int dil, int dil2, int* out);
 /* Host-only: the kernel the vocoder plan runs a Cin -> Cout = Cin / 2 upsampler of stride s over T input positions on (a stage behind the
  * first and not the last, in precision mode `precision` with vfx_config.tuning = `tuning`): 1 = k_up16, 0 = the phased k_conv,
  * -1 = bad arguments. */
@@ -152,6 +173,12 @@ int vfx_op_unet_piece(vfx_handle* h, int model, const char* piece, int B, int H,
  * block, 6 persistent C = 32 block), ksplit (1 = no split-K), activated output, bias, K segments, output channels. */
 int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches, int cap,
                         int* nlaunch);
+/* Host-only, as vfx_plan_unet_piece: what the WHOLE plan of the mel ResUNet entry point (model VFX_MODEL_UNET_MEL) or of the spectrogram
+ * one (VFX_MODEL_UNET_SPEC) launches for B clips of T frames -- build_unet_mel / build_unet_spec, the functions the product entry points
+ * build their plan with, short_clip and with it every split-K factor picked from T as they pick it.  The rows are those of
+ * vfx_plan_unet_piece in the order describe_unet_launches reports: the small kernels, then the fused blocks, then the convolutions,
+ * each group in launch order.  tests/test_plan_chains_host.py holds it to the concatenation of the pieces' lists. */
+int vfx_plan_unet(int model, int B, int T, int precision, int tuning, int* launches, int cap, int* nlaunch);
 
 /* The bi_gru / dnn analysis plans' launches (analysis.hip: k_dense, k_gru_seq), one PIECE at a time, for
  * tests/test_gpu_analysis_launches.py.  The piece is appended to a plan of its own by the member of the plan builder that vfx_analysis_mel

@@ -389,15 +389,21 @@ extern "C" int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, 
   VFX_API_BEGIN_H(h)
   VFX_CHECK(x && weight && bias && B > 0 && T > 0 && stride >= 1 && Cin % 64 == 0 && (want_raw || want_act) && (!want_raw || y) &&
                 (!want_act || ya),
-            "vfx_op_voc_upsample: bad argument");
+            "vfx_op_voc_upsample: bad argument (x %p, weight %p, bias %p, B %d, T %d, Cin %d, stride %d, want_raw %d -> y %p, want_act %d -> ya %p)",
+            (const void*)x, (const void*)weight, (const void*)bias, B, T, Cin, stride, want_raw, (void*)y, want_act, (void*)ya);
   hipStream_t s = static_cast<hipStream_t>(stream);
   OneOff o(h);
   vfx_config cfg = h->cfg;
   cfg.voc_up_slope = up_slope;
   const int form = h->cfg.precision;  // of the activated tensors
   const size_t nin = (size_t)B * T * Cin, nout = (size_t)B * T * stride * (Cin / 2);
+  const bool src_stored = (src_act & VFX_OP_STORED) != 0, act_stored = (want_act & VFX_OP_STORED) != 0;
+  src_act &= ~VFX_OP_STORED;
+  want_act &= ~VFX_OP_STORED;
   const VocConvW up = pack_voc_upsampler(cfg, o.blob, weight, bias, Cin, stride, src_act != 0);
-  const float* src = src_act ? o.in(to_stored(x, nin, form, ACT_LEAKY, up_slope)) : o.in(x, nin * sizeof(float));
+  const float* src = !src_act     ? o.in(x, nin * sizeof(float))
+                     : src_stored ? o.in(x, stored_bytes(form, nin))
+                                  : o.in(to_stored(x, nin, form, ACT_LEAKY, up_slope));
   float* dy = want_raw ? o.out(y, nout * sizeof(float)) : nullptr;
   const size_t aoff = want_act ? o.pb.arena.alloc(stored_bytes(form, nout)) : 0;
   std::vector<TapSeg> phases;
@@ -405,8 +411,9 @@ extern "C" int vfx_op_voc_upsample(vfx_handle* h, const float* x, int B, int T, 
                                               act_slope, upload_lens(o.blob, lens, B), 1, phases);
   o.pb.no_splitk = true;  // as build_vocoder
   o.pb.add_conv_phased(p, phases);
+  if (want_act && act_stored) o.copy_out(ya, aoff, stored_bytes(form, nout));
   o.run(s);
-  if (want_act) to_device(ya, from_stored(o.window(aoff, stored_bytes(form, nout)).data(), nout, form));
+  if (want_act && !act_stored) to_device(ya, from_stored(o.window(aoff, stored_bytes(form, nout)).data(), nout, form));
   if (used_up16) *used_up16 = o.plan.host_params[0].up16;
   VFX_API_END
 }
@@ -415,6 +422,11 @@ extern "C" int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, in
                                  int K, int dil, int reflect, int src_act, int act, float slope, const float* residual, int residual_act,
                                  int want_raw, int next_act, float next_slope, const int* lens, float* y, float* ya, void* stream) {
   VFX_API_BEGIN_H(h)
+  const bool src_stored = (src_act & VFX_OP_STORED) != 0, res_stored = (residual_act & VFX_OP_STORED) != 0,
+             act_stored = (next_act & VFX_OP_STORED) != 0;
+  src_act &= ~VFX_OP_STORED;
+  residual_act &= ~VFX_OP_STORED;
+  next_act &= ~VFX_OP_STORED;
   VFX_CHECK(x && weight && bias && B > 0 && T > 0 && (K == 3 || K == 7) && dil >= 1 && (want_raw || next_act != ACT_NONE) &&
                 (!want_raw || y) && (next_act == ACT_NONE || ya) && (!residual_act || residual),
             "vfx_op_voc_conv1d: bad argument");
@@ -424,19 +436,23 @@ extern "C" int vfx_op_voc_conv1d(vfx_handle* h, const float* x, int B, int T, in
   const int form = cfg.precision;  // of the activated tensors
   const size_t nin = (size_t)B * T * Cin, nout = (size_t)B * T * Cout;
   const VocConvW cw = pack_voc_conv1d(cfg, o.blob, weight, bias, Cin, Cout, K, src_act != 0);
-  const float* src = src_act ? o.in(to_stored(x, nin, form, act, slope)) : o.in(x, nin * sizeof(float));
+  const float* src = !src_act     ? o.in(x, nin * sizeof(float))
+                     : src_stored ? o.in(x, stored_bytes(form, nin))
+                                  : o.in(to_stored(x, nin, form, act, slope));
   // residual_act: the activated fp16 trunk fp16(LeakyReLU(residual, res_slope)) of the 16-bit mode
-  const float* res = !residual ? nullptr
-                     : residual_act ? o.in(to_stored(residual, nout, FORM_F16, ACT_LEAKY, cfg.voc_res_slope))
-                                    : o.in(residual, nout * sizeof(float));
+  const float* res = !residual       ? nullptr
+                     : !residual_act ? o.in(residual, nout * sizeof(float))
+                     : res_stored    ? o.in(residual, stored_bytes(FORM_F16, nout))
+                                     : o.in(to_stored(residual, nout, FORM_F16, ACT_LEAKY, cfg.voc_res_slope));
   float* dy = want_raw ? o.out(y, nout * sizeof(float)) : nullptr;
   const bool want_act = next_act != ACT_NONE;
   const size_t aoff = want_act ? o.pb.arena.alloc(stored_bytes(form, nout)) : 0;
   o.pb.no_splitk = true;  // as build_vocoder
   o.pb.add_conv(voc_conv1d_params(cfg, cw, B, T, K, dil, reflect != 0, src, src_act != 0, act, slope, res, residual_act != 0, dy,
                                   want_act ? const_cast<float*>(rel_ptr(aoff)) : nullptr, next_act, next_slope, upload_lens(o.blob, lens, B), 1));
+  if (want_act && act_stored) o.copy_out(ya, aoff, stored_bytes(form, nout));
   o.run(s);
-  if (want_act) to_device(ya, from_stored(o.window(aoff, stored_bytes(form, nout)).data(), nout, form));
+  if (want_act && !act_stored) to_device(ya, from_stored(o.window(aoff, stored_bytes(form, nout)).data(), nout, form));
   VFX_API_END
 }
 
@@ -489,7 +505,7 @@ struct ResBlockRun {
 };
 ResBlockRun run_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C, const ResLayerHost& la, int dil, const ResLayerHost* lb,
                              int dil2, float slope, float act_slope, bool last_stage, bool want_raw, bool want_act, const int* lens,
-                             int lens_mul, hipStream_t s);  // below
+                             int lens_mul, hipStream_t s, const void* xa16 = nullptr);  // below
 }  // namespace
 
 // One fused ResStack launch (a layer, or a pair: dil2 > 0) the way build_vocoder adds it (run_voc_resblock).  want_act: a stack in front
@@ -515,6 +531,45 @@ extern "C" int vfx_op_voc_resblock(vfx_handle* h, const float* x, int B, int T, 
   VFX_API_END
 }
 
+// ... at a stated place of the plan: last_stage says which stack the layer belongs to (vfx_op_voc_resblock takes want_act for it), and
+// xa is the activated fp16 trunk of a wide layer as the launch in front of it stored it -- x is NULL where that trunk is the only form.
+extern "C" int vfx_op_voc_resblock_at(vfx_handle* h, const float* x, const void* xa, int B, int T, int C, const float* w1, const float* b1,
+                                      const float* w2, const float* b2, int dil, const float* w1b, const float* b1b, const float* w2b,
+                                      const float* b2b, int dil2, float slope, float act_slope, int last_stage, int want_raw, int want_act,
+                                      float* y, float* ya, int* info, void* stream) {
+  VFX_API_BEGIN_H(h)
+  VFX_CHECK((x || xa) && w1 && b1 && w2 && b2 && B > 0 && T > 0 && C > 0 && dil >= 1 && dil2 >= 0 && (want_raw || want_act) &&
+                (!want_raw || y) && (!want_act || ya) && (dil2 == 0 || (w1b && b1b && w2b && b2b)),
+            "vfx_op_voc_resblock_at: bad argument");
+  vfx_config cfg = h->cfg;
+  cfg.voc_res_slope = slope;
+  const int kind = voc_resblock_kind(cfg, C);
+  VFX_CHECK(kind != VOC_RES_TWO_LAUNCHES, "the plan of this handle runs a %d-channel layer as two k_conv launches", C);
+  const bool wide = kind == VOC_RES_FUSED_WIDE, t16 = voc_resblock_trunk_f16(cfg, C, last_stage != 0);
+  VFX_CHECK(wide ? (xa && (t16 || x)) : (x && !xa), "vfx_op_voc_resblock_at: a %d-channel layer of this handle reads %s", C,
+            wide ? (t16 ? "xa alone" : "x and xa") : "x alone");
+  const ResLayerHost lb{w1b, b1b, w2b, b2b};
+  const ResBlockRun r = run_voc_resblock(h, x, B, T, C, ResLayerHost{w1, b1, w2, b2}, dil, dil2 > 0 ? &lb : nullptr, dil2, slope, act_slope,
+                                         last_stage != 0, want_raw != 0, want_act != 0, nullptr, 1, static_cast<hipStream_t>(stream), xa);
+  const size_t nel = (size_t)B * T * C;
+  if (info) std::copy(r.info, r.info + 12, info);
+  if (want_raw) to_device(y, from_stored(r.y.data(), nel, r.y_form));
+  if (want_act) to_device(ya, from_stored(r.ya.data(), nel, FORM_F16));
+  VFX_API_END
+}
+
+// Host work only (the handle's configuration, no launch): how the vocoder plan of this handle runs the ResStack of C channels --
+// out[0] = 0 two k_conv launches per layer / 1 one fused launch on the raw trunk / 2 one fused launch on the activated trunk, out[1] = its trunk is fp16 (last_stage: the stack in
+// front of the tail), out[2] = the layers of dilation dil, dil2 run as one launch (dil2 = 0: not asked).
+extern "C" int vfx_plan_voc_stack(vfx_handle* h, int C, int last_stage, int dil, int dil2, int* out) {
+  VFX_API_BEGIN
+  VFX_CHECK(h && C > 0 && out, "vfx_plan_voc_stack: bad argument");
+  out[0] = voc_resblock_kind(h->cfg, C);
+  out[1] = voc_resblock_trunk_f16(h->cfg, C, last_stage != 0) ? 1 : 0;
+  out[2] = dil2 > 0 && out[0] == VOC_RES_FUSED && voc_resblock_pair_ok(h->cfg, C, dil, dil2) ? 1 : 0;
+  VFX_API_END
+}
+
 namespace {
 // One fused ResStack launch (a layer, or a pair: lb != NULL) the way build_vocoder adds it: voc_resblock_params + add_resblock, the
 // trunk in the form voc_resblock_trunk_f16 gives this width on this handle.  Both outputs live in ONE arena buffer between guard zones,
@@ -522,7 +577,7 @@ namespace {
 // not given -- that changed is an error of the call.
 ResBlockRun run_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C, const ResLayerHost& la, int dil, const ResLayerHost* lb,
                              int dil2, float slope, float act_slope, bool last_stage, bool want_raw, bool want_act, const int* lens,
-                             int lens_mul, hipStream_t s) {
+                             int lens_mul, hipStream_t s, const void* xa16) {
   OneOff o(h);
   vfx_config cfg = h->cfg;
   cfg.voc_res_slope = slope;
@@ -539,7 +594,10 @@ ResBlockRun run_voc_resblock(vfx_handle* h, const float* x, int B, int T, int C,
   if (lb) l2 = pack(*lb);
   const float* dx = wide ? (t16 ? nullptr : o.in(x, nel * sizeof(float)))
                          : (t16 ? o.in(to_stored(x, nel, FORM_F16, ACT_NONE, 1.f)) : o.in(x, nel * sizeof(float)));
-  const float* dxa = wide ? o.in(to_stored(x, nel, FORM_F16, ACT_LEAKY, slope)) : nullptr;
+  // xa16 (vfx_op_voc_resblock_at): the activated fp16 trunk as its producer stored it, instead of one built here from x
+  const float* dxa = !wide ? nullptr
+                     : xa16 ? o.in(static_cast<const float*>(xa16), stored_bytes(FORM_F16, nel))
+                            : o.in(to_stored(x, nel, FORM_F16, ACT_LEAKY, slope));
   ResBlockRun r;
   r.y_form = (t16 && !wide) ? FORM_F16 : FORM_F32;
   const size_t guard = 1 << 16, ybytes = (stored_bytes(r.y_form, nel) + 255) / 256 * 256, abytes = (nel * 2 + 255) / 256 * 256;
@@ -770,6 +828,19 @@ extern "C" int vfx_op_analysis_piece(vfx_handle* h, int model, const char* piece
   VFX_API_END
 }
 
+namespace {
+// The channel counts of every ResUNet block with no tensors behind them, for host-side planning: a block with a shortcut has a bias
+UNetWeights planning_shapes() {
+  UNetWeights shapes = unet_weight_shapes();
+  static float dummy;  // never dereferenced (host-side planning only)
+  auto mark = [](ConvBlockW& w) { if (w.shortcut) w.bsc = &dummy; };
+  for (auto& lv : shapes.enc) for (auto& w : lv) mark(w);
+  for (auto& D : shapes.dec) for (auto& w : D.blocks) mark(w);
+  shapes.c1_bsc = &dummy;
+  return shapes;
+}
+}  // namespace
+
 extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int arg, int short_clip, int precision, int tuning, int* launches,
                                    int cap, int* nlaunch) {
   VFX_API_BEGIN
@@ -778,12 +849,7 @@ extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int a
   VFX_CHECK(vfx_default_config(&hh.cfg) == 0, "no default config");
   hh.cfg.precision = precision;
   hh.cfg.tuning = tuning;
-  UNetWeights shapes = unet_weight_shapes();
-  static float dummy;  // never dereferenced (host-side planning only): a block with a shortcut has a bias
-  auto mark = [](ConvBlockW& w) { if (w.shortcut) w.bsc = &dummy; };
-  for (auto& lv : shapes.enc) for (auto& w : lv) mark(w);
-  for (auto& D : shapes.dec) for (auto& w : D.blocks) mark(w);
-  shapes.c1_bsc = &dummy;
+  const UNetWeights shapes = planning_shapes();
   Plan plan;
   PlanBuilder pb{&hh, &plan, {}};
   pb.short_clip = short_clip;
@@ -794,6 +860,30 @@ extern "C" int vfx_plan_unet_piece(const char* piece, int B, int H, int W, int a
   pc.W = W;
   pc.arg = arg;
   build_unet_piece(pb, shapes, pc);
+  *nlaunch = describe_unet_launches(plan, launches, launches ? cap : 0);
+  VFX_API_END
+}
+
+// The WHOLE plan of vfx_resunet_mel / vfx_resunet_spec, planned on the host as the piece above is: build_unet_mel / build_unet_spec --
+// what run_plan calls for the product entry points -- over external buffers that nothing resolves.
+extern "C" int vfx_plan_unet(int model, int B, int T, int precision, int tuning, int* launches, int cap, int* nlaunch) {
+  VFX_API_BEGIN
+  VFX_CHECK((model == VFX_MODEL_UNET_MEL || model == VFX_MODEL_UNET_SPEC) && B > 0 && T > 0 && nlaunch && precision >= 0 && precision <= 2,
+            "vfx_plan_unet: bad argument");
+  vfx_handle hh;  // never touches a device: the builders only plan
+  VFX_CHECK(vfx_default_config(&hh.cfg) == 0, "no default config");
+  hh.cfg.precision = precision;
+  hh.cfg.tuning = tuning;
+  hh.unet[model] = std::make_shared<UNetWeights>(planning_shapes());
+  Plan plan;
+  PlanBuilder pb{&hh, &plan, {}};
+  BufRef ext[5];
+  for (int i = 0; i < 5; ++i) {
+    ext[i].ext = true;
+    ext[i].slot = i;
+  }
+  if (model == VFX_MODEL_UNET_MEL) build_unet_mel(pb, B, T, ext[0], ext[1]);
+  else build_unet_spec(pb, B, T, ext[0], ext[1], ext[2], ext[3], ext[4]);
   *nlaunch = describe_unet_launches(plan, launches, launches ? cap : 0);
   VFX_API_END
 }

@@ -1128,39 +1128,68 @@ class Engine:
         return y
 
     # the vocoder's launches as its plan builds them (include/vfx_test.h: vfx_op_voc_*)
-    def op_voc_upsample(self, x, weight, bias, stride, up_slope=0.2, src_act=True, want_raw=False, act_slope=None, lens=None):
+    OP_STORED = 0x100   # VFX_OP_STORED (include/vfx_test.h)
+
+    def stored_tensor(self, shape):
+        """A device buffer for an ACTIVATED tensor of `shape` in the form the launches of this handle store it (`stored=True` of
+        op_voc_upsample / op_voc_conv1d): fp16 in the 16-bit mode; otherwise four bytes per element -- fp32 values in the fp32 mode,
+        the packed bf16 pairs of the split-bf16 mode, which are no fp32 values.  Starts as NaN patterns."""
+        t = torch.empty(shape, device=self.device, dtype=torch.float16 if self.precision == 2 else torch.float32)
+        t.view(torch.uint8).fill_(0xff)
+        return t
+
+    def _stored_arg(self, t, name):
+        want = torch.float16 if self.precision == 2 else torch.float32
+        if not (isinstance(t, torch.Tensor) and t.dtype == want and t.is_cuda and t.is_contiguous()):
+            raise ValueError("%s: a stored tensor is a contiguous %s device tensor (Engine.stored_tensor)" % (name, want))
+        return t
+
+    def op_voc_upsample(self, x, weight, bias, stride, up_slope=0.2, src_act=True, want_raw=False, act_slope=None, lens=None,
+                        stored=False):
         """One upsampler on x (B, T, Cin): -> (y raw or None, ya activated or None, ran_on_k_up16).  act_slope None: no activated
-        output; 1.0: the fp16 trunk of the 16-bit mode.  y starts as NaN, so do unwritten elements of ya."""
-        x = _dev_f32(x, self.device)
+        output; 1.0: the fp16 trunk of the 16-bit mode.  y starts as NaN, so do unwritten elements of ya.  stored: the activated
+        tensors -- x where src_act, ya -- cross the call as the launches store them (stored_tensor), byte for byte."""
+        x = self._stored_arg(x, "op_voc_upsample") if stored and src_act else _dev_f32(x, self.device)
         B, T, Cin = x.shape
         w, b = _host(weight), _host(bias)
         Cout = w.shape[1]
         shape = (B, T * stride, Cout)
         y = torch.full(shape, float("nan"), device=self.device) if want_raw else None
-        ya = torch.empty(shape, device=self.device) if act_slope is not None else None
+        ya = None if act_slope is None else (self.stored_tensor(shape) if stored else torch.empty(shape, device=self.device))
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
         up16 = ctypes.c_int(-1)
+        st = self.OP_STORED if stored else 0
         _lib.check(_lib.load_test().vfx_op_voc_upsample(
-            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), int(stride), float(up_slope), int(bool(src_act)), int(bool(want_raw)),
-            int(act_slope is not None), float(act_slope if act_slope is not None else 1.0), _hptr(ln), _ptr(y), _ptr(ya),
+            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), int(stride), float(up_slope), (1 | st) if src_act else 0, int(bool(want_raw)),
+            (1 | st) if act_slope is not None else 0, float(act_slope if act_slope is not None else 1.0), _hptr(ln), _ptr(y), _ptr(ya),
             ctypes.byref(up16), self._stream()), "vfx_op_voc_upsample")
         return y, ya, bool(up16.value)
 
     def op_voc_conv1d(self, x, weight, bias, dil=1, reflect=False, src_act=False, act=0, slope=1.0, residual=None, residual_act=False,
-                      want_raw=True, next_act=0, next_slope=1.0, lens=None):
-        """Conv1d of the vocoder plan on x (B, T, Cin): -> (y raw or None, ya activated or None); both start as NaN."""
-        x = _dev_f32(x, self.device)
+                      want_raw=True, next_act=0, next_slope=1.0, lens=None, stored=False):
+        """Conv1d of the vocoder plan on x (B, T, Cin): -> (y raw or None, ya activated or None); both start as NaN.  stored: the
+        activated tensors -- x where src_act, the residual where residual_act (fp16), ya -- cross the call as the launches store
+        them (stored_tensor), byte for byte."""
+        x = self._stored_arg(x, "op_voc_conv1d") if stored and src_act else _dev_f32(x, self.device)
         B, T, Cin = x.shape
         w, b = _host(weight), _host(bias)
         Cout, _, K = w.shape
         y = torch.full((B, T, Cout), float("nan"), device=self.device) if want_raw else None
-        ya = torch.empty((B, T, Cout), device=self.device) if next_act else None
-        res = None if residual is None else _dev_f32(residual, self.device)
+        ya = None if not next_act else (self.stored_tensor((B, T, Cout)) if stored else torch.empty((B, T, Cout), device=self.device))
+        if residual is None:
+            res = None
+        elif stored and residual_act:
+            res = residual
+            if not (res.dtype == torch.float16 and res.is_cuda and res.is_contiguous()):
+                raise ValueError("op_voc_conv1d: a stored activated residual is a contiguous fp16 device tensor")
+        else:
+            res = _dev_f32(residual, self.device)
         ln = None if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        st = self.OP_STORED if stored else 0
         _lib.check(_lib.load_test().vfx_op_voc_conv1d(
-            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), Cout, K, int(dil), int(bool(reflect)), int(bool(src_act)), int(act),
-            float(slope), _ptr(res), int(bool(residual_act)), int(bool(want_raw)), int(next_act), float(next_slope), _hptr(ln),
-            _ptr(y), _ptr(ya), self._stream()), "vfx_op_voc_conv1d")
+            self.h, _ptr(x), B, T, Cin, _hptr(w), _hptr(b), Cout, K, int(dil), int(bool(reflect)), (1 | st) if src_act else 0, int(act),
+            float(slope), _ptr(res), (1 | st) if residual_act else 0, int(bool(want_raw)), int(next_act) | (st if next_act else 0),
+            float(next_slope), _hptr(ln), _ptr(y), _ptr(ya), self._stream()), "vfx_op_voc_conv1d")
         return y, ya
 
     def op_voc_final(self, x, weight, bias, slope=0.2, x_f16=False, lens=None, want_peak=False):
@@ -1199,6 +1228,35 @@ class Engine:
             float(slope), float(act_slope), int(bool(want_raw)), int(bool(want_act)), _hptr(ln), int(lens_mul), _ptr(y), _ptr(ya), info,
             self._stream()), "vfx_op_voc_resblock")
         return y, ya, dict(zip(self.RESBLOCK_INFO, info))
+
+    def op_voc_resblock_at(self, x, xa, layer, dil, layer2=None, dil2=0, slope=0.01, act_slope=0.2, last_stage=False, want_raw=True,
+                           want_act=False):
+        """op_voc_resblock at a stated place of the plan: last_stage -- the stack in front of the tail -- and xa, the activated fp16
+        trunk of a wide layer as the launch in front of it stored it (an fp16 device tensor; None for the other widths); x is None
+        where xa is the trunk's only form.  -> (y, ya, info) as op_voc_resblock."""
+        x = None if x is None else _dev_f32(x, self.device)
+        if xa is not None and not (xa.dtype == torch.float16 and xa.is_cuda and xa.is_contiguous()):
+            raise ValueError("op_voc_resblock_at: xa is a contiguous fp16 device tensor")
+        B, T, C = (x if x is not None else xa).shape
+        la = [_host(a) for a in layer]
+        lb = [_host(a) for a in layer2] if layer2 is not None else [None] * 4
+        y = torch.full((B, T, C), float("nan"), device=self.device) if want_raw else None
+        ya = torch.full((B, T, C), float("nan"), device=self.device) if want_act else None
+        info = (ctypes.c_int * len(self.RESBLOCK_INFO))()
+        _lib.check(_lib.load_test().vfx_op_voc_resblock_at(
+            self.h, _ptr(x), _ptr(xa), B, T, C, *[_hptr(a) for a in la], int(dil), *[_hptr(a) for a in lb],
+            int(dil2 if layer2 is not None else 0), float(slope), float(act_slope), int(bool(last_stage)), int(bool(want_raw)),
+            int(bool(want_act)), _ptr(y), _ptr(ya), info, self._stream()), "vfx_op_voc_resblock_at")
+        return y, ya, dict(zip(self.RESBLOCK_INFO, info))
+
+    VOC_STACK_KINDS = ("two_launches", "fused", "fused_wide")
+
+    def plan_voc_stack(self, C, last_stage=False, dil=1, dil2=0):
+        """How this handle's vocoder plan runs the ResStack of C channels (no launch) -> (kind, one of VOC_STACK_KINDS; the trunk
+        between its launches is fp16; the layers of dilation dil and dil2 run as one launch)."""
+        out = (ctypes.c_int * 3)()
+        _lib.check(_lib.load_test().vfx_plan_voc_stack(self.h, int(C), int(bool(last_stage)), int(dil), int(dil2), out), "vfx_plan_voc_stack")
+        return self.VOC_STACK_KINDS[out[0]], bool(out[1]), bool(out[2])
 
     # the STFT / ISTFT front end and the glue launches of a restore call (include/vfx_test.h); every output starts as NaN
     @staticmethod
@@ -1340,6 +1398,19 @@ class Engine:
         _lib.check(_lib.load_test().vfx_plan_unet_piece(piece.encode(), B, H, W, int(arg), int(short_clip), int(precision), int(tuning),
                                                         buf, 48, ctypes.byref(n)), "vfx_plan_unet_piece")
         return Engine._unet_launches(buf, min(n.value, 8))
+
+    @staticmethod
+    def plan_unet(model, B, T, precision=1, tuning=0):
+        """Host-only: the launches of the WHOLE plan of resunet_mel (MODEL_UNET_MEL) / resunet_spec (MODEL_UNET_SPEC) for B clips of T
+        frames, as plan_unet_piece reports a piece's: the small kernels, then the fused blocks, then the convolutions, each group
+        in launch order.  Needs no GPU."""
+        cap = 6 * 512
+        n, buf = ctypes.c_int(0), (ctypes.c_int * cap)()
+        _lib.check(_lib.load_test().vfx_plan_unet(int(model), int(B), int(T), int(precision), int(tuning), buf, cap, ctypes.byref(n)),
+                   "vfx_plan_unet")
+        if n.value * 6 > cap:
+            raise RuntimeError("plan_unet: %d launches" % n.value)
+        return Engine._unet_launches(buf, n.value)
 
     # the bi_gru / dnn plans' launches, one at a time, built by the plan's own builder (include/vfx_test.h: vfx_op_analysis_piece)
     ANALYSIS_PIECE_WIDTHS = {"lin1": 256, "proj0": 1536, "gru0": 512, "proj1": 1536, "gru1": 512, "lin4": 256, "lin6": 128,
