@@ -283,6 +283,51 @@ int vfx_chunk_ola(vfx_handle* h, const float* frames, const float* window, float
                   int n_chunks, int win, int hop, int lead, int L, float* y, void* stream);
 
 /*
+ * Streaming sessions: the same two chunkers for signals that arrive in blocks.  A session holds `slots` independent mono
+ * streams with all audio on the device: an input ring (capacity samples) and an output ring (out_capacity samples) per slot
+ * and, in overlap-add mode, the partial sums of the span that later chunks still change.  Fed in any blocking, a slot's
+ * output is bit for bit what the offline pair above gives for its whole signal; which chunk is due, and every ring
+ * position, is worked out on the host from sample counts (no call copies anything back from the device to decide).
+ *
+ *   mode 0, overlap-add: win even, 1 <= hop_or_margin = hop <= win.  Chunk k >= 1 is x[k hop - win, k hop) and is due once
+ *     k hop samples are fed; sample n is released when chunk (n + win) / hop is stitched.  capacity >= win.
+ *   mode 1, boxcar: hop_or_margin = in_margin >= 0.  Frame 0 is x[0, win + margin), frame k x[k win - margin,
+ *     (k + 1) win + margin), due once its last sample is fed; its win output samples are released when it is stitched.
+ *     capacity >= win + 2 margin.
+ *   window: `win` floats on the DEVICE (copied), or NULL for the factor `scale`.  out_capacity >= win.
+ *
+ * One step:  push blocks -> next: the due chunks of all slots, ordered by slot, then ascending k, as ONE batch
+ * (rows, row_len) with zeros outside the signal -> the caller's network on that batch -> put: the results are stitched and
+ * whatever no later chunk can change goes to the output rings -> pop.  A group holds rows of one length only and at most
+ * max_rows; what does not fit comes with the following `next` (rows = 0: nothing is due).  A chunk is not handed out
+ * while its slot's output ring has no room for what it would release.  vfx_stream_close marks a slot: its remaining
+ * chunks, zero-filled past the end -- in boxcar mode the last frame at its own length without a back margin, as the
+ * offline class runs it -- then come through the same next / put, after which the slot can be opened again as soon as
+ * its output is popped.  A call that is refused (a push that would overrun an input ring, a slot that is not open, a
+ * put without a next, ...) changes nothing.
+ */
+typedef struct vfx_stream vfx_stream;
+int vfx_stream_create(vfx_handle* h, int slots, int mode, int win, int hop_or_margin, const float* window, float scale,
+                      int64_t capacity, int64_t out_capacity, vfx_stream** st);
+int vfx_stream_destroy(vfx_stream* st);
+int vfx_stream_open(vfx_stream* st, int* slot);
+/* counts[i] samples for slots[i], one after the other in packed_blocks (DEVICE); a slot at most once per call */
+int vfx_stream_push(vfx_stream* st, int n, const int* slots, const int64_t* counts, const float* packed_blocks, void* stream);
+int vfx_stream_close(vfx_stream* st, int slot);
+/* chunks_out (DEVICE): room for max_rows rows of the longest row (win, resp. win + 2 margin); rows * row_len floats are written */
+int vfx_stream_next(vfx_stream* st, int max_rows, float* chunks_out, int* rows, int* row_len, void* stream);
+/* frames (DEVICE): (rows, row_len) of the outstanding `next`, the network's output for its rows in their order */
+int vfx_stream_put(vfx_stream* st, const float* frames, void* stream);
+int vfx_stream_available(vfx_stream* st, int slot, int64_t* n);
+/* what a push to the slot may hold now: the free part of its input ring, 0 for a slot that is not open */
+int vfx_stream_room(vfx_stream* st, int slot, int64_t* n);
+/* samples fed to and released by the slot's current (or last) stream */
+int vfx_stream_state(vfx_stream* st, int slot, int64_t* fed, int64_t* released);
+/* up to max_counts[i] released samples of slots[i], one after the other in packed_out (DEVICE); counts_out[i] were there */
+int vfx_stream_pop(vfx_stream* st, int n, const int* slots, const int64_t* max_counts, float* packed_out, int64_t* counts_out,
+                   void* stream);
+
+/*
  * Polyphase resampling to the library's rate: librosa.load(path, sr=44100) (tools/utils.py:46-48), i.e.
  * scipy.signal.resample_poly(x, up, down) on float32 input, bit for bit.  up / down are reduced by their gcd first; with
  * M = max(up, down), hl = 10 M, the filter has ntaps = 2 hl + 1 taps, `taps` (DEVICE, fp32) = the taps resample_poly builds:

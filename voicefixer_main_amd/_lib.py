@@ -25,6 +25,7 @@ FLAG_PEAK_NORMALISED = 4  # vfx_restore_gsr divided a clip by its peak (the refe
 N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metrics
 N_HANDLER_METRICS = 4     # VFX_N_HANDLER_METRICS: the columns of vfx_restore_*_varlen_scored
 BSSEVAL_SLAB = 8192       # VFX_BSSEVAL_SLAB: samples per partial sum of vfx_bsseval
+STREAM_OLA, STREAM_BOXCAR = 0, 1   # the modes of vfx_stream_create
 N_SPEC_LOSSES = 3         # VFX_N_SPEC_LOSSES: the columns of vfx_spec_losses (l1_wav, l1_sp, l1_log_sp)
 
 
@@ -86,6 +87,17 @@ SIGNATURES = {
     "vfx_chunk_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_chunk_ola": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_void_p, c_void_p]),
+    "vfx_stream_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int64, c_int64, POINTER(c_void_p)]),
+    "vfx_stream_destroy": (c_int, [c_void_p]),
+    "vfx_stream_open": (c_int, [c_void_p, POINTER(c_int)]),
+    "vfx_stream_push": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int64), c_void_p, c_void_p]),
+    "vfx_stream_close": (c_int, [c_void_p, c_int]),
+    "vfx_stream_next": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
+    "vfx_stream_put": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vfx_stream_available": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "vfx_stream_room": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "vfx_stream_state": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "vfx_stream_pop": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p]),
     "vfx_resunet_mel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "vfx_analysis_mel": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     "vfx_select_analysis": (c_int, [c_void_p, c_int]),

@@ -4,6 +4,7 @@
 #include <numeric>
 
 #include "clip_batch.h"
+#include "stream.h"
 #include "vfx_internal.h"
 
 namespace vfx {
@@ -1430,6 +1431,157 @@ int vfx_restore_ssr_varlen_scored(vfx_handle* h, const float* wav, const float* 
     return vfx_restore_ssr_varlen_1(h, wav + (int64_t)b * Lmax, n, Lmax, lengths + b, wav_out + (int64_t)b * Lmax, stream,
                                     target + (int64_t)b * Lmax, target_lengths + b, metrics_out + (int64_t)b * VFX_N_HANDLER_METRICS);
   });
+}
+
+// ---------------------------------------------------------------------------------------------
+// streaming sessions: the bookkeeping is stream_sched.cpp's, the kernels stream.hip's; here the two meet the device memory
+// ---------------------------------------------------------------------------------------------
+}  // extern "C"
+
+struct vfx_stream {
+  vfx_handle* h = nullptr;
+  vfx::StreamSched sched;
+  int mode, win, par;
+  int cap_in, cap_out;
+  float scale;
+  float *d_in = nullptr, *d_acc = nullptr, *d_out = nullptr, *d_window = nullptr;
+  int row_len = 0;   // of the outstanding group
+  std::vector<vfx::StreamCopyRow> copy_rows;
+  std::vector<vfx::StreamGatherRow> gather_rows;
+  std::vector<vfx::StreamOlaRow> ola_rows;
+  std::vector<vfx::StreamBoxRow> box_rows;
+  vfx_stream(vfx_handle* h_, int slots, int mode_, int win_, int par_, float scale_, int64_t ci, int64_t co)
+      : h(h_), sched(slots, mode_, win_, par_, ci, co), mode(mode_), win(win_), par(par_), cap_in((int)ci), cap_out((int)co), scale(scale_) {}
+  ~vfx_stream() {
+    (void)hipFree(d_in);
+    (void)hipFree(d_acc);
+    (void)hipFree(d_out);
+    (void)hipFree(d_window);
+  }
+};
+
+// the session's handle names the device and the turn: a NULL session is refused before it is looked into
+#define VFX_STREAM_BEGIN(st, stream)              \
+  if (!(st)) {                                    \
+    ::vfx::set_error("vfx_stream: NULL session"); \
+    return 1;                                     \
+  }                                               \
+  VFX_API_BEGIN_HS((st)->h, stream)
+#define VFX_SCHED(call) VFX_CHECK((call), "vfx_stream: %s", st->sched.error.c_str())
+
+extern "C" {
+
+int vfx_stream_create(vfx_handle* h, int slots, int mode, int win, int hop_or_margin, const float* window, float scale, int64_t capacity,
+                      int64_t out_capacity, vfx_stream** out) {
+  VFX_API_BEGIN_H(h)
+  VFX_CHECK(out != nullptr, "vfx_stream_create: st is NULL");
+  std::string why;
+  VFX_CHECK(StreamSched::check_geometry(slots, mode, win, hop_or_margin, capacity, out_capacity, &why), "vfx_stream_create: %s", why.c_str());
+  auto st = std::make_unique<vfx_stream>(h, slots, mode, win, hop_or_margin, scale, capacity, out_capacity);
+  VFX_HIP(hipMalloc(&st->d_in, (size_t)slots * capacity * sizeof(float)));
+  VFX_HIP(hipMalloc(&st->d_out, (size_t)slots * out_capacity * sizeof(float)));
+  if (mode == STREAM_OLA) {
+    VFX_HIP(hipMalloc(&st->d_acc, (size_t)slots * 2 * win * sizeof(float)));
+    VFX_HIP(hipMemset(st->d_acc, 0, (size_t)slots * 2 * win * sizeof(float)));
+  }
+  if (window) {
+    VFX_HIP(hipDeviceSynchronize());   // the caller's window may still be on its way on some stream
+    VFX_HIP(hipMalloc(&st->d_window, (size_t)win * sizeof(float)));
+    VFX_HIP(hipMemcpy(st->d_window, window, (size_t)win * sizeof(float), hipMemcpyDeviceToDevice));
+  }
+  VFX_HIP(hipDeviceSynchronize());
+  *out = st.release();
+  VFX_API_END
+}
+
+int vfx_stream_destroy(vfx_stream* st) {
+  if (!st) return 0;
+  VFX_API_BEGIN_H(st->h)
+  VFX_HIP(hipDeviceSynchronize());
+  delete st;
+  VFX_API_END
+}
+
+int vfx_stream_open(vfx_stream* st, int* slot) {
+  VFX_API_BEGIN
+  VFX_CHECK(st && slot, "vfx_stream_open: NULL argument");
+  VFX_SCHED(st->sched.open(slot));
+  VFX_API_END
+}
+
+int vfx_stream_close(vfx_stream* st, int slot) {
+  VFX_API_BEGIN
+  VFX_CHECK(st != nullptr, "vfx_stream_close: NULL session");
+  VFX_SCHED(st->sched.close(slot));
+  VFX_API_END
+}
+
+int vfx_stream_available(vfx_stream* st, int slot, int64_t* n) {
+  VFX_API_BEGIN
+  VFX_CHECK(st && n, "vfx_stream_available: NULL argument");
+  VFX_CHECK(st->sched.available(slot, n), "vfx_stream_available: slot %d does not exist", slot);
+  VFX_API_END
+}
+
+int vfx_stream_room(vfx_stream* st, int slot, int64_t* n) {
+  VFX_API_BEGIN
+  VFX_CHECK(st && n, "vfx_stream_room: NULL argument");
+  VFX_CHECK(st->sched.room(slot, n), "vfx_stream_room: slot %d does not exist", slot);
+  VFX_API_END
+}
+
+int vfx_stream_state(vfx_stream* st, int slot, int64_t* fed, int64_t* released) {
+  VFX_API_BEGIN
+  VFX_CHECK(st && fed && released, "vfx_stream_state: NULL argument");
+  VFX_CHECK(st->sched.state(slot, fed, released), "vfx_stream_state: slot %d does not exist", slot);
+  VFX_API_END
+}
+
+int vfx_stream_push(vfx_stream* st, int n, const int* slots, const int64_t* counts, const float* packed_blocks, void* stream) {
+  VFX_STREAM_BEGIN(st, stream)
+  VFX_CHECK(n >= 0 && (n == 0 || (slots && counts)), "vfx_stream_push: bad argument");
+  for (int i = 0; i < n; ++i) VFX_CHECK(counts[i] <= 0 || packed_blocks, "vfx_stream_push: packed_blocks is NULL");
+  VFX_SCHED(st->sched.push(n, slots, counts, &st->copy_rows));   // refused before anything is copied
+  launch_stream_copy(true, st->d_in, st->cap_in, const_cast<float*>(packed_blocks), st->copy_rows, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+int vfx_stream_next(vfx_stream* st, int max_rows, float* chunks_out, int* rows, int* row_len, void* stream) {
+  VFX_STREAM_BEGIN(st, stream)
+  VFX_CHECK(chunks_out && rows && row_len, "vfx_stream_next: NULL argument");
+  VFX_SCHED(st->sched.next(max_rows, &st->gather_rows, &st->row_len));
+  *rows = (int)st->gather_rows.size();
+  *row_len = st->row_len;
+  if (*rows) launch_stream_gather(st->d_in, st->cap_in, st->row_len, chunks_out, st->gather_rows, static_cast<hipStream_t>(stream));
+  VFX_API_END
+}
+
+int vfx_stream_put(vfx_stream* st, const float* frames, void* stream) {
+  VFX_STREAM_BEGIN(st, stream)
+  VFX_CHECK(frames != nullptr, "vfx_stream_put: frames is NULL");
+  VFX_SCHED(st->sched.put(&st->ola_rows, &st->box_rows));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (st->mode == STREAM_OLA)
+    launch_stream_ola(frames, st->d_window, st->scale, st->win, st->par, st->d_acc, st->d_out, st->cap_out, st->ola_rows, s);
+  else
+    launch_stream_box(frames, st->row_len, st->d_window, st->scale, st->d_out, st->cap_out, st->box_rows, s);
+  VFX_API_END
+}
+
+int vfx_stream_pop(vfx_stream* st, int n, const int* slots, const int64_t* max_counts, float* packed_out, int64_t* counts_out,
+                   void* stream) {
+  VFX_STREAM_BEGIN(st, stream)
+  VFX_CHECK(n >= 0 && (n == 0 || (slots && max_counts && counts_out)), "vfx_stream_pop: bad argument");
+  if (!packed_out) {   // nothing may be taken without a place to put it
+    for (int i = 0; i < n; ++i) {
+      int64_t have = 0;
+      VFX_CHECK(st->sched.available(slots[i], &have), "vfx_stream_pop: slot %d does not exist", slots[i]);
+      VFX_CHECK(have == 0 || max_counts[i] == 0, "vfx_stream_pop: packed_out is NULL");
+    }
+  }
+  VFX_SCHED(st->sched.pop(n, slots, max_counts, &st->copy_rows, counts_out));
+  launch_stream_copy(false, st->d_out, st->cap_out, packed_out, st->copy_rows, static_cast<hipStream_t>(stream));
+  VFX_API_END
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -411,6 +411,83 @@ class Engine:
                                           self._stream()), "vfx_chunk_ola")
         return y
 
+    # ------------------------------------------------------------------ streaming sessions (vfx_stream_*; streaming.py drives them)
+    def stream_create(self, slots, mode, win, hop_or_margin, window, scale, capacity, out_capacity):
+        """A session of `slots` streams -> its handle.  mode: _lib.STREAM_OLA (hop) or _lib.STREAM_BOXCAR (in_margin); window: (win,)
+        or None for the factor `scale`."""
+        if window is not None:
+            window = _dev_f32(window, self.device)
+            if window.numel() != win:
+                raise ValueError("stream_create: the window has %d samples, window size is %d" % (window.numel(), win))
+        st = ctypes.c_void_p()
+        _lib.check(self.lib.vfx_stream_create(self.h, int(slots), int(mode), int(win), int(hop_or_margin), _ptr(window), float(scale),
+                                              int(capacity), int(out_capacity), ctypes.byref(st)), "vfx_stream_create")
+        return st
+
+    def stream_destroy(self, st):
+        _lib.check(self.lib.vfx_stream_destroy(st), "vfx_stream_destroy")
+
+    def stream_open(self, st):
+        slot = ctypes.c_int()
+        _lib.check(self.lib.vfx_stream_open(st, ctypes.byref(slot)), "vfx_stream_open")
+        return slot.value
+
+    def stream_push(self, st, slots, counts, packed):
+        """counts[i] samples for slots[i], one after the other in `packed` (1-D float32 on the device)."""
+        n = len(slots)
+        if packed is not None and (packed.dtype != torch.float32 or packed.device != self.device or not packed.is_contiguous()
+                                   or packed.numel() < sum(counts)):
+            raise ValueError("stream_push: packed must be a contiguous float32 tensor on %s with all %d samples" % (self.device, sum(counts)))
+        _lib.check(self.lib.vfx_stream_push(st, n, (ctypes.c_int * max(n, 1))(*slots), (ctypes.c_int64 * max(n, 1))(*counts),
+                                            _ptr(packed), self._stream()), "vfx_stream_push")
+
+    def stream_close(self, st, slot):
+        _lib.check(self.lib.vfx_stream_close(st, int(slot)), "vfx_stream_close")
+
+    def stream_next(self, st, max_rows, chunks):
+        """The due chunks into `chunks` (room for max_rows of the longest row) -> (rows, row_len); rows = 0: nothing is due."""
+        rows, row_len = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.lib.vfx_stream_next(st, int(max_rows), _ptr(chunks), ctypes.byref(rows), ctypes.byref(row_len),
+                                            self._stream()), "vfx_stream_next")
+        return rows.value, row_len.value
+
+    def stream_put(self, st, frames):
+        """frames: the network's output for the rows of the outstanding stream_next, contiguous float32 (rows, row_len)."""
+        if frames is not None and (frames.dtype != torch.float32 or frames.device != self.device or not frames.is_contiguous()):
+            raise ValueError("stream_put: frames must be a contiguous float32 tensor on %s" % self.device)
+        _lib.check(self.lib.vfx_stream_put(st, _ptr(frames), self._stream()), "vfx_stream_put")
+
+    def stream_available(self, st, slot):
+        n = ctypes.c_int64()
+        _lib.check(self.lib.vfx_stream_available(st, int(slot), ctypes.byref(n)), "vfx_stream_available")
+        return n.value
+
+    def stream_room(self, st, slot):
+        """How many samples a push to the slot may hold now."""
+        n = ctypes.c_int64()
+        _lib.check(self.lib.vfx_stream_room(st, int(slot), ctypes.byref(n)), "vfx_stream_room")
+        return n.value
+
+    def stream_state(self, st, slot):
+        """(fed, released) of the slot's stream."""
+        fed, released = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self.lib.vfx_stream_state(st, int(slot), ctypes.byref(fed), ctypes.byref(released)), "vfx_stream_state")
+        return fed.value, released.value
+
+    def stream_pop(self, st, slots, max_counts):
+        """Up to max_counts[i] released samples of slots[i] -> a list of 1-D device tensors (views of one packed buffer)."""
+        n = len(slots)
+        have = [min(int(m), self.stream_available(st, s)) for s, m in zip(slots, max_counts)]
+        packed = torch.empty(max(sum(have), 1), device=self.device, dtype=torch.float32)
+        got = (ctypes.c_int64 * max(n, 1))()
+        _lib.check(self.lib.vfx_stream_pop(st, n, (ctypes.c_int * max(n, 1))(*slots), (ctypes.c_int64 * max(n, 1))(*have), _ptr(packed),
+                                           got, self._stream()), "vfx_stream_pop")
+        out, off = [], 0
+        for i in range(n):
+            out.append(packed[off:off + got[i]])
+            off += got[i]
+        return out
+
     # ------------------------------------------------------------------ resampling (librosa.load(path, sr) = scipy resample_poly)
     @staticmethod
     def resample_ratio(sr_in, sr_out):
