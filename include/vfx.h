@@ -176,6 +176,29 @@ int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int
  * NULL pointer, B <= 0, a length outside (n_fft/2, L], a negative cut or overlapping buffers. */
 int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* lengths, const int* cut_bins, float* out, void* stream);
 
+/*
+ * The bandwidth detector of load_wav_energy (tools/utils.py:33-44) for a padded batch of clips at 44.1 kHz: wav (B, Lmax) device
+ * floats, clip b = the first L_b = lengths[b] samples of row b; lengths is a HOST array int[B] with n_fft/2 < lengths[b] <= Lmax, or
+ * NULL: every clip has Lmax samples.  1 <= hop <= 2048 (librosa.stft's default is 512), 0 < threshold <= 1.  Per clip:
+ *   S = the STFT of the clip alone: n_fft 2048, `hop`, periodic Hann, centred frames with reflect padding at the clip's OWN ends,
+ *       T_b = L_b / hop + 1 frames, |S| = sqrt(re^2 + im^2) in float32 with NO eps clamp (vfx_stft_phase(eps = 0)'s arithmetic);
+ *   e[k] = sum_t log10((double)|S[k, t]| + 1), k = 0 .. 1024, in float64                                       -> energy[b][k]
+ *   P[k] = sum_{j<k} e[j], the EXCLUSIVE prefix in ascending k (the loop of utils.py:38-39); total = P[1024]: bin 1024 never counts;
+ *   cut_bin[b] = the first k that does not have P[k] < total * threshold (utils.py:41-43).  An all-zero clip gives 0.
+ * The cut-off in Hz is int((sample_rate / 2) * (cut_bin / 1025.0)) -- left to the caller.  energy: (B, VFX_BAND_BINS) device doubles,
+ * or NULL; cut_bin: B device ints.  A wave sums a fixed number of consecutive frames of one clip, a clip's partial sums are added by
+ * index: a clip's 1025 numbers and its bin do not depend on the batch it is in, on Lmax, or on what lies at or past its end (which is
+ * never read).  No spectrum is written to memory.  More than 128 clips run as consecutive sub-batches.  The partial sums live in the
+ * handle's grow-only varlen scratch: while a hipGraph captured from a plan is alive, a call that would have to grow it fails with a
+ * message that says so.
+ * Fails, naming the clip and launching nothing, for a NULL wav or cut_bin, B <= 0, or a length, hop or threshold out of range (and
+ * for a clip of more than 2^24 frames).
+ */
+#define VFX_BAND_BINS 1025
+int vfx_band_energy(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths /* HOST, or NULL: all Lmax */,
+                    int hop, double threshold, double* energy /* (B, 1025) device, may be NULL */,
+                    int* cut_bin /* (B) device */, void* stream);
+
 /* Generator.forward of models/gsr_voicefixer.py:86-91 with the mel ResUNet
  * (models/components/unet.py:60-103): linear mel (B, T, 128) >= 0 -> log10 mel (B, T, 128). */
 int vfx_resunet_mel(vfx_handle* h, const float* mel_linear, int B, int T, float* logmel_out,

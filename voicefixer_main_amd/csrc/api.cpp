@@ -278,6 +278,46 @@ int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* l
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// bandwidth detector (tools/utils.py:33-44 load_wav_energy on the device: band.hip)
+// ---------------------------------------------------------------------------------------------
+int vfx_band_energy(vfx_handle* h, const float* wav, int B, int Lmax, const int* lengths, int hop, double threshold, double* energy,
+                    int* cut_bin, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(wav && cut_bin, "vfx_band_energy: NULL argument");
+  VFX_CHECK(B > 0 && Lmax > 0, "vfx_band_energy: need B > 0 and Lmax > 0, got B=%d Lmax=%d", B, Lmax);
+  VFX_CHECK(h->cfg.n_fft == 2048, "vfx_band_energy: needs the 44.1 kHz front end (n_fft 2048)");
+  VFX_CHECK(hop >= 1 && hop <= h->cfg.n_fft, "vfx_band_energy: hop = %d (need 1 <= hop <= %d)", hop, h->cfg.n_fft);
+  VFX_CHECK(threshold > 0.0 && threshold <= 1.0, "vfx_band_energy: threshold = %g (need 0 < threshold <= 1)", threshold);
+  constexpr int kMaxFrames = 1 << 24;  // per clip: the groups of a launch set stay far inside 32 bits
+  const int half = h->cfg.n_fft / 2;
+  std::vector<int> host(B);
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    const int Lb = lengths ? lengths[b] : Lmax;
+    VFX_CHECK(Lb > half && Lb <= Lmax, "vfx_band_energy: clip %d has %d samples (need %d < length <= Lmax = %d: reflect padding)", b, Lb,
+              half, Lmax);
+    VFX_CHECK(Lb <= 0x7fffffff - 2 * h->cfg.n_fft && Lb / hop + 1 <= kMaxFrames,
+              "vfx_band_energy: clip %d has %d samples, %d frames at hop %d (at most %d frames)", b, Lb, Lb / hop + 1, hop, kMaxFrames);
+    host[b] = Lb;
+    longest = std::max(longest, Lb);
+  }
+  // the group partials of a launch set: at most kBandMaxClips clips, and fewer while a set of them would pass 256 MB
+  const int groups = band_groups(longest, hop);
+  const size_t clip_bytes = (size_t)groups * VFX_BAND_BINS * sizeof(double);
+  const int step = (int)std::max<size_t>(1, std::min<size_t>(std::min(B, kBandMaxClips), ((size_t)256 << 20) / clip_bytes));
+  double* const ws = reinterpret_cast<double*>(h->scratch.ensure(
+      h, (size_t)step * clip_bytes, 8, "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured from plan "
+      "'%s': run the largest vfx_band_energy batch once BEFORE capturing"));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int b0 = 0; b0 < B; b0 += step) {  // (a clip's numbers do not depend on the launch it is in)
+    const int n = std::min(step, B - b0);
+    launch_band_energy(h->fe, wav + (int64_t)b0 * Lmax, n, Lmax, host.data() + b0, hop, threshold, groups, ws,
+                       slice_rows(energy, b0, VFX_BAND_BINS), cut_bin + b0, s);
+  }
+  VFX_API_END
+}
+
 int vfx_mel_project(vfx_handle* h, const float* sp, int64_t rows, float* mel, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(sp && mel && rows > 0, "bad argument");

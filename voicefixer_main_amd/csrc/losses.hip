@@ -48,34 +48,6 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[kWaves])
   __syncthreads();
 }
 
-// v = the frame's sample pairs times the window: the first step of k_stft_mel's frame walk
-__device__ __forceinline__ void window_frame(const float2 (&xin)[16], const float2* wl, int lane, float2 (&v)[16]) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float2 ww = wl[lane + 64 * r];
-    v[r] = make_float2(xin[r].x * ww.x, xin[r].y * ww.y);
-  }
-}
-
-// The windowed frame v -> mag[m] = |X[lane + 64 m]|, top = |X[1024]| (lane 0; 0 elsewhere): the transform, the mirror and the untangle
-// in k_stft_mel's order, with its expressions.  On return the wave's LDS buffer is free.
-__device__ __forceinline__ void frame_magnitudes(float2 (&v)[16], float2* zw, const float2* twl, float2 rtw_lane, int lane, float eps,
-                                                 float (&mag)[16], float& top) {
-  wfft1024<-1>(v, zw, twl, lane);
-  float2 zn[16];
-  mirror_bins(v, zn, zw, lane);
-  if (lane == 0) zn[0] = v[0];  // Z[1024] = Z[0]
-  __builtin_amdgcn_sched_barrier(0);
-  float re, im;
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    untangle_bin(v[m], zn[m], rtw_of(rtw_lane, m), eps, re, im, mag[m]);
-    if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // four bins at a time, as in the forward kernel
-  }
-  top = 0.f;
-  if (lane == 0) untangle_bin(v[0], zn[0], make_float2(-1.f, 0.f), eps, re, im, top);  // W^1024 = -1
-}
-
 }  // namespace
 
 // est, tgt (B, L), pair b = the first lens[b] samples of both rows (NFFT / 2 < lens[b] <= L; lens: device) -> ws[(b T + t) 2 + k],

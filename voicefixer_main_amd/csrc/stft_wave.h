@@ -1,6 +1,6 @@
 // stft_wave.h -- the wave-level arithmetic of the STFT front end that more than one kernel file evaluates: the 1024-point complex FFT
 // of one wave, the reflect-padded frame load, the real-FFT untangle and the clamped magnitude.  stft.hip (k_stft_mel, k_istft,
-// k_stft_lowpass) and losses.hip (k_pair_stft_l1) include it; a magnitude is the same float32 in all of them.
+// k_stft_lowpass), losses.hip (k_pair_stft_l1) and band.hip (k_band_energy) include it; a magnitude is the same float32 in all of them.
 #pragma once
 #include "vfx_internal.h"
 
@@ -188,6 +188,35 @@ __device__ __forceinline__ void untangle_bin(float2 zk, float2 znk, float2 wk, f
   re = fmaf(0.5f, zk.x + znk.x, wo.x);  // E + W^k O
   im = fmaf(0.5f, zk.y - znk.y, wo.y);
   mag = __builtin_amdgcn_sqrtf(fmaxf(fmaf(im, im, re * re), eps));
+}
+
+// ---- the frame walk of the kernels that keep no spectrum (k_pair_stft_l1, k_band_energy) ------------------------------------------
+// v = the frame's sample pairs times the window: the first step of k_stft_mel's frame walk
+__device__ __forceinline__ void window_frame(const float2 (&xin)[16], const float2* wl, int lane, float2 (&v)[16]) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float2 ww = wl[lane + 64 * r];
+    v[r] = make_float2(xin[r].x * ww.x, xin[r].y * ww.y);
+  }
+}
+
+// The windowed frame v -> mag[m] = |X[lane + 64 m]|, top = |X[1024]| (lane 0; 0 elsewhere): the transform, the mirror and the untangle
+// in k_stft_mel's order, with its expressions.  On return the wave's LDS buffer is free.
+__device__ __forceinline__ void frame_magnitudes(float2 (&v)[16], float2* zw, const float2* twl, float2 rtw_lane, int lane, float eps,
+                                                 float (&mag)[16], float& top) {
+  wfft1024<-1>(v, zw, twl, lane);
+  float2 zn[16];
+  mirror_bins(v, zn, zw, lane);
+  if (lane == 0) zn[0] = v[0];  // Z[1024] = Z[0]
+  __builtin_amdgcn_sched_barrier(0);
+  float re, im;
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    untangle_bin(v[m], zn[m], rtw_of(rtw_lane, m), eps, re, im, mag[m]);
+    if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // four bins at a time, as in the forward kernel
+  }
+  top = 0.f;
+  if (lane == 0) untangle_bin(v[0], zn[0], make_float2(-1.f, 0.f), eps, re, im, top);  // W^1024 = -1
 }
 
 }  // namespace vfx

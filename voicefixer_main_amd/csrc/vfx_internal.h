@@ -556,6 +556,17 @@ void launch_l1_rows(const float* a, const float* b, int B, int64_t ld, const int
 void launch_loss_final(const double* chunk_ws, int nchunk, const int* counts, const double* frame_ws, int T, const int* frames, int nbins,
                        int col, double* out, int stride, int B, hipStream_t s);
 
+// band.hip: the bandwidth detector (vfx_band_energy).  The clips' lengths travel as kernel arguments, at most kBandMaxClips per launch
+// set (clip_batch.h).
+constexpr int kBandFrames = 8;      // consecutive frames of a clip per wave of k_band_energy: a constant, so that which frames a partial
+                                    // sum holds depends on the clip alone
+constexpr int kBandMaxClips = 128;  // clips per launch set
+inline int band_groups(int len, int hop) { return (len / hop + 1 + kBandFrames - 1) / kBandFrames; }  // partial sums per bin of a clip
+// wav (nb, ld), clip b = its first len[b] samples (len: HOST, nb <= kBandMaxClips, n_fft/2 < len[b] <= ld) -> energy (nb, 1025) or
+// NULL, cut_bin (nb).  groups >= band_groups(len[b], hop) for every b; ws: nb * groups * 1025 doubles.
+void launch_band_energy(const FrontEndTables& t, const float* wav, int nb, int64_t ld, const int* len, int hop, double threshold,
+                        int groups, double* ws, double* energy, int* cut_bin, hipStream_t s);
+
 // stft_dft.hip: the front end of the scores at 16 kHz (vfx_audio_metrics_rate): |STFT| with n_fft 743, hop 160 as a DFT-matrix GEMM on
 // the f32-input MFMA, and the 80-band mel image.  An odd n_fft pads 371 samples on each side: 1 + (len - 1) / 160 frames.
 constexpr int kDftN = 743, kDftHop = 160, kDftBins = kDftN / 2 + 1, kDftMels = 80, kDftRate = 16000;

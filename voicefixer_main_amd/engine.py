@@ -284,6 +284,34 @@ class Engine:
                                              self._stream()), "vfx_stft_lowpass")
         return y[0] if squeeze else y
 
+    def band_energy(self, wav, lengths=None, hop=512, threshold=0.95):
+        """The bandwidth detector of load_wav_energy (tools/utils.py:33-44) for a padded batch (vfx_band_energy): wav (B, L) or (L,),
+        clip b = the first lengths[b] samples of row b (default L; 1024 < lengths[b] <= L), 1 <= hop <= 2048 (librosa.stft's default
+        512), 0 < threshold <= 1 -> (energy (B, 1025) float64: e[k] = sum_t log10(|STFT[k, t]| + 1), cut_bin (B,) int32: the first bin
+        at which the exclusive prefix sum of e reaches threshold * (the sum of e[:1024])), both on the device.  A clip's numbers do not
+        depend on the batch it is in nor on what the row holds past its end; an all-zero clip gives zeros and bin 0."""
+        wav = _dev_f32(wav, self.device)
+        if wav.dim() not in (1, 2):
+            raise ValueError("band_energy: wav must be (B, L) or (L,), got %s" % (tuple(wav.shape),))
+        wav, _, B, L, lengths = _clip_rows(wav, lengths, "band_energy")
+        energy = torch.empty((B, _lib.BAND_BINS), device=self.device, dtype=torch.float64)
+        cut_bin = torch.empty((B,), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.vfx_band_energy(self.h, _ptr(wav), B, L, (ctypes.c_int * max(B, 1))(*lengths), int(hop), float(threshold),
+                                            _ptr(energy), _ptr(cut_bin), self._stream()), "vfx_band_energy")
+        return energy, cut_bin
+
+    def band_cutoff(self, wav, lengths=None, sample_rate=44100, hop=512, threshold=0.95):
+        """load_wav_energy's cut-off of every clip of a padded batch, in Hz: int((sample_rate // 2) * (cut_bin / 1025)), the reference's
+        expression (tools/utils.py:44), evaluated on the host from Engine.band_energy's bins after ONE device-to-host copy."""
+        wav = _dev_f32(wav, self.device)
+        if wav.dim() not in (1, 2):
+            raise ValueError("band_cutoff: wav must be (B, L) or (L,), got %s" % (tuple(wav.shape),))
+        wav, _, B, L, lengths = _clip_rows(wav, lengths, "band_cutoff")
+        cut_bin = torch.empty((B,), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.vfx_band_energy(self.h, _ptr(wav), B, L, (ctypes.c_int * max(B, 1))(*lengths), int(hop), float(threshold),
+                                            None, _ptr(cut_bin), self._stream()), "vfx_band_energy")
+        return [int((int(sample_rate) // 2) * (i / _lib.BAND_BINS)) for i in cut_bin.cpu().tolist()]
+
     def spectral_metrics(self, est, target):
         """Per-clip (LSD, SiSpec dB) of est vs target, (B, T, F) or (B, 1, T, F) each -> (B, 2)."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)

@@ -350,6 +350,26 @@ def _load_target(path, model, device):
         reader.close()
 
 
+def load_wav_energy(path, sample_rate, threshold=0.95, engine=None):
+    """tools/utils.py:33-44 (and eval_ssr_unet.py:25-36): -> (wav, cutoff), the file as mono float32 at `sample_rate` -- the values of
+    load_wav(path, sample_rate), a NumPy array -- and the frequency in Hz below which `threshold` of its log-spectral energy lies, what
+    eval_ssr_unet.py:105-106 hands to lowpass(wav, highcut=cutoff, fs=44100, order=5, _type="stft").  The file is read through
+    _WavReader (resampled on the device when its rate is another and DEVICE_RESAMPLE is set) and the detector runs on the device
+    (Engine.band_cutoff); `engine` defaults to simulate's module-level one.  A file of at most 1024 samples takes
+    simulate.band_cutoff on the host."""
+    from . import simulate
+    eng = engine if engine is not None else simulate._get_engine()
+    reader = _WavReader(path, sample_rate, engine=eng if DEVICE_RESAMPLE else None)
+    try:
+        x = reader.read_device(len(reader), eng.device)
+    finally:
+        reader.close()
+    wav = x.cpu().numpy()
+    if x.shape[0] <= simulate.BAND_NFFT // 2:
+        return wav, simulate.band_cutoff(wav, sample_rate, threshold)
+    return wav, eng.band_cutoff(x, sample_rate=sample_rate, hop=simulate.BAND_HOP, threshold=threshold)[0]
+
+
 class _WavWriter:
     """`save_wave` for a file that is produced segment by segment on the device: the PCM16 conversion of tools/file/wav.py
     ((x.astype(float64) * 2**15).astype(np.short), incl. its wrap of exactly +1.0) runs on the device, the 2-byte samples

@@ -392,6 +392,26 @@ def _validate_list(engine, call, wavs, targets, max_batch, bucket_key, bucket_le
     return losses, math.fsum(losses) / len(losses)
 
 
+def _restore_prefiltered_list(model, wavs, threshold, kwargs):
+    """The list layer under the two restore_prefiltered_list methods: detect each clip's bandwidth (simulate.band_cutoff_list), low-pass
+    it there (simulate.lowpass_each(..., 44100, 5, "stft"): eval_ssr_unet.py:105-106), restore (the model's own restore_list).  The clips
+    are device tensors from the first step on; what comes to the host is the cut-offs, one copy per detector batch.  A clip whose
+    cut-off is 0 Hz -- silence -- goes in unfiltered: int(ratio * 44100) = 0 is no rate to resample to."""
+    from . import simulate
+    eng = model.engine
+    sample_rate = kwargs.pop("sample_rate", 44100)
+    wavs = _resample_list(eng, list(wavs), sample_rate)      # the detector and the filter are defined at 44.1 kHz
+    wavs = [clips.as_tensor(w).reshape(-1).to(device=eng.device, dtype=torch.float32) for w in wavs]
+    cutoffs = simulate.band_cutoff_list(wavs, eng.cfg.sample_rate, threshold, engine=eng)
+    keep = [i for i, c in enumerate(cutoffs) if c > 0]
+    if keep:
+        low = simulate.lowpass_each([wavs[i] for i in keep], [cutoffs[i] for i in keep], eng.cfg.sample_rate, 5, "stft", engine=eng,
+                                    to_host=False)
+        for i, y in zip(keep, low):
+            wavs[i] = y
+    return model.restore_list(wavs, **kwargs), cutoffs
+
+
 def _wave_batch(batch, key, name):
     """batch[key] of the reference's validation loader, (B, L, 1) or (B, L) -> (B, L)."""
     x = batch[key]
@@ -588,6 +608,13 @@ class VoiceFixer(_Base):
         fn = vdist.checked_restore(self.engine, unify_energy=unify_energy)
         return vdist.restore_sharded_lengths(fn, wavs, self.device, max_batch=max_batch)
 
+    def restore_prefiltered_list(self, wavs, threshold=0.95, **kwargs):
+        """restore_list behind the reference's "remove the empty upper band first" step (eval_ssr_unet.py:105-106, tools/utils.py:33-44):
+        every clip's cut-off = the frequency below which `threshold` of its log-spectral energy lies, detected on the device
+        (Engine.band_energy), the clip low-passed there by lowpass(clip, cutoff, 44100, 5, "stft"), then restore_list, which takes
+        `kwargs` (a `sample_rate` other than 44.1 kHz is resampled first).  -> (restored clips, [cut-off in Hz per clip]) in input order.
+        A silent clip (cut-off 0) is restored unfiltered."""
+        return _restore_prefiltered_list(self, wavs, threshold, kwargs)
 
     def restore_scored_list(self, wavs, targets, unify_energy=False, max_batch=128):
         """restore_list for a test set WITH targets (every reference test list is `source target` pairs): lists of 1-D clips at
@@ -668,6 +695,10 @@ class SSR_UNet(_Base):
         fn.bucket_len = lambda L: eng.padded_frames(L) * eng.hop - 1      # one plan per (B, bucket), cf. dist.checked_restore
         return vdist.restore_sharded_lengths(fn, wavs, self.device, max_batch=max_batch)
 
+    def restore_prefiltered_list(self, wavs, threshold=0.95, **kwargs):
+        """restore_list with each clip low-passed at its own detected bandwidth first, the two lines eval_ssr_unet.py:105-106 keeps in
+        front of the model: -> (restored clips, [cut-off in Hz per clip]) in input order (cf. VoiceFixer.restore_prefiltered_list)."""
+        return _restore_prefiltered_list(self, wavs, threshold, kwargs)
 
     def restore_scored_list(self, wavs, targets, max_batch=16):
         """restore_list for a test set with targets: -> (restored clips, [{"mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"}

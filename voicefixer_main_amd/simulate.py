@@ -11,7 +11,9 @@ same names, argument meaning and error behaviour:
   (``_type in "butter"`` is a SUBSTRING test in the reference -- ``"b"``, ``"utt"`` and ``""`` all select the Butterworth
   filter; kept, since a config that relied on it must keep working);
 * ``bandpass(data, lowcut, highcut, fs, order=5, _type="butter")``     tools/dsp/lowpass.py:189-215 (IIR types, same dispatch)
-* ``bandpass_filter`` / ``align_length`` / ``limit``                       tools/dsp/lowpass.py:35-94,148-150
+* ``band_cutoff(clip, fs, threshold)``: the bandwidth detector ``load_wav_energy`` of tools/utils.py:33-44 without the file read,
+  in NumPy; ``band_cutoff_list`` is its batch form on the device (Engine.band_cutoff, csrc/band.hip);
+* ``bandpass_filter`` / ``align_length`` / ``limit``                     tools/dsp/lowpass.py:35-94,148-150
 * ``add_noise_and_scale`` / ``add_noise_and_scale_with_HQ`` / ``add_noise_and_scale_with_HQ_with_Aug``
                                                                            dataloaders/augmentation/base.py:33-118
   with their helpers ``normalize_energy`` / ``unify_energy`` (peak based: tools/others/audio_op.py:12-56); their ``..._list``
@@ -414,6 +416,62 @@ def bandpass_each(clips, lowcuts, highcuts, fs, orders=5, types="butter", engine
     cuts = list(zip(_per_clip(lowcuts, n, "bandpass_each: lowcuts"), _per_clip(highcuts, n, "bandpass_each: highcuts")))
     return _filter_each(clips, cuts, fs, _per_clip(orders, n, "bandpass_each: orders"), _per_clip(types, n, "bandpass_each: types"),
                         engine, to_host)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the bandwidth detector in front of the restoration handlers (tools/utils.py:33-44 load_wav_energy; eval_ssr_unet.py:105-106 pairs it
+# with lowpass(..., _type="stft")): the frequency below which `threshold` of a clip's log-spectral energy lies
+# ------------------------------------------------------------------------------------------------------------------
+BAND_NFFT, BAND_HOP, BAND_BINS = 2048, 512, 1025     # librosa.stft's defaults
+
+
+def band_cutoff_hz(cut_bin, fs):
+    """The reference's last expression (utils.py:44): bin -> Hz."""
+    return int((int(fs) // 2) * (cut_bin / BAND_BINS))
+
+
+def band_cutoff(clip, fs=44100, threshold=0.95):
+    """load_wav_energy's cut-off in Hz of ONE clip (samples,), on the host in NumPy with the reference's number formats: librosa.stft's
+    defaults (n_fft 2048, hop 512, periodic Hann, centred, reflect padding; the transform in float64, stored as complex64), float32
+    magnitudes, logarithms and sums.  e[k] = sum_t log10(|S[k, t]| + 1); P[k] = sum(e[:k]), the exclusive prefix the loop of
+    utils.py:38-39 leaves (it runs from the top down, so every sum sees original values); total = P[1024]; the cut-off bin is the
+    first k that does not have P[k] < total * threshold."""
+    x = np.asarray(_clips.as_numpy(clip), dtype=np.float32).reshape(-1)
+    xp = np.pad(x, BAND_NFFT // 2, mode="reflect")
+    idx = np.arange(x.shape[0] // BAND_HOP + 1)[:, None] * BAND_HOP + np.arange(BAND_NFFT)[None, :]
+    window = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(BAND_NFFT) / BAND_NFFT)
+    spec = np.fft.rfft(xp[idx] * window, axis=-1).astype(np.complex64).T          # (1025, T)
+    e = np.sum(np.log10(np.abs(spec) + 1.0), axis=1)
+    prefix = np.array([np.sum(e[:k]) for k in range(e.shape[0])], dtype=e.dtype)
+    level = prefix[-1] * threshold
+    cut_bin = e.shape[0] - 1
+    for k in range(e.shape[0]):
+        if not prefix[k] < level:
+            cut_bin = k
+            break
+    return band_cutoff_hz(cut_bin, fs)
+
+
+def band_cutoff_list(clips, fs=44100, threshold=0.95, engine=None):
+    """`band_cutoff` for a list of 1-D clips of any lengths (NumPy arrays or tensors, on any device) -> [Hz per clip] in the caller's
+    order.  Clips of more than 1024 samples go through Engine.band_cutoff as float32 padded batches, sorted by length, up to MAX_BATCH
+    per call, ONE device-to-host copy per batch; a clip's cut-off does not depend on its batch.  The device sums in float64 where the
+    host form sums in float32: the two agree wherever the decision is not within rounding of a bin's edge.  Shorter clips take the
+    host form."""
+    clips = list(clips)
+    _check_1d(clips)
+    eng = _engine_or_default(engine)
+    lengths = [c.shape[0] for c in clips]
+    out = [None] * len(clips)
+    for idx in _clips.batches([i for i in range(len(clips)) if lengths[i] > BAND_NFFT // 2], lengths, MAX_BATCH):
+        lens = [lengths[i] for i in idx]
+        x = _clips.pad([clips[i] for i in idx], eng.device, torch.float32)
+        for i, hz in zip(idx, eng.band_cutoff(x, lengths=lens, sample_rate=fs, hop=BAND_HOP, threshold=threshold)):
+            out[i] = hz
+    for i in range(len(clips)):
+        if out[i] is None:
+            out[i] = band_cutoff(clips[i], fs, threshold)
+    return out
 
 
 def draw_lowpass_params(n, low_pass_range, filter_order_range, filter_type, rng):
