@@ -540,6 +540,51 @@ int vfx_effect_chain(vfx_handle* h, const float* x, int B, int64_t ldx, const in
                      float* y, int64_t ldy, void* stream);
 
 /*
+ * The peak-threshold silence functions of the reference's data preparation (tools/others/audio_op.py:79-150) for a padded batch of
+ * clips: x (B, ldx) device, float32 (x_f64 = 0) or float64 (1), clip b = the first n_b = lengths[b] samples of row b; lengths is a HOST
+ * array.  Everything is decided by window peaks max |x[i]| over windows of one clip, compared with `threshold` IN THE CLIP'S DTYPE: the
+ * threshold is rounded to float32 first for float32 clips, as NumPy >= 2 compares a Python scalar with a float32 array.  A NaN sample
+ * makes its windows' peaks NaN, which is neither < nor > the threshold, as the reference's comparisons come out.
+ *
+ * vfx_trim_bounds: trim_tail_empty (`which` = VFX_TRIM_TAIL), trim_head_empty (VFX_TRIM_HEAD) or trim_empty (VFX_TRIM_BOTH) as the
+ * sample range [start[b], stop[b]) the function keeps of clip b, or start = stop = -1 where it returns None.  seg = int(sample_rate *
+ * frame_length).
+ *   tail  n < seg -> None.  The windows lie on the grid that ENDS at n (origin n % seg, stride = width = seg); from the last one, while
+ *         the window's end L > seg and its peak < threshold, L -= seg.  L < seg -> None; L == n -> [0, n); else [0, L - seg): the
+ *         reference drops one further segment, and L == seg leaves the EMPTY clip [0, 0), which is not None.
+ *   head  on a clip of m samples: windows [k seg, (k + 1) seg) from 0; s = 0, and while s < m - seg and the peak < threshold, s += seg.
+ *         s >= m - seg -> None (every m <= seg among them); s == 0 -> [0, m); else [s - seg, m): one quiet segment stays.
+ *   both  tail, then head on the tail's result (m = its stop); None if either is.
+ * Lengths 0 <= n_b <= ldx; a clip of length 0 gives None.
+ *
+ * vfx_long_empty: has_long_empty.  flag[b] = 1 if any window [L - seg, L), L = n, n - step, n - 2 step, ... while L > seg, has a peak
+ * < threshold, else 0 (the reference: seg = int(sample_rate * 3), step = sample_rate, threshold 400).  Lengths 0 <= n_b <= ldx.
+ *
+ * vfx_active_frames: get_all_active_segment_index.  The clip is reflect-padded by `shift` samples on both sides (np.pad(...,
+ * mode="reflect"): the edge sample is not repeated); frames of `frame` samples every `shift` start at padded index 0 while a frame fits
+ * into n + 2 shift samples: vfx_active_frames_count frames (host arithmetic; -1 for arguments out of range).  labels[b][k] = 1 where
+ * frame k's peak > threshold (strictly: is_valid_signal), else 0; the rest of the row, up to ldf, is 0.  counts (may be NULL): the frame
+ * count of each clip.  Lengths shift < n_b <= ldx (one reflection), ldf >= every clip's frame count.
+ *
+ * One wave takes one window (a 20-ms window is 3.5 kB); a second kernel decides a clip from its peaks by index.  A clip's results do
+ * not depend on the batch it is in, on ldx, on the rows' alignment or on what lies at or past its end, which is never read.  More than
+ * 128 clips run as consecutive sub-batches.  The peaks live in the handle's grow-only varlen scratch: while a hipGraph captured from a
+ * plan is alive, a call that would have to grow it fails with a message that says so.
+ * Each call fails, naming the clip where there is one and launching nothing, for a NULL pointer (counts excepted), B outside 1..1024,
+ * a length out of range, seg, step, frame or shift <= 0, an unknown `which`, or a threshold that is not finite.
+ */
+enum { VFX_TRIM_TAIL = 0, VFX_TRIM_HEAD = 1, VFX_TRIM_BOTH = 2 };
+int vfx_trim_bounds(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths /* HOST */, int64_t seg,
+                    double threshold, int which, int64_t* start /* (B) device */, int64_t* stop /* (B) device, -1 / -1 = None */,
+                    void* stream);
+int vfx_long_empty(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths /* HOST */, int64_t seg,
+                   int64_t step, double threshold, int* flag /* (B) device */, void* stream);
+int vfx_active_frames(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths /* HOST */, int64_t frame,
+                      int64_t shift, double threshold, uint8_t* labels /* (B, ldf) device */, int64_t ldf,
+                      int64_t* counts /* (B) device, may be NULL */, void* stream);
+int64_t vfx_active_frames_count(int64_t n, int64_t frame, int64_t shift);
+
+/*
  * Spectral metrics of the evaluation handlers, per clip, without leaving the device
  * (evaluation_proc/metrics.py:83-95 `lsd`, `sispec`; evaluation_proc/utils.py:81-101 `energy_unify`,
  * `pow_p_norm`; used at eval_gsr_voicefixer.py:56-64):  est, target (B, T, F) -> out (B, 2),

@@ -26,6 +26,7 @@ N_AUDIO_METRICS = 9       # VFX_N_AUDIO_METRICS: the columns of vfx_audio_metric
 N_HANDLER_METRICS = 4     # VFX_N_HANDLER_METRICS: the columns of vfx_restore_*_varlen_scored
 BSSEVAL_SLAB = 8192       # VFX_BSSEVAL_SLAB: samples per partial sum of vfx_bsseval
 STREAM_OLA, STREAM_BOXCAR = 0, 1   # the modes of vfx_stream_create
+TRIM_TAIL, TRIM_HEAD, TRIM_BOTH = 0, 1, 2   # VFX_TRIM_*: the `which` of vfx_trim_bounds
 BAND_BINS = 1025          # VFX_BAND_BINS: the columns of vfx_band_energy's energy
 N_SPEC_LOSSES = 3         # VFX_N_SPEC_LOSSES: the columns of vfx_spec_losses (l1_wav, l1_sp, l1_log_sp)
 
@@ -58,6 +59,13 @@ SIGNATURES = {
     "vfx_istft": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_stft_lowpass": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
     "vfx_band_energy": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+    "vfx_trim_bounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_int64, ctypes.c_double, c_int, c_void_p,
+                        c_void_p, c_void_p]),
+    "vfx_long_empty": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_int64, c_int64, ctypes.c_double, c_void_p,
+                       c_void_p]),
+    "vfx_active_frames": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_int64, c_int64, ctypes.c_double,
+                          c_void_p, c_int64, c_void_p, c_void_p]),
+    "vfx_active_frames_count": (c_int64, [c_int64, c_int64, c_int64]),
     "vfx_resample_out_len": (c_int64, [c_int64, c_int, c_int]),
     "vfx_resample_window": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "vfx_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_int,

@@ -824,6 +824,78 @@ int vfx_effect_chain(vfx_handle* h, const float* x, int B, int64_t ldx, const in
   VFX_API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// silence and activity (tools/others/audio_op.py:79-150 on the device: activity.hip)
+// ---------------------------------------------------------------------------------------------
+// What the three entry points share once their own arguments are checked: the lengths, the threshold in the clips' dtype, the peaks'
+// scratch, the launches.
+static void run_activity(vfx_handle* h, const char* who, int mode, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths,
+                         int64_t W, int64_t S, double threshold, int64_t* start, int64_t* stop, int* flag, uint8_t* labels, int64_t ldf,
+                         int64_t* counts, void* stream) {
+  VFX_CHECK(x_f64 == 0 || x_f64 == 1, "%s: x_f64 = %d (need 0 or 1)", who, x_f64);
+  VFX_CHECK(B >= 1 && B <= kMaxVarlenClips, "%s: %d clips (need 1 <= B <= %d)", who, B, kMaxVarlenClips);
+  VFX_CHECK(std::isfinite(threshold), "%s: threshold = %g (need a finite number)", who, threshold);
+  if (mode == ACT_FRAMES)
+    check_clip_lengths(who, B, lengths, S + 1, "the reflect padding", ldx, nullptr, 0x7fffffff - 2 * kClipChunk);
+  else
+    check_clip_lengths(who, B, lengths, 0, nullptr, ldx, nullptr, 0x7fffffff - 2 * kClipChunk);
+  int64_t ldp = 1;
+  for (int b = 0; b < B; ++b) {
+    const int64_t c = activity_windows(mode, lengths[b], W, S);
+    if (mode == ACT_FRAMES) VFX_CHECK(c <= ldf, "%s: clip %d has %lld frames, the label rows hold %lld", who, b, (long long)c, (long long)ldf);
+    ldp = std::max(ldp, c);
+  }
+  const size_t esz = x_f64 ? sizeof(double) : sizeof(float);
+  void* const ws = h->scratch.ensure(
+      h, (size_t)(mode == ACT_BOTH ? 2 : 1) * std::min(B, kActMaxClips) * ldp * esz, 8,
+      "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured from plan '%s': run the largest silence / "
+      "activity batch once BEFORE capturing");
+  // a Python scalar against a float32 array is compared in float32 (NumPy >= 2): the threshold is rounded once, here
+  const double thr = x_f64 ? threshold : (double)(float)threshold;
+  launch_activity(mode, x, x_f64, B, ldx, lengths, W, S, thr, ws, ldp, start, stop, flag, labels, ldf, counts,
+                  static_cast<hipStream_t>(stream));
+}
+
+int vfx_trim_bounds(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, int64_t seg, double threshold,
+                    int which, int64_t* start, int64_t* stop, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && start && stop, "vfx_trim_bounds: NULL argument");
+  VFX_CHECK(seg > 0, "vfx_trim_bounds: seg = %lld (need seg > 0)", (long long)seg);
+  VFX_CHECK(which == VFX_TRIM_TAIL || which == VFX_TRIM_HEAD || which == VFX_TRIM_BOTH, "vfx_trim_bounds: which = %d (need VFX_TRIM_TAIL, "
+            "VFX_TRIM_HEAD or VFX_TRIM_BOTH)", which);
+  static_assert(VFX_TRIM_TAIL == ACT_TAIL && VFX_TRIM_HEAD == ACT_HEAD && VFX_TRIM_BOTH == ACT_BOTH, "the public names of the modes");
+  run_activity(h, "vfx_trim_bounds", which, x, x_f64, B, ldx, lengths, seg, seg, threshold, start, stop, nullptr, nullptr, 0, nullptr,
+               stream);
+  VFX_API_END
+}
+
+int vfx_long_empty(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, int64_t seg, int64_t step,
+                   double threshold, int* flag, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && flag, "vfx_long_empty: NULL argument");
+  VFX_CHECK(seg > 0 && step > 0, "vfx_long_empty: seg = %lld, step = %lld (need both > 0)", (long long)seg, (long long)step);
+  run_activity(h, "vfx_long_empty", ACT_LONG, x, x_f64, B, ldx, lengths, seg, step, threshold, nullptr, nullptr, flag, nullptr, 0,
+               nullptr, stream);
+  VFX_API_END
+}
+
+int64_t vfx_active_frames_count(int64_t n, int64_t frame, int64_t shift) {
+  if (n < 0 || frame <= 0 || shift <= 0 || n > 0x7fffffff || shift > 0x7fffffff) return -1;
+  return activity_windows(ACT_FRAMES, n, frame, shift);
+}
+
+int vfx_active_frames(vfx_handle* h, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, int64_t frame, int64_t shift,
+                      double threshold, uint8_t* labels, int64_t ldf, int64_t* counts, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && lengths && labels, "vfx_active_frames: NULL argument");
+  VFX_CHECK(frame > 0 && shift > 0 && shift <= 0x7fffffff, "vfx_active_frames: frame = %lld, shift = %lld (need both > 0)",
+            (long long)frame, (long long)shift);
+  VFX_CHECK(ldf >= 1, "vfx_active_frames: ldf = %lld (need ldf >= 1)", (long long)ldf);
+  run_activity(h, "vfx_active_frames", ACT_FRAMES, x, x_f64, B, ldx, lengths, frame, shift, threshold, nullptr, nullptr, nullptr, labels,
+               ldf, counts, stream);
+  VFX_API_END
+}
+
 int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int L, float* wav, void* stream) {
   VFX_API_BEGIN_HS(h, stream)
   VFX_CHECK(re && im && wav && B > 0 && T > 0 && L > 0, "bad argument");

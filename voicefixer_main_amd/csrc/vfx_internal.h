@@ -567,6 +567,32 @@ inline int band_groups(int len, int hop) { return (len / hop + 1 + kBandFrames -
 void launch_band_energy(const FrontEndTables& t, const float* wav, int nb, int64_t ld, const int* len, int hop, double threshold,
                         int groups, double* ws, double* energy, int* cut_bin, hipStream_t s);
 
+// activity.hip: the peak-threshold silence functions (vfx_trim_bounds, vfx_long_empty, vfx_active_frames).  A mode names the window
+// grid of a clip of n samples -- windows of W samples every S, the first at activity_origin, activity_windows of them:
+//   ACT_TAIL, ACT_BOTH  the grid that ends at n: origin n % W, stride W (ACT_BOTH adds the grid from 0 behind it)
+//   ACT_HEAD            the grid from 0, stride W; only whole windows
+//   ACT_LONG            [L - W, L) for L = n, n - S, ... while L > W, in ascending order of position
+//   ACT_FRAMES          the frames of the clip reflect-padded by S on both sides, from padded index 0 while a frame fits
+enum { ACT_TAIL = 0, ACT_HEAD = 1, ACT_BOTH = 2, ACT_LONG = 3, ACT_FRAMES = 4 };  // the first three are VFX_TRIM_*
+constexpr int kActMaxClips = 128;  // clips per launch set (clip_batch.h)
+inline int64_t activity_windows(int mode, int64_t n, int64_t W, int64_t S) {
+  if (mode == ACT_LONG) return n > W ? (n - W - 1) / S + 1 : 0;
+  if (mode == ACT_FRAMES) return n + 2 * S >= W ? (n + 2 * S - W) / S + 1 : 0;
+  return n / W;
+}
+inline int64_t activity_origin(int mode, int64_t n, int64_t W, int64_t S) {
+  if (mode == ACT_LONG) return n > W ? n - W - (activity_windows(mode, n, W, S) - 1) * S : 0;
+  if (mode == ACT_FRAMES) return -S;
+  return mode == ACT_HEAD ? 0 : n % W;
+}
+// x (B, ldx) float32 or float64, clip b = its first lengths[b] samples (HOST; the caller has checked them with check_clip_lengths, and
+// lengths[b] > S for ACT_FRAMES) -> the outputs of the mode: start, stop (B) for the trims (-1 / -1 = None), flag (B) for ACT_LONG,
+// labels (B, ldf) and counts (B, or NULL) for ACT_FRAMES, everything device.  threshold: already rounded to x's dtype.  ws: (2 for
+// ACT_BOTH, else 1) * min(B, kActMaxClips) * ldp elements of x's size, ldp >= activity_windows of every clip.
+void launch_activity(int mode, const void* x, int x_f64, int B, int64_t ldx, const int64_t* lengths, int64_t W, int64_t S,
+                     double threshold, void* ws, int64_t ldp, int64_t* start, int64_t* stop, int* flag, uint8_t* labels, int64_t ldf,
+                     int64_t* counts, hipStream_t s);
+
 // stft_dft.hip: the front end of the scores at 16 kHz (vfx_audio_metrics_rate): |STFT| with n_fft 743, hop 160 as a DFT-matrix GEMM on
 // the f32-input MFMA, and the 80-band mel image.  An odd n_fft pads 371 samples on each side: 1 + (len - 1) / 160 frames.
 constexpr int kDftN = 743, kDftHop = 160, kDftBins = kDftN / 2 + 1, kDftMels = 80, kDftRate = 16000;

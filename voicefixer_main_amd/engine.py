@@ -312,6 +312,55 @@ class Engine:
                                             None, _ptr(cut_bin), self._stream()), "vfx_band_energy")
         return [int((int(sample_rate) // 2) * (i / _lib.BAND_BINS)) for i in cut_bin.cpu().tolist()]
 
+    # ------------------------------------------------------------------ silence and activity (tools/others/audio_op.py:79-150)
+    def _activity_rows(self, x, lengths, name):
+        x, squeeze, B, L, lengths = _clip_rows(_float_rows(x, self.device, name, ValueError), lengths, name)
+        if B == 0:
+            raise ValueError("%s: no clips" % name)
+        return x, B, L, (ctypes.c_int64 * B)(*lengths)
+
+    def trim_bounds(self, x, lengths=None, threshold=500, sample_rate=44100, frame_length=0.02, which="both"):
+        """trim_tail_empty (which="tail"), trim_head_empty ("head") or trim_empty ("both") of every clip of a padded batch as sample
+        ranges (vfx_trim_bounds): x (B, L) or (L,), float32 or float64, clip b = the first lengths[b] samples (default L; 0 is
+        allowed) of row b -> (start, stop), two (B,) int64 device tensors: the function keeps clip[start:stop], and start = stop = -1
+        where it returns None.  The threshold is compared in x's dtype; a clip's bounds do not depend on the batch nor on what the row
+        holds past its end.  activity.trim_empty is the host form."""
+        x, B, L, lens = self._activity_rows(x, lengths, "trim_bounds")
+        mode = {"tail": _lib.TRIM_TAIL, "head": _lib.TRIM_HEAD, "both": _lib.TRIM_BOTH}.get(which)
+        if mode is None:
+            raise ValueError("trim_bounds: which must be 'tail', 'head' or 'both', got %r" % (which,))
+        start = torch.empty((B,), device=self.device, dtype=torch.int64)
+        stop = torch.empty((B,), device=self.device, dtype=torch.int64)
+        _lib.check(self.lib.vfx_trim_bounds(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, lens, int(sample_rate * frame_length),
+                                            float(threshold), mode, _ptr(start), _ptr(stop), self._stream()), "vfx_trim_bounds")
+        return start, stop
+
+    def has_long_empty(self, x, lengths=None, length=3, sample_rate=44100, threshold=400):
+        """has_long_empty of every clip of a padded batch (vfx_long_empty): x and lengths as in `trim_bounds` -> (B,) int32 device
+        tensor, 1 where a window of int(sample_rate * length) samples that ends at n, n - sample_rate, ... has a peak < threshold."""
+        x, B, L, lens = self._activity_rows(x, lengths, "has_long_empty")
+        flag = torch.empty((B,), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.vfx_long_empty(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, lens, int(sample_rate * length),
+                                           int(sample_rate), float(threshold), _ptr(flag), self._stream()), "vfx_long_empty")
+        return flag
+
+    def active_frames_count(self, n, sample_rate=44100, frame_length=0.02, frame_shift=0.01):
+        """The number of labels get_all_active_segment_index gives a clip of n samples (vfx_active_frames_count)."""
+        return int(self.lib.vfx_active_frames_count(int(n), int(frame_length * sample_rate), int(frame_shift * sample_rate)))
+
+    def active_frames(self, x, lengths=None, threshold=500, sample_rate=44100, frame_length=0.02, frame_shift=0.01):
+        """get_all_active_segment_index of every clip of a padded batch (vfx_active_frames): x and lengths as in `trim_bounds`, every
+        clip longer than int(frame_shift * sample_rate) samples -> (labels (B, F) uint8, counts (B,) int64), both on the device:
+        labels[b, :counts[b]] are the clip's labels, 1 where the frame's peak > threshold; the rest of the row is 0."""
+        x, B, L, lens = self._activity_rows(x, lengths, "active_frames")
+        frame, shift = int(frame_length * sample_rate), int(frame_shift * sample_rate)
+        ldf = max(1, max(int(self.lib.vfx_active_frames_count(int(n), frame, shift)) for n in lens))
+        labels = torch.empty((B, ldf), device=self.device, dtype=torch.uint8)
+        counts = torch.empty((B,), device=self.device, dtype=torch.int64)
+        _lib.check(self.lib.vfx_active_frames(self.h, _ptr(x), int(x.dtype == torch.float64), B, L, lens, frame, shift, float(threshold),
+                                              _ptr(labels), ldf, _ptr(counts), self._stream()), "vfx_active_frames")
+        return labels, counts
+
     def spectral_metrics(self, est, target):
         """Per-clip (LSD, SiSpec dB) of est vs target, (B, T, F) or (B, 1, T, F) each -> (B, 2)."""
         est, target = _dev_f32(est, self.device), _dev_f32(target, self.device)

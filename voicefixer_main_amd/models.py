@@ -412,6 +412,42 @@ def _restore_prefiltered_list(model, wavs, threshold, kwargs):
     return model.restore_list(wavs, **kwargs), cutoffs
 
 
+MIN_RESTORE_SAMPLES = 1025     # more than n_fft / 2 samples: the shortest clip restore_list takes (the STFT's reflect padding)
+
+
+def trimmed_span(bounds, n, least=MIN_RESTORE_SAMPLES):
+    """The span of a clip of n samples that restore_trimmed_list restores, from what trim_empty keeps of it, (start, stop): a span of
+    fewer than `least` samples is widened to `least`, first to the right, then to the left, within the clip; a clip that is itself
+    shorter goes in whole."""
+    start, stop = bounds
+    if n < least:
+        return 0, n
+    if stop - start < least:
+        stop = min(n, start + least)
+        start = max(0, stop - least)
+    return start, stop
+
+
+def _restore_trimmed_list(model, wavs, threshold, frame_length, kwargs):
+    """The list layer under the two restore_trimmed_list methods: find what trim_empty keeps of every clip on the device
+    (activity.trim_empty_bounds_list: the bounds come to the host, one copy per batch; the samples stay), restore those spans in ONE
+    restore_list call, write each into zeros of its clip's length.  A clip trim_empty returns None for never reaches the network."""
+    from . import activity
+    eng = model.engine
+    sample_rate = kwargs.pop("sample_rate", 44100)
+    wavs = _resample_list(eng, list(wavs), sample_rate)      # the segment length is defined at 44.1 kHz
+    wavs = [clips.as_tensor(w).reshape(-1).to(device=eng.device, dtype=torch.float32) for w in wavs]
+    found = activity.trim_empty_bounds_list(wavs, threshold, eng.cfg.sample_rate, frame_length, engine=eng)
+    bounds = [None if b is None else trimmed_span(b, int(w.shape[0])) for b, w in zip(found, wavs)]
+    outs = [torch.zeros_like(w) for w in wavs]
+    keep = [i for i, b in enumerate(bounds) if b is not None]
+    if keep:
+        restored = model.restore_list([wavs[i][bounds[i][0]:bounds[i][1]] for i in keep], **kwargs)
+        for i, y in zip(keep, restored or []):       # (None on the ranks of a distributed restore_list that do not hold the result)
+            outs[i][bounds[i][0]:bounds[i][1]] = y
+    return outs, bounds
+
+
 def _wave_batch(batch, key, name):
     """batch[key] of the reference's validation loader, (B, L, 1) or (B, L) -> (B, L)."""
     x = batch[key]
@@ -616,6 +652,16 @@ class VoiceFixer(_Base):
         A silent clip (cut-off 0) is restored unfiltered."""
         return _restore_prefiltered_list(self, wavs, threshold, kwargs)
 
+    def restore_trimmed_list(self, wavs, threshold=500 / 2 ** 15, frame_length=0.02, **kwargs):
+        """restore_list of the ACTIVE span of every clip: leading and trailing silence, as the reference's trim_empty finds it
+        (tools/others/audio_op.py:107-109: window peaks below `threshold` in segments of `frame_length` seconds; 500 / 2**15 is its
+        default of 500 on the float scale), costs no network time.  The bounds are found on the device (Engine.trim_bounds), a span
+        shorter than restore_list's minimum is widened (trimmed_span), the spans go through ONE restore_list call, which takes
+        `kwargs`.  -> (outs, bounds) in input order: outs[i] has the length of clip i (at 44.1 kHz), zeros outside
+        bounds[i] = (start, stop), the restored span inside -- bit for bit restore_list of that span; bounds[i] is None and outs[i]
+        all zeros for a clip trim_empty returns None for (silence, or activity only in the segments its rules drop)."""
+        return _restore_trimmed_list(self, wavs, threshold, frame_length, kwargs)
+
     def restore_scored_list(self, wavs, targets, unify_energy=False, max_batch=128):
         """restore_list for a test set WITH targets (every reference test list is `source target` pairs): lists of 1-D clips at
         44.1 kHz -> (restored clips, [{"mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"} per clip]) in input order -- the
@@ -699,6 +745,11 @@ class SSR_UNet(_Base):
         """restore_list with each clip low-passed at its own detected bandwidth first, the two lines eval_ssr_unet.py:105-106 keeps in
         front of the model: -> (restored clips, [cut-off in Hz per clip]) in input order (cf. VoiceFixer.restore_prefiltered_list)."""
         return _restore_prefiltered_list(self, wavs, threshold, kwargs)
+
+    def restore_trimmed_list(self, wavs, threshold=500 / 2 ** 15, frame_length=0.02, **kwargs):
+        """restore_list of the active span of every clip, zeros around it: -> (outs, bounds) in input order (cf.
+        VoiceFixer.restore_trimmed_list)."""
+        return _restore_trimmed_list(self, wavs, threshold, frame_length, kwargs)
 
     def restore_scored_list(self, wavs, targets, max_batch=16):
         """restore_list for a test set with targets: -> (restored clips, [{"mel-lsd", "mel-sispec", "mel-non-log-sispec", "mel-ssim"}
