@@ -177,6 +177,44 @@ int vfx_istft(vfx_handle* h, const float* re, const float* im, int B, int T, int
 int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* lengths, const int* cut_bins, float* out, void* stream);
 
 /*
+ * The splice of a restored clip onto its band-limited input, for a padded batch of clip pairs at 44.1 kHz, in ONE launch with no spectrum
+ * in memory: below the cut-off bin the result is the input, above it the restored clip, with a linear ramp of `ramp` bins between.  Not in
+ * the reference (its level half is amp_to_original_f, tools/utils.py:50-55).  x (the input), y (the restored clip): (B, L) device, pair
+ * b = the first L_b = lengths[b] samples of row b of both; lengths, cut_bins: HOST arrays int[B], n_fft/2 < lengths[b] <= L, c =
+ * cut_bins[b] >= 0; w = ramp >= 0, one value per call; gains: HOST array float[B] of finite values, or NULL: every g = 1.  Per pair, in
+ * float32, every product and difference rounded on its own:
+ *   gy[n] = g * y[n];  d[n] = x[n] - gy[n];
+ *   a[k] = 1 for k <= c - w - 1, 0 for k >= c, float(c - k) / float(w + 1) between (w = 0: the hard mask of vfx_stft_lowpass);
+ *   D = vfx_stft_mel's (sp * cos, sp * sin) of d alone (eps = 1e-8), the bins with a = 0 set to +0, each product of a bin with
+ *       0 < a < 1 multiplied by a[k], the bins with a = 1 untouched;  r = vfx_istft of D to L_b samples;
+ *   out[n] = gy[n] + r[n] for n < L_b, zeros from L_b to L.
+ * By linearity this is ISTFT(a STFT(x) + (1 - a) STFT(g y)) with one forward transform per frame, and the band above the seam is g y
+ * itself.  Exactly: y == x with g = 1 gives x; y == 0 with w = 0 gives vfx_stft_lowpass(x); c = 0 gives g y.  out (B, L) device must
+ * overlap neither x nor y.  Row b is bit for bit the chain of launches above run on the pair alone; it does not depend on the batch, and
+ * nothing at or past L_b of either row is read.  More than 128 pairs run as consecutive sub-batches.
+ * Fails, naming the clip and launching nothing, for a NULL pointer (gains excepted), B <= 0, a length outside (n_fft/2, L], a negative
+ * cut or ramp, a gain that is not finite, or overlapping buffers.
+ */
+int vfx_stft_splice(vfx_handle* h, const float* x, const float* y, int B, int L, const int* lengths /* HOST */,
+                    const int* cut_bins /* HOST */, int ramp, const float* gains /* HOST, or NULL: 1 */, float* out, void* stream);
+
+/*
+ * The power of two clips in a band of STFT bins, per pair of a padded batch at 44.1 kHz -- what the level match of the splice compares.
+ * a, b: (B, Lmax) device, pair p = the first L_p = lengths[p] samples of row p of both; lengths: HOST array int[B] with n_fft/2 <
+ * lengths[p] <= Lmax, or NULL: every clip has Lmax samples; lo_bins, hi_bins: HOST arrays int[B], 0 <= lo <= hi <= 1025.
+ *   out[p][0] = sum_t sum_{k = lo}^{hi - 1} (double)|A[k, t]|^2,  out[p][1] = the same of b,  t < L_p / hop + 1,
+ * |.| = vfx_stft_mel's float32 magnitude of the clip alone (eps = 1e-8), squared and summed in float64: a lane sums its bins in ascending
+ * order, a wave by a fixed tree, the frames by index -- no float atomics, no spectrum in memory.  hi == lo gives zeros.  out: (B, 2)
+ * device doubles.  A pair's two numbers do not depend on the batch it is in, on Lmax, or on what lies at or past its end (never read).
+ * More than 128 pairs run as consecutive sub-batches.  The frame sums live in the handle's grow-only varlen scratch (see
+ * vfx_band_energy).
+ * Fails, naming the clip and launching nothing, for a NULL pointer (lengths excepted), B <= 0, a length outside (n_fft/2, Lmax],
+ * lo < 0, hi > 1025, hi < lo, or out overlapping a or b.
+ */
+int vfx_band_power(vfx_handle* h, const float* a, const float* b, int B, int Lmax, const int* lengths /* HOST, or NULL */,
+                   const int* lo_bins /* HOST */, const int* hi_bins /* HOST */, double* out /* (B, 2) device */, void* stream);
+
+/*
  * The bandwidth detector of load_wav_energy (tools/utils.py:33-44) for a padded batch of clips at 44.1 kHz: wav (B, Lmax) device
  * floats, clip b = the first L_b = lengths[b] samples of row b; lengths is a HOST array int[B] with n_fft/2 < lengths[b] <= Lmax, or
  * NULL: every clip has Lmax samples.  1 <= hop <= 2048 (librosa.stft's default is 512), 0 < threshold <= 1.  Per clip:

@@ -58,6 +58,10 @@ SIGNATURES = {
     "vfx_mel_project": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "vfx_istft": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vfx_stft_lowpass": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p]),
+    "vfx_stft_splice": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_float),
+                        c_void_p, c_void_p]),
+    "vfx_band_power": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p,
+                       c_void_p]),
     "vfx_band_energy": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
     "vfx_trim_bounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, POINTER(c_int64), c_int64, ctypes.c_double, c_int, c_void_p,
                         c_void_p, c_void_p]),

@@ -1,4 +1,5 @@
 // api.cpp -- error text, the stream turns and the extern "C" entry points of libvfx.so.
+#include <cmath>
 #include <cstring>
 #include <cstdlib>
 #include <numeric>
@@ -274,6 +275,90 @@ int vfx_stft_lowpass(vfx_handle* h, const float* wav, int B, int L, const int* l
     launch_set_frames(d_l, lengths + b0, n, s);
     launch_set_frames(d_c, cut_bins + b0, n, s);
     launch_stft_lowpass(h->fe, wav + (int64_t)b0 * L, n, L, h->cfg.hop, d_l, d_c, out + (int64_t)b0 * L, s);
+  }
+  VFX_API_END
+}
+
+// [p, p + bytes) and [q, q + bytes) share no byte (compared as integers)
+static bool ranges_disjoint(const void* p, const void* q, uintptr_t bytes) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a + bytes <= b || b + bytes <= a;
+}
+
+int vfx_stft_splice(vfx_handle* h, const float* x, const float* y, int B, int L, const int* lengths, const int* cut_bins, int ramp,
+                    const float* gains, float* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(x && y && lengths && cut_bins && out, "vfx_stft_splice: NULL argument");
+  VFX_CHECK(B > 0 && L > 0, "vfx_stft_splice: need B > 0 and L > 0, got B=%d L=%d", B, L);
+  VFX_CHECK(h->cfg.n_fft == 2048, "vfx_stft_splice: needs the 44.1 kHz front end (n_fft 2048)");
+  VFX_CHECK(ramp >= 0, "vfx_stft_splice: ramp = %d bins (need >= 0)", ramp);
+  std::vector<int> gbits(B);  // the gains as float32 bit patterns: they travel in an int row of d_lens
+  for (int b = 0; b < B; ++b) {
+    VFX_CHECK(lengths[b] > h->cfg.n_fft / 2 && lengths[b] <= L,
+              "vfx_stft_splice: clip %d has %d samples (need n_fft/2 = %d < length <= L = %d: reflect padding)", b, lengths[b],
+              h->cfg.n_fft / 2, L);
+    VFX_CHECK(cut_bins[b] >= 0, "vfx_stft_splice: clip %d has cut-off bin %d (need >= 0)", b, cut_bins[b]);
+    const float g = gains ? gains[b] : 1.f;
+    VFX_CHECK(std::isfinite(g), "vfx_stft_splice: clip %d has gain %g (need a finite gain)", b, (double)g);
+    std::memcpy(&gbits[b], &g, sizeof(float));
+  }
+  const uintptr_t bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float);
+  VFX_CHECK(ranges_disjoint(out, x, bytes), "vfx_stft_splice: out overlaps x (a workgroup reads samples its neighbours write)");
+  VFX_CHECK(ranges_disjoint(out, y, bytes), "vfx_stft_splice: out overlaps y (a workgroup reads samples its neighbours write)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_l = h->lens_row(LENS_SPLICE_SAMPLES);
+  int* const d_c = h->lens_row(LENS_SPLICE_CUT);
+  int* const d_g = h->lens_row(LENS_SPLICE_GAIN);
+  for (int b0 = 0; b0 < B; b0 += kSpliceMaxClips) {  // (a clip's samples do not depend on the launch it is in)
+    const int n = std::min(kSpliceMaxClips, B - b0);
+    launch_set_frames(d_l, lengths + b0, n, s);
+    launch_set_frames(d_c, cut_bins + b0, n, s);
+    launch_set_frames(d_g, gbits.data() + b0, n, s);
+    launch_stft_splice(h->fe, x + (int64_t)b0 * L, y + (int64_t)b0 * L, n, L, h->cfg.hop, d_l, d_c, d_g, ramp, out + (int64_t)b0 * L, s);
+  }
+  VFX_API_END
+}
+
+int vfx_band_power(vfx_handle* h, const float* a, const float* b, int B, int Lmax, const int* lengths, const int* lo_bins,
+                   const int* hi_bins, double* out, void* stream) {
+  VFX_API_BEGIN_HS(h, stream)
+  VFX_CHECK(a && b && lo_bins && hi_bins && out, "vfx_band_power: NULL argument");
+  VFX_CHECK(B > 0 && Lmax > 0, "vfx_band_power: need B > 0 and Lmax > 0, got B=%d Lmax=%d", B, Lmax);
+  VFX_CHECK(h->cfg.n_fft == 2048, "vfx_band_power: needs the 44.1 kHz front end (n_fft 2048)");
+  const int hop = h->cfg.hop, half = h->cfg.n_fft / 2, nbins = half + 1;
+  std::vector<int> host(2 * (size_t)B);  // samples | frames
+  for (int i = 0; i < B; ++i) {
+    const int Lb = lengths ? lengths[i] : Lmax;
+    VFX_CHECK(Lb > half && Lb <= Lmax, "vfx_band_power: clip %d has %d samples (need %d < length <= Lmax = %d: reflect padding)", i, Lb, half,
+              Lmax);
+    VFX_CHECK(lo_bins[i] >= 0 && hi_bins[i] <= nbins && hi_bins[i] >= lo_bins[i],
+              "vfx_band_power: clip %d has the band [%d, %d) (need 0 <= lo <= hi <= %d)", i, lo_bins[i], hi_bins[i], nbins);
+    host[i] = Lb;
+    host[(size_t)B + i] = Lb / hop + 1;
+  }
+  const uintptr_t in_bytes = (uintptr_t)B * (uintptr_t)Lmax * sizeof(float), out_bytes = (uintptr_t)B * 2 * sizeof(double);
+  for (const float* in : {a, b}) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    VFX_CHECK(o0 + out_bytes <= i0 || i0 + in_bytes <= o0, "vfx_band_power: out overlaps %s", in == a ? "a" : "b");
+  }
+  const int T = frames_of(h, Lmax);
+  const int step = std::min(B, kSpliceMaxClips);
+  double* const ws = reinterpret_cast<double*>(h->scratch.ensure(
+      h, (size_t)step * T * 2 * sizeof(double), 8, "the varlen scratch would have to grow from %zu to %zu bytes, but a hipGraph was captured "
+      "from plan '%s': run the largest vfx_band_power batch once BEFORE capturing"));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* const d_n = h->lens_row(LENS_POWER_SAMPLES);
+  int* const d_f = h->lens_row(LENS_POWER_FRAMES);
+  int* const d_lo = h->lens_row(LENS_POWER_LO);
+  int* const d_hi = h->lens_row(LENS_POWER_HI);
+  for (int b0 = 0; b0 < B; b0 += step) {  // (a clip's numbers do not depend on the launch it is in)
+    const int n = std::min(step, B - b0);
+    launch_set_frames(d_n, host.data() + b0, n, s);
+    launch_set_frames(d_f, host.data() + B + b0, n, s);
+    launch_set_frames(d_lo, lo_bins + b0, n, s);
+    launch_set_frames(d_hi, hi_bins + b0, n, s);
+    launch_pair_band_power(h->fe, a + (int64_t)b0 * Lmax, b + (int64_t)b0 * Lmax, n, Lmax, T, d_n, d_lo, d_hi, d_f, hop, 1e-8f, ws,
+                           out + (int64_t)b0 * 2, s);
   }
   VFX_API_END
 }

@@ -205,6 +205,12 @@ __global__ __launch_bounds__(128) void k_mel_project(const float* __restrict__ s
 // above.  No spectrum in HBM; the 4 halo frames of a group are transformed forward by both neighbours ((IH + 4) / IH forward
 // FFTs per frame).  Every expression is the one the two-launch path (k_stft_mel<true>, sp * cos and sp * sin by torch, k_istft)
 // evaluates, so the samples are bit for bit that path's.
+//
+// Splice (vfx_stft_splice, k_stft_splice): the same workgroup once more, over TWO rows -- the input x and the restored clip y.  The
+// wave loads the frame from both, forms d = x - g y in registers, makes the spectrum of d as above with the weight a[k] of splice.py's
+// ramp_weights in place of the hard mask, and the final loop adds g y back: g y + ISTFT(a . STFT(x - g y)), which by linearity is
+// ISTFT(a STFT(x) + (1 - a) STFT(g y)) -- x below the seam, g y above -- with one forward transform per frame.  Bit for bit the chain
+// torch (g y, x - g y), k_stft_mel<true>, torch (the products and weights), k_istft, torch (+).
 
 // a * b rounded to float32 ON ITS OWN: never the multiplication of an FMA.  The two-launch path stores mag * cos and mag * sin
 // to memory as float32 before the pack adds them; here the products feed straight into the pack's sums.  (The file's pragma says
@@ -216,8 +222,12 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
 
 // One frame of the low-pass, by the wave that owns it.  In: xk = the sixteen sample pairs load_frame left.  Out: xk[r] = X[k],
 // xn[r] = X[1024 - k], k = lane + 64 r -- what k_istft's load_spectrum leaves -- with X = 0 for the bins k >= cut.
+// RAMP (k_stft_splice): the bins cut - ramp <= k < cut are weighted by a[k] = float(cut - k) / float(ramp + 1) -- one division, computed
+// from k, no table -- each of the two products times a[k], rounded on its own; the bins below them (a = 1) are left as they are.
+// ramp = 0 is the hard mask.
+template <bool RAMP>
 __device__ __forceinline__ void lowpass_spectrum(float2 (&xk)[16], float2 (&xn)[16], float2* zw, const float2* twl,
-                                                 const float2* wl, float2 rtw_lane, int lane, int cut) {
+                                                 const float2* wl, float2 rtw_lane, int lane, int cut, int ramp) {
   asm volatile("" : "+v"(rtw_lane.x), "+v"(rtw_lane.y));  // the sixteen W^k are made per frame, not kept across the frame walk (and spilled)
   float2 v[16];
 #pragma unroll
@@ -234,7 +244,16 @@ __device__ __forceinline__ void lowpass_spectrum(float2 (&xk)[16], float2 (&xn)[
     untangle_bin(zk, znk, wk, 1e-8f, re, im, mag);  // eps of wav_to_spectrogram_phase
     const float inv = __builtin_amdgcn_rcpf(mag);
     const float c = re * inv, s = im * inv;  // what k_stft_mel stores as cos / sin
-    return k >= cut ? make_float2(0.f, 0.f) : make_float2(mul_rounded(mag, c), mul_rounded(mag, s));
+    if constexpr (RAMP) {
+      float2 X = make_float2(mul_rounded(mag, c), mul_rounded(mag, s));
+      if (k >= cut - ramp) {
+        const float a = __fdiv_rn((float)(cut - k), (float)(ramp + 1));
+        X = make_float2(mul_rounded(X.x, a), mul_rounded(X.y, a));
+      }
+      return k >= cut ? make_float2(0.f, 0.f) : X;
+    } else {  // (the low-pass's own expression, kept as it was: k_stft_lowpass compiles to the instructions it had)
+      return k >= cut ? make_float2(0.f, 0.f) : make_float2(mul_rounded(mag, c), mul_rounded(mag, s));
+    }
   };
   float2 top = make_float2(0.f, 0.f);
   if (lane == 0) top = bin(NC, v[0], xn[0], make_float2(-1.f, 0.f));  // Z[1024] = Z[0], W^1024 = -1
@@ -247,16 +266,24 @@ __device__ __forceinline__ void lowpass_spectrum(float2 (&xk)[16], float2 (&xn)[
   mirror_bins(xk, xn, zw, lane);
 }
 
-// One workgroup of the inverse.  LOWPASS = false (k_istft): the spectrum is re / im (B, T, 1025).  true (k_stft_lowpass): it is
-// made from the rows of `src` (B, L) as above, masked from bin cuts[b] up; re / im are not read.
-template <bool LOWPASS>
+// Where a workgroup of the inverse takes its spectrum from
+enum IstftMode {
+  ISTFT_SPECTRUM,  // k_istft: re / im (B, T, 1025)
+  ISTFT_LOWPASS,   // k_stft_lowpass: made from the rows of `src` (B, L) as above, masked from bin cuts[b] up; re / im are not read
+  ISTFT_SPLICE     // k_stft_splice: made from d = src - gains[b] * src2 (both (B, L)) with the ramp below cuts[b], and gains[b] * src2
+                   // is added to the samples at the end
+};
+
+// One workgroup of the inverse.
+template <IstftMode MODE>
 __device__ __forceinline__ void istft_group(const float* __restrict__ re, const float* __restrict__ im,
-                                            const float* __restrict__ src, const int* __restrict__ cuts,
+                                            const float* __restrict__ src, const float* __restrict__ src2,
+                                            const int* __restrict__ cuts, const int* __restrict__ gains, int ramp,
                                             const float* __restrict__ window, const float2* __restrict__ tw,
                                             const float2* __restrict__ rtw, int T, int L, int hop, int groups, int IH,
                                             float* __restrict__ wav, const int* __restrict__ lens) {
   __shared__ float2 twl[NC];
-  __shared__ float2 wl[NC];  // the synthesis window, as pairs (LOWPASS: the analysis window too)
+  __shared__ float2 wl[NC];  // the synthesis window, as pairs (ISTFT_LOWPASS, ISTFT_SPLICE: the analysis window too)
   __shared__ float2 zbuf[STFT_WAVES][ZP];
   extern __shared__ __attribute__((aligned(16))) float ola[];  // [IH * hop]
   const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
@@ -284,10 +311,17 @@ __device__ __forceinline__ void istft_group(const float* __restrict__ re, const 
   __syncthreads();  // ola zeroed, twl and wl complete
 
   // the spectrum of this wave's frame of a round: (Re, Im) of bins k and 1024 - k, k = lane + 64 r
-  // (LOWPASS: what is requested ahead is the frame's samples, in xk; lowpass_spectrum turns them into the spectrum in place)
+  // (ISTFT_LOWPASS: what is requested ahead is the frame's samples, in xk; lowpass_spectrum turns them into the spectrum in place.
+  // ISTFT_SPLICE: the samples of both rows, the second in yk, at the same indices)
   float2 xk[16], xn[16];
+  [[maybe_unused]] float2 yk[16];
+  [[maybe_unused]] float gain = 1.f;
+  if constexpr (MODE == ISTFT_SPLICE) gain = __int_as_float(gains[b]);  // (a float32 bit pattern: the host arrays travel in int rows)
   auto load_spectrum = [&](int t) __attribute__((always_inline)) {
-    if constexpr (LOWPASS) {
+    if constexpr (MODE == ISTFT_SPLICE) {
+      load_frame(src + (int64_t)b * Ls, L, t, hop, lane, xk);
+      load_frame(src2 + (int64_t)b * Ls, L, t, hop, lane, yk);
+    } else if constexpr (MODE == ISTFT_LOWPASS) {
       load_frame(src + (int64_t)b * Ls, L, t, hop, lane, xk);
     } else {
       const float* R = re + ((int64_t)b * Ts + t) * NBINS;
@@ -316,7 +350,13 @@ __device__ __forceinline__ void istft_group(const float* __restrict__ re, const 
     while (r == round) {
       const int t = t_lo + f;
       asm volatile("" : "+v"(lane));  // as in the forward kernel
-      if constexpr (LOWPASS) lowpass_spectrum(xk, xn, zbuf[wave], twl, wl, rtw_lane, lane, cuts[b]);
+      if constexpr (MODE == ISTFT_SPLICE) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)  // d = x - g y: the product rounded, then one subtraction
+          xk[q] = make_float2(xk[q].x - mul_rounded(gain, yk[q].x), xk[q].y - mul_rounded(gain, yk[q].y));
+        lowpass_spectrum<true>(xk, xn, zbuf[wave], twl, wl, rtw_lane, lane, cuts[b], ramp);
+      }
+      if constexpr (MODE == ISTFT_LOWPASS) lowpass_spectrum<false>(xk, xn, zbuf[wave], twl, wl, rtw_lane, lane, cuts[b], 0);
       float2 v[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -361,6 +401,7 @@ __device__ __forceinline__ void istft_group(const float* __restrict__ re, const 
         }
       }
       out = env > 1.1754944e-38f ? ola[i] / env : ola[i];
+      if constexpr (MODE == ISTFT_SPLICE) out = mul_rounded(gain, src2[(int64_t)b * Ls + n]) + out;  // g y, the same rounded product, + r
     }
     wav[(int64_t)b * Ls + n] = out;
   }
@@ -370,7 +411,7 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_istft(const float* __res
                                                               const float* __restrict__ window, const float2* __restrict__ tw,
                                                               const float2* __restrict__ rtw, int T, int L, int hop, int groups,
                                                               int IH, float* __restrict__ wav, const int* __restrict__ lens) {
-  istft_group<false>(re, im, nullptr, nullptr, window, tw, rtw, T, L, hop, groups, IH, wav, lens);
+  istft_group<ISTFT_SPECTRUM>(re, im, nullptr, nullptr, nullptr, nullptr, 0, window, tw, rtw, T, L, hop, groups, IH, wav, lens);
 }
 
 // wav (B, L), clip b = its first lens[b] samples (1024 < lens[b] <= L) -> out (B, L): the clip with the STFT bins from cut[b] up
@@ -382,7 +423,20 @@ __global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_lowpass(const float
                                                                      const float2* __restrict__ tw,
                                                                      const float2* __restrict__ rtw, int T, int L, int hop,
                                                                      int groups, int IH, float* __restrict__ out) {
-  istft_group<true>(nullptr, nullptr, wav, cut, window, tw, rtw, T, L, hop, groups, IH, out, lens);
+  istft_group<ISTFT_LOWPASS>(nullptr, nullptr, wav, nullptr, cut, nullptr, 0, window, tw, rtw, T, L, hop, groups, IH, out, lens);
+}
+
+// x, y (B, L), pair b = the first lens[b] samples of both rows (1024 < lens[b] <= L) -> out (B, L) = g y + ISTFT(a . STFT(x - g y)),
+// g = gains[b] (a float32 bit pattern), a = 1 below bin cut[b] - ramp, 0 from cut[b] up, the linear ramp between; zeros past lens[b].
+// By linearity ISTFT(a STFT(x) + (1 - a) STFT(g y)): x below the seam, g y above it, with one forward transform per frame.  `out` must
+// overlap neither x nor y; nothing at or past lens[b] of either row is read.
+__global__ __launch_bounds__(STFT_WAVES * 64, 2) void k_stft_splice(const float* __restrict__ x, const float* __restrict__ y,
+                                                                    const int* __restrict__ lens, const int* __restrict__ cut,
+                                                                    const int* __restrict__ gains, int ramp,
+                                                                    const float* __restrict__ window, const float2* __restrict__ tw,
+                                                                    const float2* __restrict__ rtw, int T, int L, int hop, int groups,
+                                                                    int IH, float* __restrict__ out) {
+  istft_group<ISTFT_SPLICE>(nullptr, nullptr, x, y, cut, gains, ramp, window, tw, rtw, T, L, hop, groups, IH, out, lens);
 }
 
 // Frames per wave of the forward kernel: as many as keep the launch at about one round of resident waves
@@ -437,6 +491,16 @@ void launch_stft_lowpass(const FrontEndTables& t, const float* wav, int B, int L
   hipLaunchKernelGGL(k_stft_lowpass, dim3(B * g.groups), dim3(256), (size_t)g.span * sizeof(float), stream, wav, lens, cut,
                      t.window, reinterpret_cast<const float2*>(t.twiddle), reinterpret_cast<const float2*>(t.rtwiddle), T, L,
                      hop, g.groups, g.IH, out);
+  VFX_HIP(hipGetLastError());
+}
+
+void launch_stft_splice(const FrontEndTables& t, const float* x, const float* y, int B, int L, int hop, const int* lens, const int* cut,
+                        const int* gains, int ramp, float* out, hipStream_t stream) {
+  const int T = L / hop + 1;  // frames of a clip that fills its row
+  const IstftGrid g = istft_grid(B, T, L, hop);
+  hipLaunchKernelGGL(k_stft_splice, dim3(B * g.groups), dim3(256), (size_t)g.span * sizeof(float), stream, x, y, lens, cut, gains, ramp,
+                     t.window, reinterpret_cast<const float2*>(t.twiddle), reinterpret_cast<const float2*>(t.rtwiddle), T, L, hop,
+                     g.groups, g.IH, out);
   VFX_HIP(hipGetLastError());
 }
 

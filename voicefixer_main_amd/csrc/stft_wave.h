@@ -1,6 +1,7 @@
 // stft_wave.h -- the wave-level arithmetic of the STFT front end that more than one kernel file evaluates: the 1024-point complex FFT
 // of one wave, the reflect-padded frame load, the real-FFT untangle and the clamped magnitude.  stft.hip (k_stft_mel, k_istft,
-// k_stft_lowpass), losses.hip (k_pair_stft_l1) and band.hip (k_band_energy) include it; a magnitude is the same float32 in all of them.
+// k_stft_lowpass, k_stft_splice), losses.hip (k_pair_stft_l1), band.hip (k_band_energy) and splice.hip (k_pair_band_power) include it; a
+// magnitude is the same float32 in all of them.
 #pragma once
 #include "vfx_internal.h"
 

@@ -167,7 +167,10 @@ enum LensRow {
   LENS_TARGET_SAMPLES = 17,                                            // samples of the targets of a vfx_restore_*_varlen_scored call
   LENS_BSS_SAMPLES = 18,                                               // samples of the vfx_bsseval sub-batch in flight
   LENS_LOSS_COUNT = 19, LENS_LOSS_FRAMES = 20,                         // elements per row / frames of the vfx_spec_losses or vfx_validate_gsr_varlen sub-batch in flight
-  kLensRows = 21
+  LENS_SPLICE_SAMPLES = 21, LENS_SPLICE_CUT = 22, LENS_SPLICE_GAIN = 23,  // samples / cut-off bin / gain (a float32 bit pattern) of the vfx_stft_splice sub-batch in flight
+  LENS_POWER_SAMPLES = 24, LENS_POWER_FRAMES = 25,                     // samples / frames of the vfx_band_power sub-batch in flight ...
+  LENS_POWER_LO = 26, LENS_POWER_HI = 27,                              // ... and the first bin of its band / the bin behind it
+  kLensRows = 28
 };
 constexpr size_t kMaxCachedPlans = 32; // per handle (round 5: 8 -> 32 -- a file with a target alternates between more than eight (stage, B, T) keys and rebuilt plans on every call; a plan is ~0.4 MB on each side); a plan owns host + device parameter blocks (the eval handler's last
                                         // segment has a new length for every file)  // patch pixels per stage (6 row groups of 32)
@@ -465,8 +468,15 @@ void launch_istft(const FrontEndTables& t, const float* re, const float* im, int
 // sp * sin, masked, through launch_istft.
 void launch_stft_lowpass(const FrontEndTables& t, const float* wav, int B, int L, int hop, const int* lens, const int* cut,
                          float* out, hipStream_t stream);
-// The launch geometry of the two (host-only; the tests assert the geometry they exercise through these): the frames a wave of
-// k_stft_mel walks for a launch of `frames` = B * T frames; the hops a workgroup of k_istft / k_stft_lowpass owns and the groups per clip
+// The splice in one launch: x, y (B, L), pair b = the first lens[b] samples of both rows -> out (B, L) = g y + ISTFT(a . STFT(x - g y)),
+// g = gains[b] (float32 bit patterns), a = 1 below bin cut[b] - ramp, the linear ramp (cut[b] - k) / (ramp + 1) up to cut[b], 0 from
+// there; zeros past lens[b]; lens, cut, gains: device, [B].  out must overlap neither x nor y.  Bit for bit launch_stft_mel of
+// d = x - g y, its sp * cos and sp * sin weighted, through launch_istft, plus g y.
+void launch_stft_splice(const FrontEndTables& t, const float* x, const float* y, int B, int L, int hop, const int* lens, const int* cut,
+                        const int* gains, int ramp, float* out, hipStream_t stream);
+// The launch geometry of these (host-only; the tests assert the geometry they exercise through these): the frames a wave of
+// k_stft_mel walks for a launch of `frames` = B * T frames; the hops a workgroup of k_istft / k_stft_lowpass / k_stft_splice owns and
+// the groups per clip
 int frames_per_group(int64_t frames);
 struct IstftGrid {
   int IH, span, groups;
@@ -556,7 +566,14 @@ void launch_l1_rows(const float* a, const float* b, int B, int64_t ld, const int
 void launch_loss_final(const double* chunk_ws, int nchunk, const int* counts, const double* frame_ws, int T, const int* frames, int nbins,
                        int col, double* out, int stride, int B, hipStream_t s);
 
-// band.hip: the bandwidth detector (vfx_band_energy).  The clips' lengths travel as kernel arguments, at most kBandMaxClips per launch
+// splice.hip: the level match of the splice (vfx_band_power).  a, b (B, L), pair p = the first lens[p] samples of both rows -> out (B, 2):
+// the sums over its frames[p] = lens[p] / hop + 1 frames and the bins lo[p] <= k < hi[p] of |A|^2 and |B|^2 in float64, the magnitudes
+// launch_stft_mel's (eps), bit for bit; lens, lo, hi, frames: device, [B]; ws: B * T * 2 doubles.  No spectrum is stored.
+constexpr int kSpliceMaxClips = 128;  // clips per launch set of vfx_stft_splice and vfx_band_power (a clip's numbers do not depend on it)
+void launch_pair_band_power(const FrontEndTables& t, const float* a, const float* b, int B, int L, int T, const int* lens, const int* lo,
+                            const int* hi, const int* frames, int hop, float eps, double* ws, double* out, hipStream_t s);
+
+// band.hip: the bandwidth detector (vfx_band_energy). The clips' lengths travel as kernel arguments, at most kBandMaxClips per launch
 // set (clip_batch.h).
 constexpr int kBandFrames = 8;      // consecutive frames of a clip per wave of k_band_energy: a constant, so that which frames a partial
                                     // sum holds depends on the clip alone

@@ -284,6 +284,46 @@ class Engine:
                                              self._stream()), "vfx_stft_lowpass")
         return y[0] if squeeze else y
 
+    def stft_splice(self, x, y, cut_bins, lengths=None, ramp=0, gains=None):
+        """The splice of restored clips onto their band-limited inputs in ONE launch (vfx_stft_splice): x (the input), y (the restored
+        clip) (B, L) or (L,), pair b = the first lengths[b] samples of row b of both (default L; 1024 < lengths[b] <= L); cut_bins: the
+        first bin that is y's alone, one int or one per clip (>= 0); ramp: the bins below it over which the weight of x falls from 1 to
+        0 (splice.ramp_weights; 0: the hard mask of stft_lowpass); gains: g, one float or one per clip (default 1).  -> float32 of the
+        same shape on the device, g y + ISTFT(a . STFT(x - g y)): x below the seam, g y above it; rows zero past their length.  Row b
+        is bit for bit the chain stft -> weights -> istft on the pair alone, whatever batch it is in."""
+        x, y = _dev_f32(x, self.device), _dev_f32(y, self.device)
+        if x.dim() not in (1, 2) or x.shape != y.shape:
+            raise ValueError("stft_splice: x %s and y %s must be equal (B, L) or (L,) tensors" % (tuple(x.shape), tuple(y.shape)))
+        x, squeeze, B, L, lengths = _clip_rows(x, lengths, "stft_splice")
+        y = y[None] if squeeze else y
+        cut_bins = _per_clip(cut_bins, B, int, "stft_splice", "cut-off bins")
+        if B == 0:
+            raise ValueError("stft_splice: %d cut-off bins for %d clips" % (len(cut_bins), B))
+        g = None if gains is None else (ctypes.c_float * B)(*_per_clip(gains, B, float, "stft_splice", "gains"))
+        out = torch.empty((B, L), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.vfx_stft_splice(self.h, _ptr(x), _ptr(y), B, L, (ctypes.c_int * B)(*lengths), (ctypes.c_int * B)(*cut_bins),
+                                            int(ramp), g, _ptr(out), self._stream()), "vfx_stft_splice")
+        return out[0] if squeeze else out
+
+    def band_power(self, a, b, lo_bins, hi_bins, lengths=None):
+        """The power of two clips in a band of STFT bins (vfx_band_power): a, b (B, L) or (L,), pair p = the first lengths[p] samples of
+        row p of both (default L; 1024 < lengths[p] <= L); lo_bins, hi_bins: the band lo <= k < hi, one int or one per clip
+        (0 <= lo <= hi <= 1025) -> (B, 2) or (2,) float64 on the device: the sums over the clip's frames and the band of |A|^2 and
+        |B|^2, the magnitudes stft's (eps 1e-8).  hi == lo gives zeros.  A pair's numbers do not depend on the batch it is in."""
+        a, b = _dev_f32(a, self.device), _dev_f32(b, self.device)
+        if a.dim() not in (1, 2) or a.shape != b.shape:
+            raise ValueError("band_power: a %s and b %s must be equal (B, L) or (L,) tensors" % (tuple(a.shape), tuple(b.shape)))
+        a, squeeze, B, L, lengths = _clip_rows(a, lengths, "band_power")
+        b = b[None] if squeeze else b
+        lo_bins = _per_clip(lo_bins, B, int, "band_power", "lower bins")
+        hi_bins = _per_clip(hi_bins, B, int, "band_power", "upper bins")
+        if B == 0:
+            raise ValueError("band_power: no clips")
+        out = torch.empty((B, 2), device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.vfx_band_power(self.h, _ptr(a), _ptr(b), B, L, (ctypes.c_int * B)(*lengths), (ctypes.c_int * B)(*lo_bins),
+                                           (ctypes.c_int * B)(*hi_bins), _ptr(out), self._stream()), "vfx_band_power")
+        return out[0] if squeeze else out
+
     def band_energy(self, wav, lengths=None, hop=512, threshold=0.95):
         """The bandwidth detector of load_wav_energy (tools/utils.py:33-44) for a padded batch (vfx_band_energy): wav (B, L) or (L,),
         clip b = the first lengths[b] samples of row b (default L; 1024 < lengths[b] <= L), 1 <= hop <= 2048 (librosa.stft's default

@@ -412,6 +412,30 @@ def _restore_prefiltered_list(model, wavs, threshold, kwargs):
     return model.restore_list(wavs, **kwargs), cutoffs
 
 
+def _restore_spliced_list(model, wavs, cut_bins, threshold, ramp, match, max_gain_db, kwargs):
+    """The list layer under the two restore_spliced_list methods: resample to 44.1 kHz, take each clip's cut-off bin from the bandwidth
+    detector (splice.cut_bins_list) unless the caller gave them, restore the UNFILTERED clips (the model's own restore_list), splice each
+    result onto its input (splice.splice_list).  The clips are device tensors from the first step on.  Under torch.distributed the
+    splice runs on the rank that holds restore_list's gathered outputs; the other ranks return (None, None)."""
+    from . import simulate, splice
+    eng = model.engine
+    sample_rate = kwargs.pop("sample_rate", 44100)
+    wavs = _resample_list(eng, list(wavs), sample_rate)      # the detector and the splice are defined at 44.1 kHz
+    wavs = [clips.as_tensor(w).reshape(-1).to(device=eng.device, dtype=torch.float32) for w in wavs]
+    if cut_bins is None:
+        bins = splice.cut_bins_list(wavs, threshold, engine=eng)
+    else:
+        bins = [int(cut_bins)] * len(wavs) if np.ndim(cut_bins) == 0 else [int(c) for c in cut_bins]
+        if len(bins) != len(wavs):
+            raise ValueError("restore_spliced_list: %d cut-off bins for %d clips" % (len(bins), len(wavs)))
+    restored = model.restore_list(wavs, **kwargs)
+    if restored is None:
+        return None, None
+    outs, gains = splice.splice_list(wavs, restored, bins, ramp=ramp, match=match, max_gain_db=max_gain_db, engine=eng)
+    info = [{"cut_bin": c, "cutoff_hz": simulate.band_cutoff_hz(c, eng.cfg.sample_rate), "gain": g} for c, g in zip(bins, gains)]
+    return outs, info
+
+
 MIN_RESTORE_SAMPLES = 1025     # more than n_fft / 2 samples: the shortest clip restore_list takes (the STFT's reflect padding)
 
 
@@ -652,6 +676,17 @@ class VoiceFixer(_Base):
         A silent clip (cut-off 0) is restored unfiltered."""
         return _restore_prefiltered_list(self, wavs, threshold, kwargs)
 
+    def restore_spliced_list(self, wavs, cut_bins=None, threshold=0.95, ramp=8, match=64, max_gain_db=12.0, **kwargs):
+        """restore_list for BANDWIDTH EXTENSION of clean, band-limited input (8 / 16 kHz material, low-passed recordings): the band
+        below a clip's cut-off was fine to begin with, so the result keeps the input there and takes the restored clip above it.
+        Every clip's cut-off bin is the bandwidth detector's (Engine.band_energy at `threshold`) unless `cut_bins` gives them; the
+        unfiltered clips go through restore_list, which takes `kwargs` (a `sample_rate` other than 44.1 kHz is resampled first); then
+        splice.splice_list: a cross-fade of `ramp` STFT bins under the cut-off, the restored clip level-matched to the input over the
+        `match` bins under the ramp, within +-`max_gain_db` (match=0: no level match).  -> (outs, info) in input order, info[i] =
+        {"cut_bin", "cutoff_hz", "gain"}.  NOT for full-band noisy input: there the detector's cut-off lies near Nyquist and the splice
+        hands back mostly the input, noise included."""
+        return _restore_spliced_list(self, wavs, cut_bins, threshold, ramp, match, max_gain_db, kwargs)
+
     def restore_trimmed_list(self, wavs, threshold=500 / 2 ** 15, frame_length=0.02, **kwargs):
         """restore_list of the ACTIVE span of every clip: leading and trailing silence, as the reference's trim_empty finds it
         (tools/others/audio_op.py:107-109: window peaks below `threshold` in segments of `frame_length` seconds; 500 / 2**15 is its
@@ -745,6 +780,12 @@ class SSR_UNet(_Base):
         """restore_list with each clip low-passed at its own detected bandwidth first, the two lines eval_ssr_unet.py:105-106 keeps in
         front of the model: -> (restored clips, [cut-off in Hz per clip]) in input order (cf. VoiceFixer.restore_prefiltered_list)."""
         return _restore_prefiltered_list(self, wavs, threshold, kwargs)
+
+    def restore_spliced_list(self, wavs, cut_bins=None, threshold=0.95, ramp=8, match=64, max_gain_db=12.0, **kwargs):
+        """restore_list for bandwidth extension of clean, band-limited input: the input below each clip's detected cut-off, the
+        super-resolved clip above it, cross-faded and level-matched: -> (outs, info) in input order (cf.
+        VoiceFixer.restore_spliced_list; not for full-band noisy input, which the splice would mostly hand back)."""
+        return _restore_spliced_list(self, wavs, cut_bins, threshold, ramp, match, max_gain_db, kwargs)
 
     def restore_trimmed_list(self, wavs, threshold=500 / 2 ** 15, frame_length=0.02, **kwargs):
         """restore_list of the active span of every clip, zeros around it: -> (outs, bounds) in input order (cf.
