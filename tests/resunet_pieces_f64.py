@@ -13,7 +13,9 @@ prologue may differ from this module's, pushed through the |weights|; see prolog
 import torch
 import torch.nn.functional as F
 
+import plan_chains as PC
 from launch_parity_f64 import U32, _operand
+from voicefixer_main_amd.engine import MODEL_UNET_SPEC
 
 BN_EPS = 1e-5
 SLOPE = 0.01
@@ -184,12 +186,11 @@ def final_mel(sd, y, mel, T):
     return dict(ref=F.pad(v, (0, 1)) + lg, S=F.pad(S, (0, 1)), log=lg)
 
 
-def generator_mel_chain(sd, mel, p=0):
-    """The mel ResUNet as the plan runs it, piece by piece: prep, entry, encoders with pools, bottleneck, decoders (upsample, the
-    two-source block, three more), after, final.  mel (B, T, 128) float32 -> (B, T, 128) float64."""
-    B, T, _ = mel.shape
-    Tpad = (T + 63) // 64 * 64
-    y = entry_chain(sd, prep_logmel(mel, Tpad).float(), p)
+def trunk_chain(sd, x, prune_w, p=0):
+    """The trunk both ResUNets share, piece by piece in plan order: entry, encoders with pools, bottleneck, decoders (upsample, the
+    two-source block, three more), after.  x (B, Tpad, W) float32 -> (B, Tpad, W, 32) float32.  prune_w: the spectrogram model's
+    even-width upsamplers."""
+    y = entry_chain(sd, x, p)
     skips = []
     for l in range(1, 7):
         for j in range(2 if l == 1 else 1, 5):
@@ -198,18 +199,52 @@ def generator_mel_chain(sd, mel, p=0):
         y = pool(y)
     y = block_chain(sd, block_prefix("bott"), [y], p)
     for d in range(1, 7):
-        up = nhwc(upsample(sd, block_prefix("dec%d.up" % d), y, False, p)["ref"]).float().contiguous()
+        up = nhwc(upsample(sd, block_prefix("dec%d.up" % d), y, prune_w, p)["ref"]).float().contiguous()
         y = block_chain(sd, block_prefix("dec%d.1" % d), [up, skips[6 - d]], p)
         for j in (2, 3, 4):
             y = block_chain(sd, block_prefix("dec%d.%d" % (d, j)), [y], p)
-    y = block_chain(sd, block_prefix("after"), [y], p)
-    return final_mel(sd, y, mel, T)["ref"]
+    return block_chain(sd, block_prefix("after"), [y], p)
+
+
+def generator_mel_chain(sd, mel, p=0):
+    """The mel ResUNet as the plan runs it, piece by piece: prep, the trunk, final.  mel (B, T, 128) float32 -> (B, T, 128) float64."""
+    B, T, _ = mel.shape
+    Tpad = (T + 63) // 64 * 64
+    return final_mel(sd, trunk_chain(sd, prep_logmel(mel, Tpad).float(), False, p), mel, T)["ref"]
+
+
+def final_spec_mag(sd, y, T):
+    """after_conv2 (1x1, 32 -> 1, bias) on rows < T of the trunk's output y (B, Tpad, W, 32), the last bin 0 -> dict with ref and S
+    (B, T, W + 1) float64: the magnitude the spectrogram model's epilogue multiplies with cos and sin."""
+    w = sd["after_conv2.weight"].double().reshape(32)
+    bias = sd["after_conv2.bias"].double()
+    mag = (y[:, :T].double() * w).sum(-1) + bias
+    S = (y[:, :T].double().abs() * w.abs()).sum(-1) + bias.abs()
+    return dict(ref=F.pad(mag, (0, 1)), S=F.pad(S, (0, 1)))
+
+
+def prep_spec(sp, Tpad, lens=None):
+    """(B, T, W + 1) magnitudes -> (B, Tpad, W) float32: a copy without the last bin, zeros past each clip's frames."""
+    B, T, W1 = sp.shape
+    out = torch.zeros((B, Tpad, W1 - 1))
+    for b in range(B):
+        L = T if lens is None else min(T, lens[b])
+        out[b, :L] = sp[b, :L, :W1 - 1]
+    return out
+
+
+def spec_mag_chain(sd, sp, p=0):
+    """The spectrogram ResUNet's magnitude as the plan runs it: prep_spec, the trunk with pruned upsamplers, after_conv2 with the last
+    bin 0.  sp (B, T, 1025) float32 -> (B, T, 1025) float64."""
+    B, T, _ = sp.shape
+    Tpad = (T + 63) // 64 * 64
+    return final_spec_mag(sd, trunk_chain(sd, prep_spec(sp, Tpad), True, p), T)["ref"]
 
 
 # The deep pieces (two launches of k_conv each: C >= 128, and the blocks with a 1x1 shortcut above C = 32) at the mel net's own level shapes for Tpad = 64 and 128 --
 # level l runs at (Tpad >> (l - 1), 127 >> (l - 1)), the bottleneck at (1, 1) and (2, 1) -- plus shapes that are no multiple of a tile.
-def _level(l):
-    return [(64 >> (l - 1), 127 >> (l - 1)), (128 >> (l - 1), 127 >> (l - 1))]
+def _level(l, W0=127):
+    return [(64 >> (l - 1), W0 >> (l - 1)), (128 >> (l - 1), W0 >> (l - 1))]
 
 
 DEEP_CASES = {
@@ -221,11 +256,11 @@ DEEP_CASES = {
 SHORT_CLIPS = (1, 0, -2)
 
 
-def splitk_coverage(plan):
-    """plan(piece, H, W, short_clip) -> launches (Engine.plan_unet_piece).  -> the ksplit values the DEEP_CASES run with an activated
-    output, and with shortcut segments plus bias."""
+def splitk_coverage(plan, cases=None):
+    """plan(piece, H, W, short_clip) -> launches (Engine.plan_unet_piece).  -> the ksplit values the deep cases (default: DEEP_CASES)
+    run with an activated output, and with shortcut segments plus bias."""
     act, shortcut = set(), set()
-    for piece, shapes in DEEP_CASES.items():
+    for piece, shapes in (DEEP_CASES if cases is None else cases).items():
         for H, W in shapes:
             for sc in SHORT_CLIPS:
                 for l in plan(piece, H, W, sc):
@@ -234,3 +269,48 @@ def splitk_coverage(plan):
                     if l["family"] == "k_conv" and l["bias"] and l["nseg"] >= 2:
                         shortcut.add(l["ksplit"])
     return act, shortcut
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The spectrogram model's geometry: trunk width 1024, even-width (pruned) upsamplers, so level l runs at (Tpad >> (l - 1), 1024 >> (l - 1))
+# and the bottleneck at (1, 16) and (2, 16).  Every shape is read off plan_chains.unet_geometry(MODEL_UNET_SPEC, T) for T = 64 and
+# T = 128 -- the (H, W) the chain of the network's own pieces hands each piece -- not typed in.
+# ---------------------------------------------------------------------------------------------------------------------------------
+SPEC_W0 = PC.UNET_WIDTH[MODEL_UNET_SPEC]
+SPEC_T = (64, 128)
+
+
+def spec_shapes(piece, Ts=SPEC_T):
+    """-> [(H, W)]: what the spectrogram chain hands `piece` for clips of each T in Ts frames ("pool": every level's, in order)."""
+    return [(H, W) for T in Ts for pc, _, H, W in PC.unet_geometry(MODEL_UNET_SPEC, T) if pc == piece]
+
+
+SPEC_FUSED_SHAPES = spec_shapes("entry", (64,))                      # level 1 at Tpad = 64: (64, 1024)
+SPEC_DEEP_CASES = {piece: spec_shapes(piece) for piece in DEEP_CASES}
+SPEC_UP_CASES = {d: spec_shapes("dec%d.up" % d, (64,))[0] for d in range(1, 7)}   # (1, 16) -> (2, 32) ... (32, 512) -> (64, 1024)
+SPEC_UP_WIDE_UNPRUNED = (5, SPEC_UP_CASES[5])                        # the one arg = 0 case: (16, 256) -> (32, 513)
+# (piece, (H, W), B): the single-launch blocks (two k_conv launches each in fp32); B = 1 at (64, 1024) keeps the float64 reference short
+SPEC_FUSED_CASES = [(piece, spec_shapes(piece, (64,))[0], 1) for piece in ("enc1.2", "dec6.1", "after")] + \
+                   [(piece, spec_shapes(piece, (64,))[0], 2) for piece in ("enc2.2", "dec5.2")]
+SPEC_OLD_BLOCK2D_CASE = ("enc1.3", spec_shapes("enc1.3", (64,))[0], 1)
+SPEC_POOL_CASES = [(64, SPEC_W0, 32), (2, SPEC_W0 >> 5, 384)]         # level 1 at Tpad = 64, level 6 at Tpad = 64
+SPEC_FINAL_T = (3, 70)                                              # T < Tpad = 64, and T = 70 on a Tpad = 128 trunk
+SPEC_PREP_CASE = (130, [130, 67])                                   # T, frames per clip
+
+
+def spec_launch_cases(precision):
+    """Every spectrogram-geometry case of tests/test_gpu_resunet_launches.py as the arguments of Engine.plan_unet_piece:
+    -> [(piece, B, H, W, arg, short_clip, tuning name or None)].  tests/test_resunet_pieces_host.py holds the families these launch to
+    the whole spectrogram plan's."""
+    out = [("entry", 1) + SPEC_FUSED_SHAPES[0] + (0, 0, None)]
+    out += [(piece, B) + hw + (0, 0, None) for piece, hw, B in SPEC_FUSED_CASES]
+    if precision:
+        piece, hw, B = SPEC_OLD_BLOCK2D_CASE
+        out.append((piece, B) + hw + (0, 0, "TUNE_OLD_BLOCK2D"))
+    out += [(piece, 2, H, W, 0, sc, None) for piece, shapes in SPEC_DEEP_CASES.items() for H, W in shapes for sc in SHORT_CLIPS]
+    out += [("dec%d.up" % d, 2) + hw + (1, 0, None) for d, hw in SPEC_UP_CASES.items()]
+    out.append(("dec%d.up" % SPEC_UP_WIDE_UNPRUNED[0], 2) + SPEC_UP_WIDE_UNPRUNED[1] + (0, 0, None))
+    out += [("pool", 2, H, W, C, 0, None) for H, W, C in SPEC_POOL_CASES]
+    out += [("final", 2, T, SPEC_W0, 1, 0, None) for T in SPEC_FINAL_T]
+    out.append(("prep_spec", 2, SPEC_PREP_CASE[0], SPEC_W0 + 1, 0, 0, None))
+    return out

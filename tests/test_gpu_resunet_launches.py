@@ -33,6 +33,7 @@ import resunet_pieces_f64 as R
 from conftest import TOL
 from launch_parity_f64 import U32, _act_bar, _bar, _check, _rand
 from resunet_pieces_f64 import nchw
+from voicefixer_main_amd.engine import MODEL_UNET_MEL, MODEL_UNET_SPEC
 
 pytestmark = pytest.mark.gpu
 
@@ -68,8 +69,10 @@ def _families(launches):
     return [l["family"] for l in launches]
 
 
-def _block_case(eng, sd, piece, H, W, seed, short_clips=(0,)):
-    """One ConvBlockRes piece over (B, H, W): every launch against its reference; -> the launches of each run."""
+def _block_case(eng, sd, piece, H, W, seed, short_clips=(0,), model=MODEL_UNET_MEL, B=B, run=None, plan_B=None):
+    """One ConvBlockRes piece of `model` over (B, H, W): every launch against its reference; -> the launches of each run.
+    run: stands in for eng.op_unet_piece (tests/test_gpu_large_tensors.py: the same clips repeated to a batch of plan_B, of which it
+    hands back the first B)."""
     p, tol = _mode(eng)
     prefix = R.block_prefix(piece)
     cin = sd[prefix + ".conv1.weight"].shape[1]
@@ -79,7 +82,7 @@ def _block_case(eng, sd, piece, H, W, seed, short_clips=(0,)):
     ha, bar_ha = _h_bound(sd, prefix, c1, _bound(c1, p, tol), p, tol)
     runs = []
     for sc in short_clips:
-        (y,), h, launches = eng.op_unet_piece(piece, srcs, short_clip=sc)
+        (y,), h, launches = (run or eng.op_unet_piece)(piece, srcs, short_clip=sc, model=model)
         what = (piece, H, W, sc, _families(launches))
         if h is None:   # one launch: h stayed in LDS
             c2 = R.conv2(sd, prefix, ha, srcs, p)
@@ -90,7 +93,7 @@ def _block_case(eng, sd, piece, H, W, seed, short_clips=(0,)):
             _check(hg, ha, bar_ha, what + ("h",))
             c2 = R.conv2(sd, prefix, hg.double(), srcs, p)   # conv2 on its own input: the h the GPU stored, already in operand form
             _check(nchw(y.cpu()), c2["ref"], _bound(c2, p, tol), what + ("y",))
-        assert launches == eng.plan_unet_piece(piece, B, H, W, short_clip=sc, precision=eng.cfg.precision, tuning=eng.cfg.tuning), what
+        assert launches == eng.plan_unet_piece(piece, plan_B or B, H, W, short_clip=sc, precision=eng.cfg.precision, tuning=eng.cfg.tuning), what
         runs.append(launches)
     return runs
 
@@ -98,14 +101,14 @@ def _block_case(eng, sd, piece, H, W, seed, short_clips=(0,)):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # level 1: the single-launch blocks (two launches each in fp32)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _entry_case(eng, sd, H, W):
-    """encoder_block1.conv_block1 on a (B, H, W) plane; -> the launches' families."""
+def _entry_case(eng, sd, H, W, model=MODEL_UNET_MEL, B=B, run=None):
+    """encoder_block1.conv_block1 of `model` on a (B, H, W) plane; -> the launches' families."""
     p, tol = _mode(eng)
     prefix = "encoder_block1.conv_block1"
     x = _src((B, H, W), 11 * H + W, 1.2, -2.5)   # log-mel-like
     c1, sc = R.entry_conv1(sd, x, p)
     bar_h = _bound(c1, 0, tol)
-    (y,), h, launches = eng.op_unet_piece("entry", [x])
+    (y,), h, launches = (run or eng.op_unet_piece)("entry", [x], model=model)
     what = ("entry", H, W, _families(launches))
     if h is None:
         assert _families(launches) == ["k_resblock_in1"], what
@@ -193,12 +196,12 @@ UP_FALLBACK = [(1, 1), (2, 1), (1, 3)]            # four parity launches (the me
 UP_PHASED = [(2, 2), (2, 3), (5, 17), (16, 31)]   # one launch of four phases
 
 
-def _up_case(eng, sd, d, H, W, prune_w, seed):
+def _up_case(eng, sd, d, H, W, prune_w, seed, model=MODEL_UNET_MEL, run=None):
     p, tol = _mode(eng)
     cin = sd["decoder_block%d.conv1.weight" % d].shape[0]
     x = _src((B, H, W, cin), seed)
     r = R.upsample(sd, "decoder_block%d" % d, x, prune_w, p)
-    (y,), _, launches = eng.op_unet_piece("dec%d.up" % d, [x], arg=int(prune_w))
+    (y,), _, launches = (run or eng.op_unet_piece)("dec%d.up" % d, [x], arg=int(prune_w), model=model)
     assert y.shape == (B, 2 * H, 2 * W if prune_w else 2 * W + 1, r["ref"].shape[1])
     # (the output started as NaN: _check requires every element finite -- no pixel unwritten; a write past the last column would land in
     # the next row's first pixels and fail there)
@@ -228,10 +231,10 @@ def test_two_launch_upsamplers(engine, unet_sd):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # precision 2 runs the ResUNets as precision 1
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _engine(precision, tuning, sd):
-    from voicefixer_main_amd.engine import Engine, MODEL_UNET_MEL
+def _engine(precision, tuning, sd, model=MODEL_UNET_MEL):
+    from voicefixer_main_amd.engine import Engine
     eng = Engine("cuda:0", config={"precision": precision, "tuning": tuning})
-    eng.load_state_dict(MODEL_UNET_MEL, sd)
+    eng.load_state_dict(model, sd)
     eng.tol = TOL[precision]
     return eng
 
@@ -260,8 +263,12 @@ def test_precision_2_gives_precision_1_bits(unet_sd):
 def test_pool(engine, H, W, C):
     """F.avg_pool2d(2) with floor semantics on odd and even extents: ((a + b) + c) + d in fp32 is three roundings of partial sums no
     larger than |a| + |b| + |c| + |d| (the 0.25 is exact)."""
+    _pool_case(engine, H, W, C)
+
+
+def _pool_case(engine, H, W, C, model=MODEL_UNET_MEL, run=None):
     x = _src((B, H, W, C), 500 + H)
-    (y,), _, launches = engine.op_unet_piece("pool", [x], arg=C)
+    (y,), _, launches = (run or engine.op_unet_piece)("pool", [x], arg=C, model=model)
     assert y.shape == (B, H // 2, W // 2, C) and _families(launches) == ["small"]
     ref = F.avg_pool2d(nchw(x).double(), 2)
     _check(nchw(y.cpu()), ref, 3 * U32 * F.avg_pool2d(nchw(x).double().abs(), 2) + 2.0 ** -149, ("pool", H, W, C))
@@ -300,14 +307,19 @@ def test_prep_logmel(engine, negative):
 def test_prep_spec(engine):
     """(B, T, 1025) -> (B, Tpad, 1024): a copy without the last bin, zeros past each clip's frames."""
     for T, lens in ((70, None), (70, [70, 33]), (1, None)):
-        sp = _rand((B, T, 1025), 600 + T).abs()
-        Tpad = (T + 63) // 64 * 64
-        (x,), _, _ = engine.op_unet_piece("prep_spec", [sp], lens=lens)
-        ref = torch.zeros((B, Tpad, 1024))
-        for b in range(B):
-            L = T if lens is None else lens[b]
-            ref[b, :L] = sp[b, :L, :1024]
-        assert torch.equal(x.cpu(), ref), (T, lens)
+        _prep_spec_case(engine, T, lens)
+
+
+def _prep_spec_case(engine, T, lens, model=MODEL_UNET_MEL):
+    sp = _rand((B, T, 1025), 600 + T).abs()
+    Tpad = (T + 63) // 64 * 64
+    (x,), _, launches = engine.op_unet_piece("prep_spec", [sp], lens=lens, model=model)
+    ref = torch.zeros((B, Tpad, 1024))
+    for b in range(B):
+        L = T if lens is None else lens[b]
+        ref[b, :L] = sp[b, :L, :1024]
+    assert torch.equal(x.cpu(), ref), (T, lens)
+    return _families(launches)
 
 
 @pytest.mark.parametrize("T", [1, 70])
@@ -327,14 +339,125 @@ def test_final_mel(engine, unet_sd, T):
 
 def test_final_spec(engine, unet_sd):
     """The spectrogram model's epilogue (mode 1) on a narrow trunk: mag = after_conv2(y), re = mag cos, im = mag sin, last bin 0."""
-    T, W = 3, 40
-    y = _src((B, 64, W, 32), 800)
+    _final_spec_case(engine, unet_sd, 3, 40)
+
+
+def _final_spec_case(engine, sd, T, W, model=MODEL_UNET_MEL, run=None):
+    """Rows >= T of the padded trunk hold NaN: a finite output read rows < T only."""
+    Tpad = (T + 63) // 64 * 64
+    y = _src((B, Tpad, W, 32), 800)
+    y[:, T:] = float("nan")
     cos, sin = _rand((B, T, W + 1), 801), _rand((B, T, W + 1), 802)
-    (re, im), _, _ = engine.op_unet_piece("final", [y, cos, sin], arg=1)
-    w = unet_sd["after_conv2.weight"].double().reshape(32)
-    bias = unet_sd["after_conv2.bias"].double()
-    mag = F.pad((y[:, :T].double() * w).sum(-1) + bias, (0, 1))
-    S = F.pad((y[:, :T].double().abs() * w.abs()).sum(-1) + bias.abs(), (0, 1))
+    (re, im), _, launches = (run or engine.op_unet_piece)("final", [y, cos, sin], arg=1, model=model)
+    r = R.final_spec_mag(sd, y, T)
+    assert re.shape == im.shape == (B, T, W + 1)
     for got, aux, name in ((re, cos, "re"), (im, sin, "im")):
-        _check(got.cpu(), mag * aux.double(), (32 + 3) * U32 * S * aux.double().abs() + 2.0 ** -149, ("final spec", name))
+        _check(got.cpu(), r["ref"] * aux.double(), (32 + 3) * U32 * r["S"] * aux.double().abs() + 2.0 ** -149, ("final spec", name, T, W))
         assert (got[..., W] == 0).all(), name
+    return _families(launches)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the spectrogram model's geometry: trunk width 1024, pruned (even-width) upsamplers, the two-output epilogue
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Level l runs at (Tpad >> (l - 1), 1024 >> (l - 1)), the bottleneck at (1, 16) and (2, 16): every level tiles exactly in W (128 tiles
+# across at level 1), and plan_conv picks tile shapes no mel case gets (4 x 16, 2 x 32, 2 x 16, 1 x 128 with dead columns).  The shapes
+# are resunet_pieces_f64's SPEC_* lists, read off plan_chains.unet_geometry(MODEL_UNET_SPEC, 64 | 128); the references and the
+# per-element bound are the mel cases'.  B = 1 at (64, 1024) keeps the float64 convolutions of a case under a second each.
+@pytest.fixture(scope="module")
+def spec_sd():
+    from voicefixer_main_amd import synth
+    return synth.make_resunet_state_dict(2)
+
+
+@pytest.fixture(scope="module")
+def spec_engines(spec_sd):
+    """get(precision, tuning = 0): a handle with the spectrogram ResUNet's synthetic weights (those of test_gpu_plan_chains)."""
+    engines = {}
+
+    def get(precision, tuning=0):
+        if (precision, tuning) not in engines:
+            engines[precision, tuning] = _engine(precision, tuning, spec_sd, MODEL_UNET_SPEC)
+        return engines[precision, tuning]
+    yield get
+    for eng in engines.values():
+        eng.close()
+
+
+def test_spec_entry_block(engine, spec_engines, spec_sd):
+    """The entry block at (64, 1024): the fused IN1 launch, or k_conv_c1 + k_conv in fp32."""
+    eng = spec_engines(engine.precision)
+    p, _ = _mode(eng)
+    (H, W), = R.SPEC_FUSED_SHAPES
+    assert _entry_case(eng, spec_sd, H, W, MODEL_UNET_SPEC, B=1) == (["k_resblock_in1"] if p == 1 else ["small", "k_conv"])
+
+
+@pytest.mark.parametrize("piece,hw,batch", R.SPEC_FUSED_CASES, ids=[c[0] for c in R.SPEC_FUSED_CASES])
+def test_spec_fused_block(engine, spec_engines, spec_sd, piece, hw, batch):
+    """Level 1 at (64, 1024) -- the C = 32 identity blocks on k_block2d32, dec6.1's two sources with shortcut segments on k_resblock
+    SC2 -- and the C = 64 identity blocks at (32, 512) on k_resblock G2; in fp32 each is two k_conv launches."""
+    eng = spec_engines(engine.precision)
+    p, _ = _mode(eng)
+    (launches,) = _block_case(eng, spec_sd, piece, hw[0], hw[1], 900, model=MODEL_UNET_SPEC, B=batch)
+    want = {"dec6.1": ["k_resblock_two_src"], "enc2.2": ["k_resblock"], "dec5.2": ["k_resblock"]}.get(piece, ["k_block2d32"])
+    assert _families(launches) == (["k_conv", "k_conv"] if p == 0 else want), (piece, hw, launches)
+
+
+def test_spec_level1_block_on_16x16_tiles(spec_engines, spec_sd):
+    """VFX_TUNE_OLD_BLOCK2D at (64, 1024): the C = 32 identity block on k_resblock's 16 x 16 h tiles."""
+    from voicefixer_main_amd import _lib
+    piece, (H, W), batch = R.SPEC_OLD_BLOCK2D_CASE
+    (launches,) = _block_case(spec_engines(1, _lib.TUNE_OLD_BLOCK2D), spec_sd, piece, H, W, 910, model=MODEL_UNET_SPEC, B=batch)
+    assert _families(launches) == ["k_resblock"], launches
+
+
+@pytest.mark.parametrize("piece", sorted(R.SPEC_DEEP_CASES))
+def test_spec_two_launch_block(engine, spec_engines, spec_sd, piece):
+    """Every deep block at its spectrogram level shapes for Tpad = 64 and 128 with short_clip 1, 0 and -2, whatever ksplit and tile
+    shape the planner picks there."""
+    eng = spec_engines(engine.precision)
+    for i, (H, W) in enumerate(R.SPEC_DEEP_CASES[piece]):
+        for launches in _block_case(eng, spec_sd, piece, H, W, 920 + i, short_clips=R.SHORT_CLIPS, model=MODEL_UNET_SPEC):
+            assert _families(launches) == ["k_conv", "k_conv"] and launches[0]["out_act"] and not launches[1]["out_act"], (piece, H, W, launches)
+
+
+SPEC_SPLIT_K = {1, 2, 4, 8}   # what the planner reaches over SPEC_DEEP_CASES x SHORT_CLIPS: every factor it has
+
+
+def test_spec_deep_cases_split_k(engine):
+    """The spectrogram cases above run ksplit 1, 2, 4 and 8 -- the planner's whole set, as the mel cases do -- each with an activated
+    output and with shortcut segments plus bias, on this handle's precision and tuning."""
+    act, shortcut = R.splitk_coverage(lambda piece, H, W, sc: engine.plan_unet_piece(piece, B, H, W, short_clip=sc, precision=engine.cfg.precision,
+                                                                                     tuning=engine.cfg.tuning), R.SPEC_DEEP_CASES)
+    assert act == SPEC_SPLIT_K and shortcut == SPEC_SPLIT_K, (act, shortcut)
+
+
+@pytest.mark.parametrize("d", sorted(R.SPEC_UP_CASES))
+def test_spec_upsampler(engine, spec_engines, spec_sd, d):
+    """Every decoder's pruned-width ConvTranspose2d at the input shape the spectrogram chain gives it, (1, 16) -> (2, 32) up to
+    (32, 512) -> (64, 1024): one row of input is the four-parity fallback, the others one launch of four phases."""
+    H, W = R.SPEC_UP_CASES[d]
+    assert _up_case(spec_engines(engine.precision), spec_sd, d, H, W, True, 930 + d, MODEL_UNET_SPEC) == (["k_conv"] * 4 if H == 1 else ["k_conv_phased"])
+
+
+def test_spec_upsampler_odd_width(engine, spec_engines, spec_sd):
+    """The unpruned width at a wide shape: (16, 256) -> (32, 513)."""
+    d, (H, W) = R.SPEC_UP_WIDE_UNPRUNED
+    assert _up_case(spec_engines(engine.precision), spec_sd, d, H, W, False, 940, MODEL_UNET_SPEC) == ["k_conv_phased"]
+
+
+@pytest.mark.parametrize("H,W,C", R.SPEC_POOL_CASES)
+def test_spec_pool(engine, spec_engines, H, W, C):
+    _pool_case(spec_engines(engine.precision), H, W, C, MODEL_UNET_SPEC)
+
+
+@pytest.mark.parametrize("T", R.SPEC_FINAL_T)
+def test_spec_final(engine, spec_engines, spec_sd, T):
+    """The two-output epilogue at W = 1024 on rows < T of a Tpad = 64 and of a Tpad = 128 trunk; the last bin exactly 0."""
+    assert _final_spec_case(spec_engines(engine.precision), spec_sd, T, R.SPEC_W0, MODEL_UNET_SPEC) == ["small"]
+
+
+def test_spec_prep_spec(engine, spec_engines):
+    """T = 130 (Tpad = 192) with per-clip frame counts."""
+    T, lens = R.SPEC_PREP_CASE
+    assert _prep_spec_case(spec_engines(engine.precision), T, lens, MODEL_UNET_SPEC) == ["small"]

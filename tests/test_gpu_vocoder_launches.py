@@ -54,7 +54,7 @@ def _lens_for(B, T):
     return [T, max(1, T - 1 - (T // 3)), 1][:B]
 
 
-def _run_upsample(eng, p, Cin, s, T, B, seed, src_act, form, lens):
+def _run_upsample(eng, p, Cin, s, T, B, seed, src_act, form, lens, run=None):
     """form: 'raw' fp32 y, 'act' y activated with res_slope (beside raw unless the trunk is fp16), 'trunk' the fp16 trunk (slope 1)."""
     Cout = Cin // 2
     x = _rand((B, T, Cin), seed)
@@ -64,7 +64,7 @@ def _run_upsample(eng, p, Cin, s, T, B, seed, src_act, form, lens):
     want_raw = form in ("raw", "act+raw")
     act_slope = {"raw": None, "act": RES_SLOPE, "act+raw": RES_SLOPE, "trunk": 1.0}[form]
     eng.take_flags()
-    y, ya, up16 = eng.op_voc_upsample(x, w.numpy(), b.numpy(), s, UP_SLOPE, src_act=src_act, want_raw=want_raw, act_slope=act_slope,
+    y, ya, up16 = (run or eng.op_voc_upsample)(x, w.numpy(), b.numpy(), s, UP_SLOPE, src_act=src_act, want_raw=want_raw, act_slope=act_slope,
                                       lens=lens)
     assert eng.take_flags() == 0, ("a device flag was raised on O(1) data", Cin, s, T, B)
     tol = eng.tol['conv']
@@ -146,7 +146,7 @@ def test_k_up16_matches_phased_k_conv_bitwise(Cin):
 # the conv1d builder
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _conv_case(eng, p, Cin, Cout, T, B, K, dil, seed, *, reflect=False, src_act=False, act=0, slope=1.0, residual=False,
-               residual_act=False, want_raw=True, next_act=0, next_slope=1.0, lens=None):
+               residual_act=False, want_raw=True, next_act=0, next_slope=1.0, lens=None, run=None):
     x = _rand((B, T, Cin), seed)
     w = _rand((Cout, Cin, K), seed + 1, 1.0 / np.sqrt(K * Cin))
     b = _rand((Cout,), seed + 2, 0.1)
@@ -154,7 +154,7 @@ def _conv_case(eng, p, Cin, Cout, T, B, K, dil, seed, *, reflect=False, src_act=
     if res is not None:
         res[:, ::2, 1::3] = -res[:, ::2, 1::3].abs()   # negative trunk values: the inverted LeakyReLU branch
     eng.take_flags()
-    y, ya = eng.op_voc_conv1d(x, w.numpy(), b.numpy(), dil=dil, reflect=reflect, src_act=src_act, act=act, slope=slope, residual=res,
+    y, ya = (run or eng.op_voc_conv1d)(x, w.numpy(), b.numpy(), dil=dil, reflect=reflect, src_act=src_act, act=act, slope=slope, residual=res,
                               residual_act=residual_act, want_raw=want_raw, next_act=next_act, next_slope=next_slope, lens=lens)
     assert eng.take_flags() == 0, ("a device flag was raised on O(1) data", Cin, Cout, T, K, dil)
     tol = eng.tol['conv']
@@ -244,23 +244,27 @@ def test_voc_final(engine, x_f16):
     """tanh(conv1d(ReflectionPad1d(3)(LeakyReLU(x, 0.2)))) to one channel on an fp32 or fp16 trunk, with and without per-clip lengths:
     each clip reflects at its own end and writes nothing past it.  The tail is plain fp32 arithmetic (n = 7 C products)."""
     for i, (B, T, C, lens) in enumerate(((1, 4, 64, None), (1, 1000, 64, None), (3, 777, 64, [777, 500, 4]), (2, 300, 128, [300, 13]))):
-        x = _rand((B, T, C), 800 + i)
-        w = _rand((1, C, 7), 850 + i, 1.0 / np.sqrt(7 * C))
-        bias = 0.05
-        engine.take_flags()
-        wav = engine.op_voc_final(x, w.numpy(), bias, UP_SLOPE, x_f16=x_f16, lens=lens).cpu()
-        assert engine.take_flags() == 0, ("a device flag was raised on O(1) data", B, T, C)
-        xs = x.half().float() if x_f16 else x
-        for b_ in range(B):
-            L = T if lens is None else lens[b_]
-            a = F.pad(F.leaky_relu(xs[b_:b_ + 1, :L].double(), UP_SLOPE).permute(0, 2, 1), (3, 3), mode="reflect")
-            pre = F.conv1d(a, w.double())[0, 0] + bias
-            S = F.conv1d(a.abs(), w.double().abs())[0, 0]
-            ref = torch.tanh(pre)
-            bar = (7 * C + 2) * U32 * (S + abs(bias)) + 8 * U32
-            bar = torch.minimum(bar, torch.full_like(bar, engine.tol['conv']))
-            _check(wav[b_, :L], ref, bar, ("tail", B, T, C, b_))
-            assert torch.isnan(wav[b_, L:]).all(), ("tail written past the clip's end", b_)
+        _final_case(engine, B, T, C, lens, x_f16, 800 + i)
+
+
+def _final_case(engine, B, T, C, lens, x_f16, seed, run=None):
+    x = _rand((B, T, C), seed)
+    w = _rand((1, C, 7), seed + 50, 1.0 / np.sqrt(7 * C))
+    bias = 0.05
+    engine.take_flags()
+    wav = (run or engine.op_voc_final)(x, w.numpy(), bias, UP_SLOPE, x_f16=x_f16, lens=lens).cpu()
+    assert engine.take_flags() == 0, ("a device flag was raised on O(1) data", B, T, C)
+    xs = x.half().float() if x_f16 else x
+    for b_ in range(B):
+        L = T if lens is None else lens[b_]
+        a = F.pad(F.leaky_relu(xs[b_:b_ + 1, :L].double(), UP_SLOPE).permute(0, 2, 1), (3, 3), mode="reflect")
+        pre = F.conv1d(a, w.double())[0, 0] + bias
+        S = F.conv1d(a.abs(), w.double().abs())[0, 0]
+        ref = torch.tanh(pre)
+        bar = (7 * C + 2) * U32 * (S + abs(bias)) + 8 * U32
+        bar = torch.minimum(bar, torch.full_like(bar, engine.tol['conv']))
+        _check(wav[b_, :L], ref, bar, ("tail", B, T, C, b_))
+        assert torch.isnan(wav[b_, L:]).all(), ("tail written past the clip's end", b_)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -282,8 +282,8 @@ void finish_params(TapConvParams& p) {
   VFX_CHECK((int64_t)p.B * p.Hg * p.Wg < (int64_t)1 << 31, "conv: too many output pixels");
   VFX_CHECK((int64_t)p.B * p.out_img_stride < (int64_t)1 << 31, "conv: too many output pixels");
   VFX_CHECK((int64_t)p.B * p.in_img_stride < (int64_t)1 << 31, "conv: too many input pixels");
-  for (int s = 0; s < p.nseg; ++s)  // the kernel addresses a source with 32-bit byte offsets
-    VFX_CHECK((int64_t)p.B * p.in_img_stride * p.seg[s].C * 4 < ((int64_t)1 << 32) - 4096,
+  for (int s = 0; s < p.nseg; ++s)  // the kernel addresses a source with 32-bit byte offsets: its bytes as build_stages counts them
+    VFX_CHECK((int64_t)p.B * p.in_img_stride * p.seg[s].C * (stage_channels(p, p.seg[s]) == 64 ? 2 : 4) < ((int64_t)1 << 32) - 4096,
               "conv: source tensor of segment %d exceeds 4 GiB", s);
   VFX_CHECK(p.out || p.out_act, "conv: no output");
   VFX_CHECK(!p.residual_act || (p.hionly && !p.residual && p.Cout % 4 == 0 && p.residual_inv_slope >= 1.f),
